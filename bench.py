@@ -7,7 +7,7 @@ guidance, scale 5) + VAE decode.  Inputs (image / mask / exempl
 noise) are resident in HBM before the timed region.  Weights: name-seeded random init of the
 configs/v1.yaml architecture (no checkpoint exists offline).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (driver, N > 1)
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
@@ -18,6 +18,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
   cpu_baseline the CPU oracle (a port: oracle/pbe_oracle.py, fp32 torch) timed on this box's host
                cores on a bounded sample (warm-up + 3 CFG U-Net pairs, median; VAE enc/dec + CLIP for one image),
                extrapolated to images/sec; CPU model and physical core count reported.  Rank 0, N = 1 only.
+
+--dump-outputs DIR writes what the LAST timed step returned (rank 0) as DIR/<name>.npy, float32: the `inpaint` dict (image, latent,
+c, z_inpaint, mask_lat; rank 0's own shard) and image_u8, the uint8 images the step hands back (all ranks' when N > 1).  Inputs and
+weights are seeded, so the same arguments give the same inputs on every run and two builds can be compared file for file.
 """
 from __future__ import annotations
 
@@ -50,9 +54,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-batch16", action="store_true", help="skip the extra BASELINE configs[2]-size (batch 16) measurement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="tests only: workers rendezvous (gloo), all-reduce one number and rank 0 prints a JSON line; no GPU work")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def self_launch(a) -> int:
@@ -99,6 +108,30 @@ import torch.distributed as dist  # noqa: E402
 # algorithmic FLOP per image at the headline config = 85.08e12 (51*2*796.94 + 1116.7 + 2514.5 + 155.5 + 0.13 GFLOP); main() computes it
 MFMA_PEAK_TFLOPS = 2500.0          # dense fp16/bf16, MI355X_MICROARCH.md "Chip-level parameters"
 HBM_PEAK_TBS = 8.0                 # HBM3E spec, same table (6.3 TB/s is what a streaming copy reaches)
+
+
+DUMP_BYTES = 64_000_000 - 64 * 1024       # --dump-outputs: array payload cap (64 MB in all, .npy headers included)
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> tensor, written as path/<name>.npy in float32.  Arrays that fit their share of DUMP_BYTES are written whole;
+    a larger one is cut to a fixed, seeded sample of its flattened elements (sorted indices from one seed: identical for identical
+    shapes, so two runs stay comparable element for element).  Returns {name: (full shape, elements written)}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    left, info = DUMP_BYTES, {}
+    names = sorted(host, key=lambda k: host[k].size)                  # small arrays first: they are kept whole
+    for i, k in enumerate(names):
+        x = host[k]
+        share = left // 4 // (len(names) - i)
+        flat = x.reshape(-1)
+        if flat.size > share:
+            flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, share, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(flat if flat.size < x.size else x, dtype=np.float32))
+        left -= 4 * flat.size
+        info[k] = (list(x.shape), int(flat.size))
+    return info
 
 
 def log(msg):
@@ -276,7 +309,7 @@ def main():
         out = inpaint(model, inp["image"], inp["mask"], inp["ref"], steps=a.plms_steps, scale=a.scale, x_T=inp["x_T"],
                       post_eps=inp["post_eps"], timings=timings)
         u8 = (out["image"] * 255.0).round().to(torch.uint8)
-        return gather_images(u8) if world > 1 else u8
+        return out, (gather_images(u8) if world > 1 else u8)
 
     def fence():
         if world > 1:
@@ -289,7 +322,7 @@ def main():
         fence()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            one_step()
+            last = one_step()
         torch.cuda.synchronize()
         own_elapsed = time.perf_counter() - t0                     # this rank's K steps, before it waits for the others
         fence()
@@ -305,6 +338,11 @@ def main():
             t = torch.tensor([elapsed], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        if a.dump_outputs and rank == 0:                          # before the passes below reuse any buffer
+            out, u8 = last
+            info = dump_outputs(a.dump_outputs, {**out, "image_u8": u8})
+            log(f"outputs of the last timed step -> {a.dump_outputs}: " + ", ".join(f"{k} {s} ({n} written)" for k, (s, n) in info.items()))
+        del last
 
         # ---- separate passes (outside the timed region): stage split and per-kernel-class events ----
         stage = {}
