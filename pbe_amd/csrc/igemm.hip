@@ -1,5 +1,5 @@
 // Host side of the implicit-GEMM entry points: descriptor checks, plan queries, developer knobs.  The kernel and its planner are in
-// igemm_kernel.h; the instantiations in igemm_{dense,conv,halo,f8,ex}.hip.
+// igemm_kernel.h (tile table kTiles); the instantiations in igemm_{dense,conv,halo,f8,ex*}.hip.
 #include "igemm_kernel.h"
 
 #ifdef PBE_STAMPS
@@ -92,16 +92,17 @@ extern "C" int pbe_gemm_f16(const pbe_gemm_desc* d, pbe_stream_t stream) {
     const int rc = fill_gemm(d, p, "pbe_gemm_f16");
     if (rc != PBE_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (d->operand_dtype == PBE_DTYPE_F8E4M3) pbe_dispatch_f8(p, d->batch, s, d->tile_cfg);
-    else if (ex_needed(p)) pbe_dispatch_ex(p, d->batch, s, d->tile_cfg);
-    else pbe_dispatch_dense(p, d->batch, s, d->workspace ? d->workspace_bytes : 0, d->tile_cfg);
+    const int lrc = d->operand_dtype == PBE_DTYPE_F8E4M3 ? pbe_dispatch_f8(p, d->batch, s, d->tile_cfg)
+                    : ex_needed(p)                       ? pbe_dispatch_ex(p, d->batch, s, d->tile_cfg)
+                                                         : pbe_dispatch_dense(p, d->batch, s, d->workspace ? d->workspace_bytes : 0, d->tile_cfg);
+    if (lrc != PBE_OK) return lrc;
     PBE_LAUNCH_CHECK("pbe_gemm_f16");
     return PBE_OK;
 }
 
 static void report_plan(const IGemmP& p, int batch, size_t ws_bytes, int want_cfg, int32_t* out, int mode) {
     const Plan pl = plan_igemm(p, batch, ws_bytes, want_cfg, mode);
-    const TileCfg& t = kCfg[pl.cfg];
+    const TileCfg& t = kTiles[pl.cfg];
     out[0] = pl.cfg; out[1] = pl.splits; out[2] = t.bm; out[3] = t.bn;
     out[4] = cdiv(p.M, t.bm) * cdiv(p.N, t.bn) * batch * pl.splits;                       // workgroups launched
     out[5] = 0;
@@ -168,7 +169,8 @@ extern "C" int pbe_conv3x3_f16(const pbe_conv3x3_desc* d, pbe_stream_t stream) {
     const int rc = fill_conv(d, p, "pbe_conv3x3_f16");
     if (rc != PBE_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    pbe_dispatch_conv(p, p.phase ? 4 : 1, s, d->workspace ? d->workspace_bytes : 0, d->tile_cfg);
+    const int lrc = pbe_dispatch_conv(p, p.phase ? 4 : 1, s, d->workspace ? d->workspace_bytes : 0, d->tile_cfg);
+    if (lrc != PBE_OK) return lrc;
     PBE_LAUNCH_CHECK("pbe_conv3x3_f16");
     return PBE_OK;
 }

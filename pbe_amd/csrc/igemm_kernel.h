@@ -31,6 +31,7 @@
 //     as a lower clock.
 #pragma once
 #include <type_traits>
+#include <utility>
 #include "common.h"
 #include "../../include/pbe_hip.h"
 
@@ -1238,39 +1239,59 @@ static __global__ void __launch_bounds__(256) splitk_reduce_kernel(const IGemmP 
 // ---- host side --------------------------------------------------------------------------------
 static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 struct Plan { int cfg; int splits; };
-struct TileCfg { int bm, bn, nwm, nwn, slots_per_cu; double eff; int hpa; };      // hpa > 0: halo-resident conv tile (MODE 2), rows of its halo image
-// eff = relative per-FLOP efficiency of the tile when the chip is full (ordered by staged bytes per FLOP).
-// Ring depth per tile (k-tiles of 64): the deepest that fits the LDS share of the tile's workgroups per CU.
-static const TileCfg kCfg[] = {
-    {256, 256, 2, 4, 1, 1.00},           // 0: S = 2, 128 KiB
-    {256, 128, 4, 2, 1, 0.82},           // 1: S = 3, 144 KiB
-    {128, 256, 2, 4, 1, 0.75},           // 2: S = 3, 144 KiB
-    {128, 128, 2, 2, 2, 0.88},           // 3: S = 2,  64 KiB, 4 waves: two workgroups per CU
-    {128, 64, 2, 2, 3, 0.65},            // 4: S = 2,  48 KiB
-    {64, 128, 2, 2, 3, 0.65},            // 5: S = 2,  48 KiB
-    {64, 64, 2, 2, 4, 0.60},             // 6: S = 2,  32 KiB
-    {256, 320, 2, 4, 1, 1.05},           // 7: S = 2, 144 KiB: N = 320 / 640 / 960 / 1280 without column padding (142 FLOP per staged byte)
-    {128, 320, 2, 4, 1, 0.96},           // 8: S = 2, 112 KiB: same, half the rows: fills the chip when M / 256 < 256 tiles
-    {128, 160, 2, 2, 2, 0.90},           // 9: S = 2,  72 KiB, 4 waves: two workgroups per CU overlap each other's prologue / epilogue
+// Forms a tile is instantiated for (TileCfg.forms): the dispatch of each form launches exactly these rows, the planner picks among them.
+enum : unsigned {
+    F_DENSE = 1u << 0,      // MODE 0 (igemm_dense.hip)
+    F_CONV = 1u << 1,       // MODE 1 gather (igemm_conv.hip)
+    F_HALO = 1u << 2,       // MODE 2 halo-resident conv (igemm_halo.hip); hpa = rows of its halo image
+    F_EX = 1u << 3,         // extended epilogue (igemm_ex_{ln,st,qkv,all}.hip)
+    F_F8 = 1u << 4,         // fp8 operands (igemm_f8.hip)
+    F_ASTAT = 1u << 5,      // A-stationary (igemm_astat.hip), where pbe_astat_ok() holds
+    F_FORCED = 1u << 6,     // only through desc.tile_cfg / the tuned table, never by the heuristic
+};
+// s = ring depth in k-tiles of 64 (the weight ring of the halo / A-stationary tiles): the deepest that fits the LDS share of the tile's
+// workgroups per CU.  eff = relative per-FLOP efficiency of the tile when the chip is full (ordered by staged bytes per FLOP); eff_shallow
+// the same for shallow-K problems (< 10 k-tiles), dominated by the prologue / epilogue.  Both efficiency columns are fitted to the 472
+// measured shapes of profiles/r01_autotune_report.txt (the heuristic then costs 4 % over the best tile per shape, 12 % before the fit);
+// pbe_amd/tuned_mi355x.json overrides them per shape (desc.tile_cfg), so they only decide shapes outside the table.
+// f8 = the tile an fp8-operand problem runs when the planner picks this one (the fp8 form instantiates a subset of the dense tiles).
+struct TileCfg { int bm, bn, nwm, nwn, s, slots_per_cu; double eff, eff_shallow; int hpa; unsigned forms; int f8; };
+static constexpr TileCfg kTiles[] = {
+    {256, 256, 2, 4, 2, 1, 1.00, 0.82, 0, F_DENSE | F_CONV, 3},                     // 0: 128 KiB
+    {256, 128, 4, 2, 3, 1, 0.82, 0.72, 0, F_DENSE | F_CONV, 3},                     // 1: 144 KiB
+    {128, 256, 2, 4, 3, 1, 0.75, 0.66, 0, F_DENSE | F_CONV, 3},                     // 2: 144 KiB
+    {128, 128, 2, 2, 2, 2, 0.88, 1.00, 0, F_DENSE | F_CONV | F_EX | F_F8, 3},       // 3:  64 KiB, 4 waves: two workgroups per CU
+    {128, 64, 2, 2, 2, 3, 0.65, 0.84, 0, F_DENSE | F_CONV | F_EX | F_F8, 4},        // 4:  48 KiB
+    {64, 128, 2, 2, 2, 3, 0.65, 0.85, 0, F_DENSE | F_CONV | F_EX, 6},               // 5:  48 KiB
+    {64, 64, 2, 2, 2, 4, 0.60, 0.80, 0, F_DENSE | F_CONV | F_EX | F_F8, 6},         // 6:  32 KiB
+    {256, 320, 2, 4, 2, 1, 1.05, 0.80, 0, F_DENSE | F_CONV, 8},                     // 7: 144 KiB: N = 320 / 640 / 960 / 1280 without column padding (142 FLOP per staged byte)
+    {128, 320, 2, 4, 2, 1, 0.96, 0.95, 0, F_DENSE | F_CONV | F_EX | F_F8, 8},       // 8: 112 KiB: same, half the rows: fills the chip when M / 256 < 256 tiles
+    {128, 160, 2, 2, 2, 2, 0.90, 0.97, 0, F_DENSE | F_CONV | F_EX | F_F8, 9},       // 9:  72 KiB, 4 waves: two workgroups per CU overlap each other's prologue / epilogue
     // halo-resident 3x3 conv tiles (stride 1, pad 1, image width 8 .. 128 = tile width): only the weights stream per k-tile
-    {256, 160, 4, 2, 1, 1.40, 392},      // 10: weight ring 3, 160 KiB: 256 pixels (4 rows at 64x64) x 160 channels, 8 waves, ping-pong
-    {128, 160, 4, 2, 1, 1.20, 264},      // 11: weight ring 3, 128 KiB: 128 pixels x 160 channels
-    {128, 320, 2, 4, 1, 1.25, 264},      // 12: weight ring 2, 149 KiB: 128 pixels x 320 channels
-    {256, 128, 4, 2, 1, 1.30, 392},      // 13: weight ring 3, 148 KiB: channel counts that are multiples of 128 only, ping-pong
-    {128, 128, 4, 2, 1, 1.10, 392},      // 14: weight ring 3, 148 KiB: one 128-pixel row of a 128-wide image (VAE)
+    {256, 160, 4, 2, 3, 1, 1.40, 1.40, 392, F_HALO, 9},                   // 10: 160 KiB: 256 pixels (4 rows at 64x64) x 160 channels, 8 waves, ping-pong
+    {128, 160, 4, 2, 3, 1, 1.20, 1.20, 264, F_HALO, 9},                   // 11: 128 KiB: 128 pixels x 160 channels
+    {128, 320, 2, 4, 2, 1, 1.25, 1.25, 264, F_HALO, 9},                   // 12: 149 KiB: 128 pixels x 320 channels
+    {256, 128, 4, 2, 3, 1, 1.30, 1.30, 392, F_HALO, 9},                   // 13: 148 KiB: channel counts that are multiples of 128 only, ping-pong
+    {128, 128, 4, 2, 3, 1, 1.10, 1.10, 392, F_HALO, 9},                   // 14: 148 KiB: one 128-pixel row of a 128-wide image (VAE)
     // deep-ring forms of the small dense tiles, ONE workgroup per CU: for grids of <= 256 workgroups (M <= 2 048 rows) the second
     // workgroup of a CU never arrives, and S = 2 then leaves one k-tile in flight per CU - a k-tile per DMA round trip
-    {128, 128, 2, 2, 1, 0.50},           // 15: S = 4, 128 KiB
-    {128, 64, 2, 2, 1, 0.40},            // 16: S = 4,  96 KiB
-    {64, 64, 2, 2, 2, 0.38},             // 17: S = 4,  64 KiB
-    {128, 160, 2, 2, 1, 0.52},           // 18: S = 4, 144 KiB
+    {128, 128, 2, 2, 4, 1, 0.50, 0.50, 0, F_DENSE | F_CONV | F_EX, 3},              // 15: 128 KiB
+    {128, 64, 2, 2, 4, 1, 0.40, 0.40, 0, F_DENSE | F_CONV | F_EX, 4},               // 16:  96 KiB
+    {64, 64, 2, 2, 4, 2, 0.38, 0.38, 0, F_DENSE | F_CONV | F_EX, 6},                // 17:  64 KiB
+    {128, 160, 2, 2, 4, 1, 0.52, 0.52, 0, F_DENSE | F_CONV | F_EX, 9},              // 18: 144 KiB
     // A-stationary persistent tiles (igemm_astat.hip): K = 320 GEGLU projection with the LayerNorm fold, A block in registers, 4 waves,
-    // two workgroups per CU; never picked by the heuristic (eff 0), only through desc.tile_cfg / the tuned table where pbe_astat_ok() holds
-    {128, 128, 4, 1, 2, 0.0},            // 19: weight ring 48 KiB
-    {128, 160, 4, 1, 2, 0.0},            // 20: weight ring 60 KiB (256 registers, 14 spilled)
+    // two workgroups per CU; only through desc.tile_cfg / the tuned table where pbe_astat_ok() holds
+    {128, 128, 4, 1, 3, 2, 0.0, 0.0, 0, F_ASTAT | F_FORCED, 9},           // 19: weight ring 48 KiB
+    {128, 160, 4, 1, 3, 2, 0.0, 0.0, 0, F_ASTAT | F_FORCED, 9},           // 20: weight ring 60 KiB (256 registers, 14 spilled)
     // dense 8-wave tile with 160 columns: 6.5 LDS-DMA pieces per wave and k-tile against 40 MFMAs (the 4-wave 128x160 tile: 9)
-    {256, 160, 4, 2, 1, 0.0}};           // 21: S = 3, 156 KiB (MODE 0 only; through the tuned table)
-static const int kNCfg = sizeof(kCfg) / sizeof(kCfg[0]);
+    {256, 160, 4, 2, 3, 1, 0.0, 0.0, 0, F_DENSE | F_FORCED, 9}};          // 21: 156 KiB
+static constexpr int kNCfg = sizeof(kTiles) / sizeof(kTiles[0]);
+static constexpr bool f8_column_ok() {      // every row maps to a tile the fp8 form instantiates
+    for (const TileCfg& t : kTiles)
+        if (!(kTiles[t.f8].forms & F_F8)) return false;
+    return true;
+}
+static_assert(f8_column_ok(), "kTiles: an f8 column names a tile without F_F8");
 
 #ifdef PBE_STAMPS
 extern unsigned long long* g_pbe_stamps;
@@ -1287,23 +1308,27 @@ static inline int no_empty_slices(int nk, int granule, int s) {
     return (units + per - 1) / per;
 }
 
-static int splits_for(const IGemmP& p, const TileCfg& c, int batch, size_t ws_bytes, long tiles) {
-    if (!g_pbe_allow_splitk || batch != 1 || !p.ws || (p.N & 3) || (p.ldc & 3) || (p.resid && (p.ldr & 3))) return 1;
-    const int nk = (p.K + 63) >> 6;                          // k-tiles of 64
-    const long slots = 256L * c.slots_per_cu;
-    if (tiles * 4 > slots * 3 || nk < 8) return 1;           // grid already fills >= 75 % of the chip
-    int s = (int)((slots * 5 / 4 + tiles - 1) / tiles);
+// Split-K at all: batch 1, a workspace, and the 4-column rows of C (and the residual) the reduce kernel writes (reads)
+static inline bool splitk_ok(const IGemmP& p, int batch) {
+    return g_pbe_allow_splitk && batch == 1 && p.ws && !(p.N & 3) && !(p.ldc & 3) && !(p.resid && (p.ldr & 3));
+}
+
+// Clamp a split-K factor to what the problem allows: >= 4 k-tiles of 64 per slice, slabs fit the workspace, no empty slice
+static int clamp_splits(const IGemmP& p, const TileCfg& c, size_t ws_bytes, int s) {
+    const int nk = (p.K + 63) >> 6;
     if (s > nk / 4) s = nk / 4;
-    if (s > 32) s = 32;
     while (s > 1 && (size_t)s * p.M * p.N * sizeof(float) > ws_bytes) --s;
     return no_empty_slices(nk, c.hpa ? 9 : 1, s);
 }
 
-// Shallow-K problems (< 20 k-tiles) are dominated by the prologue / epilogue, deep-K problems by staged bytes per
-// FLOP.  Both efficiency rows are fitted to the 472 measured shapes of profiles/r01_autotune_report.txt (the
-// heuristic then costs 4 % over the best tile per shape, 12 % before the fit).  pbe_amd/tuned_mi355x.json overrides
-// this per shape (desc.tile_cfg), so these rows only decide shapes outside the table.
-static const double kEffShallow[] = {0.82, 0.72, 0.66, 1.00, 0.84, 0.85, 0.80, 0.80, 0.95, 0.97, 1.4, 1.2, 1.25, 1.3, 1.1, 0.5, 0.4, 0.38, 0.52, 0.0, 0.0, 0.0};
+static int splits_for(const IGemmP& p, const TileCfg& c, int batch, size_t ws_bytes, long tiles) {
+    if (!splitk_ok(p, batch)) return 1;
+    const int nk = (p.K + 63) >> 6;                          // k-tiles of 64
+    const long slots = 256L * c.slots_per_cu;
+    if (tiles * 4 > slots * 3 || nk < 8) return 1;           // grid already fills >= 75 % of the chip
+    const int s = (int)((slots * 5 / 4 + tiles - 1) / tiles);
+    return clamp_splits(p, c, ws_bytes, s > 32 ? 32 : s);
+}
 
 // Can this conv run as a halo-resident tile of bm pixels with a halo image of hpa rows?  Returns the image rows per tile (0: no).
 static int halo_rows(const IGemmP& p, int mode, int bm, int hpa) {
@@ -1318,9 +1343,7 @@ static int halo_rows(const IGemmP& p, int mode, int bm, int hpa) {
     return th;
 }
 
-// dense tiles that are instantiated with the extended epilogue (EX): the one-pass 4-wave tiles and 128x320
-static const unsigned kExCfgs = (1u << 3) | (1u << 4) | (1u << 5) | (1u << 6) | (1u << 8) | (1u << 9) | (1u << 15) | (1u << 16) | (1u << 17) | (1u << 18) | (3u << 19);
-bool pbe_astat_ok(const IGemmP& p, int batch, int cfg);      // igemm_astat.hip: can tile 19 run this problem?
+bool pbe_astat_ok(const IGemmP& p, int batch, int cfg);      // igemm_astat.hip: can tile 19 / 20 run this problem?
 static inline bool ex_needed(const IGemmP& p) { return p.alpha_cols > 0 || p.ln_stat || p.rstat || p.vt; }
 
 // want_cfg: -1 = heuristic; else (tile config index) | (split-K factor << 8), factor 0 = heuristic factor for that tile.
@@ -1334,35 +1357,31 @@ static Plan plan_igemm(const IGemmP& p, int batch, size_t ws_bytes, int want_cfg
     const int forced = (want >= 0 && (want & 255) < kNCfg) ? (want & 255) : -1;
     const int want_splits = want >= 0 ? (want >> 8) & 255 : 0;
     const bool shallow = ((p.K + 63) >> 6) < 10;
+    // candidates: the tiles of the problem's form (fp8 operands score the dense tiles and run the f8 column of the pick, below)
+    const unsigned forms = mode == 1 ? F_CONV | F_HALO : ex_needed(p) ? F_EX | F_ASTAT : F_DENSE;
     for (int c = 0; c < kNCfg; ++c) {
         if (forced >= 0 && c != forced) continue;
-        TileCfg t = kCfg[c];
-        if (c >= 19 && (forced != c || mode != 0 || (c < 21 && !pbe_astat_ok(p, batch, c)))) continue;
-        if (ex_needed(p) && (!(kExCfgs >> c & 1) || (p.vt && p.vt_col0 % t.bn))) continue;   // extended epilogue: its tiles only, V^T columns start on a tile
+        const TileCfg& t = kTiles[c];
+        if (!(t.forms & forms) || ((t.forms & F_FORCED) && forced != c)) continue;
+        if ((t.forms & F_ASTAT) && !pbe_astat_ok(p, batch, c)) continue;
+        if (p.vt && p.vt_col0 % t.bn) continue;                              // extended epilogue: V^T columns start on a tile
         if (t.hpa && !halo_rows(p, mode, t.bm, t.hpa)) continue;              // a forced halo tile that does not apply falls back below
         if (t.hpa && p.N % 8) continue;
-        if (shallow) t.eff = kEffShallow[c];
         const long tm = (p.M + t.bm - 1) / t.bm, tn = (p.N + t.bn - 1) / t.bn;
         const long tiles = tm * tn * batch;
-        int sp = splits_for(p, t, batch, ws_bytes, tiles);
-        if (forced >= 0 && want_splits > 0) {
-            const int nk = (p.K + 63) >> 6;
-            sp = want_splits;
-            if (!g_pbe_allow_splitk || batch != 1 || !p.ws || (p.N & 3) || (p.ldc & 3) || (p.resid && (p.ldr & 3))) sp = 1;
-            if (sp > nk / 4) sp = nk / 4;
-            while (sp > 1 && (size_t)sp * p.M * p.N * sizeof(float) > ws_bytes) --sp;
-            sp = no_empty_slices(nk, t.hpa ? 9 : 1, sp);
-        }
+        const int sp = forced >= 0 && want_splits > 0 ? (splitk_ok(p, batch) ? clamp_splits(p, t, ws_bytes, want_splits) : 1)
+                                                      : splits_for(p, t, batch, ws_bytes, tiles);
         const double useful = (double)p.M * p.N * batch / ((double)tiles * t.bm * t.bn);
         const double blocks = (double)tiles * sp, slots = 256.0 * t.slots_per_cu;
         const double rounds = (double)((long)((blocks + slots - 1) / slots));
         const double quant = blocks / (rounds * slots);
         const double split_cost = sp > 1 ? 0.93 : 1.0;        // slab write + reduce launch
-        const double score = t.eff * useful * (0.30 + 0.70 * quant) * split_cost;
+        const double score = (shallow ? t.eff_shallow : t.eff) * useful * (0.30 + 0.70 * quant) * split_cost;
         if (score > best_score) { best_score = score; best = Plan{c, sp}; }
     }
     if (best_score < 0.0 && forced >= 0)              // the requested tile cannot run this problem: let the heuristic choose
-        best = plan_igemm(p, batch, ws_bytes, -1, mode, false);
+        return plan_igemm(p, batch, ws_bytes, -1, mode, false);
+    if (p.sa) best.cfg = kTiles[best.cfg].f8;         // fp8 operands (fill_gemm sets the scales): the tile that launches
     return best;
 }
 
@@ -1425,14 +1444,37 @@ static void launch_cfg(IGemmP p, int batch, hipStream_t s) {
 }
 
 
+// ---- dispatch: launch tile `cfg` of kTiles in one form.  The rows are walked at compile time and launch_cfg is instantiated for the
+// rows that carry the form bit only; a tile without it is an error (the planner never picks one) ----
+template <unsigned FORM, int MODE, bool F8, int EX, size_t I>
+static bool launch_row(IGemmP p, int batch, hipStream_t s) {
+    constexpr TileCfg t = kTiles[I];
+    if constexpr ((t.forms & FORM) != 0) {
+        launch_cfg<t.bm, t.bn, t.nwm, t.nwn, t.s, MODE, t.hpa, false, F8, EX>(p, batch, s);
+        return true;
+    }
+    return false;
+}
+
+template <unsigned FORM, int MODE, bool F8, int EX, size_t... I>
+static bool launch_rows(int cfg, IGemmP p, int batch, hipStream_t s, std::index_sequence<I...>) {
+    return ((cfg == (int)I && launch_row<FORM, MODE, F8, EX, I>(p, batch, s)) || ...);
+}
+
+template <unsigned FORM, int MODE, bool F8 = false, int EX = 0>
+static int launch_tile(int cfg, IGemmP p, int batch, hipStream_t s) {
+    if (launch_rows<FORM, MODE, F8, EX>(cfg, p, batch, s, std::make_index_sequence<kNCfg>{})) return PBE_OK;
+    return pbe_set_error(PBE_ENOTSUP, "igemm: tile config %d is not instantiated in form 0x%x", cfg, FORM);
+}
+
 // ---- the instantiations live in five translation units (igemm_dense / _conv / _halo / _f8 / _ex .hip), compiled in parallel ----
-void pbe_dispatch_dense(IGemmP p, int batch, hipStream_t s, size_t ws_bytes, int want_cfg);     // MODE 0
-void pbe_dispatch_conv(IGemmP p, int batch, hipStream_t s, size_t ws_bytes, int want_cfg);      // MODE 1 gather tiles; forwards tiles 10-14 to
-void pbe_launch_halo(int cfg, IGemmP p, int batch, hipStream_t s);                              // MODE 2 halo-resident tiles
-void pbe_dispatch_f8(IGemmP p, int batch, hipStream_t s, int want_cfg);
-void pbe_dispatch_ex(IGemmP p, int batch, hipStream_t s, int want_cfg);          // picks the feature combination: igemm_ex_{ln,st,qkv,all}.hip
-void pbe_launch_ex_ln(int cfg, IGemmP p, int batch, hipStream_t s);
-void pbe_launch_ex_st(int cfg, IGemmP p, int batch, hipStream_t s);
-void pbe_launch_ex_qkv(int cfg, IGemmP p, int batch, hipStream_t s);
-void pbe_launch_ex_all(int cfg, IGemmP p, int batch, hipStream_t s);
-void pbe_launch_astat(int cfg, IGemmP p, hipStream_t s);                                                  // tile 19 (igemm_astat.hip)
+int pbe_dispatch_dense(IGemmP p, int batch, hipStream_t s, size_t ws_bytes, int want_cfg);      // MODE 0
+int pbe_dispatch_conv(IGemmP p, int batch, hipStream_t s, size_t ws_bytes, int want_cfg);       // MODE 1 gather tiles; forwards F_HALO tiles to
+int pbe_launch_halo(int cfg, IGemmP p, int batch, hipStream_t s);                               // MODE 2 halo-resident tiles
+int pbe_dispatch_f8(IGemmP p, int batch, hipStream_t s, int want_cfg);
+int pbe_dispatch_ex(IGemmP p, int batch, hipStream_t s, int want_cfg);           // picks the feature combination: igemm_ex_{ln,st,qkv,all}.hip
+int pbe_launch_ex_ln(int cfg, IGemmP p, int batch, hipStream_t s);
+int pbe_launch_ex_st(int cfg, IGemmP p, int batch, hipStream_t s);
+int pbe_launch_ex_qkv(int cfg, IGemmP p, int batch, hipStream_t s);
+int pbe_launch_ex_all(int cfg, IGemmP p, int batch, hipStream_t s);
+void pbe_launch_astat(int cfg, IGemmP p, hipStream_t s);                                                  // tiles 19 / 20 (igemm_astat.hip)

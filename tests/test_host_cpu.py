@@ -199,6 +199,68 @@ def test_instantiate_from_config_and_tuned_table():
     assert table and all(0 <= (int(v) & 255) <= 21 and 0 <= (int(v) >> 8) <= 64 for v in table.values())     # tile config | split-K factor << 8
 
 
+def _plan(kind, **fields):
+    """out6 of pbe_gemm_plan / pbe_conv3x3_plan (host only, nothing is launched) for a descriptor with non-null, aligned operands."""
+    import ctypes
+    from pbe_amd import lib
+    desc = (lib.GemmDesc if kind == "gemm" else lib.Conv3x3Desc)()
+    for name in (("A", "W", "C") if kind == "gemm" else ("X", "Wp", "Y")):
+        setattr(desc, name, 1 << 20)
+    for name, value in fields.items():
+        setattr(desc, name, value)
+    out, need = (ctypes.c_int32 * 6)(), ctypes.c_size_t()
+    fn = lib.load().pbe_gemm_plan if kind == "gemm" else lib.load().pbe_conv3x3_plan
+    assert fn(ctypes.byref(desc), out, ctypes.byref(need)) == 0, lib.load().pbe_last_error()
+    return list(out)
+
+
+def _gemm_fields(M, N, K, batch, tile_cfg, fp8):
+    from pbe_amd import ops
+    f = dict(M=M, N=N, K=K, K1=K, lda=K, ldw=K, ldc=N, batch=batch, alpha=1.0, group_rows=1, tile_cfg=tile_cfg)
+    if fp8:                                      # ops.gemm_f8: scales, no workspace
+        f.update(operand_dtype=1, a_scale=1 << 20, w_scale=1 << 20)
+    else:
+        f.update(workspace=1 << 20, workspace_bytes=ops.SPLITK_WS_BYTES)
+    return f
+
+
+def test_fp8_plans_name_a_launchable_tile():
+    """The fp8 form instantiates tiles 3, 4, 6, 8 and 9 only: whatever the heuristic or a forced tile picks, the plan reports the tile
+    that launches, with its geometry."""
+    launched = {3: (128, 128), 4: (128, 64), 6: (64, 64), 8: (128, 320), 9: (128, 160)}
+    for M, N, K, batch in [(4608, 2560, 1280, 1), (1152, 10240, 1280, 1), (73728, 640, 320, 1), (18432, 1280, 640, 1), (64, 144, 320, 1),
+                           (1280, 576, 1280, 8), (320, 9216, 320, 8)]:
+        for cfg in [-1] + list(range(22)):
+            out = _plan("gemm", **_gemm_fields(M, N, K, batch, cfg, fp8=True))
+            assert out[0] in launched and tuple(out[2:4]) == launched[out[0]], ((M, N, K, batch, cfg), out)
+            bm, bn = launched[out[0]]
+            assert out[1] == 1 and out[4] == -(-M // bm) * -(-N // bn) * batch and out[5] == -(-N // bn), ((M, N, K, batch, cfg), out)
+
+
+def test_tuned_entries_plan_to_themselves():
+    """Every g / g8 / c entry of the tuned table is a (tile, split-K) pair the library runs as stated for its shape: no silent
+    fallback to the heuristic, no fp8 tile remapping."""
+    import json
+    from pbe_amd import ops
+    table = json.load(open(os.path.join(ROOT, "pbe_amd", "tuned_mi355x.json")))
+    checked, wrong = 0, []
+    for key, v in table.items():
+        kind, *f = key.split(":")
+        if kind in ("g", "g8"):
+            M, N, K, batch = map(int, f)
+            out = _plan("gemm", **_gemm_fields(M, N, K, batch, v, fp8=kind == "g8"))
+        elif kind == "c":
+            B, H, W, C1, C2, Cout, stride, pad, ups = map(int, f)
+            out = _plan("conv", X2=(1 << 20) if C2 else None, B=B, H=H, W=W, C1=C1, C2=C2, Cout=Cout, stride=stride, pad=pad, upsample=ups,
+                        workspace=1 << 20, workspace_bytes=ops.SPLITK_WS_BYTES, tile_cfg=v, kblock=ops.conv_kblock(C1, C2))
+        else:
+            continue
+        checked += 1
+        if (out[0], out[1]) != (v & 255, v >> 8):
+            wrong.append((key, v & 255, v >> 8, out[:2]))
+    assert checked == sum(k.split(":")[0] in ("g", "g8", "c") for k in table) and not wrong, wrong
+
+
 def test_preprocessing_of_bundled_example(golden_dir):
     """scripts/inference.py:306-318 on the reference's own examples/example_1 triple (data files copied
     into tests/golden/examples/): the product's loader against the oracle's statement of the formulas."""
