@@ -7,14 +7,21 @@ guidance, scale 5) + VAE decode.  Inputs (image / mask / exempl
 noise) are resident in HBM before the timed region.  Weights: name-seeded random init of the
 configs/v1.yaml architecture (no checkpoint exists offline).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (driver, N > 1)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value (images/s of the whole job), unit, higher_is_better, dtype, ms_per_step, the config,
+e2e_mfma_frac and, when N > 1, per_rank_ms and startup.  A plain run does nothing else: set-up, warm-up, the timed steps,
+--dump-outputs, the line.
+
+--full adds the measurements that take passes of their own after the timed region (`extra_legs`; --no-profile, --no-batch16 and
+--no-cpu-baseline trim them):
+  stage_ms_per_batch  one more step with per-stage events (CLIP, VAE encode, sampler, VAE decode), and unet_ms_per_step_per_image
   roofline     the kernel class with the most GPU time (3x3-conv implicit GEMM or the Linear GEMM, both MFMA): algorithmic
                FLOP per launch / average launch duration, measured with HIP events on the launch stream in a separate
                profiled pass AFTER the timed region (pbe_prof_*), against 2.5 PFLOP/s dense fp16; `classes` holds the same
                for every kernel class plus `frac_of_binding_roofline` (per launch: max(FLOP / peak, bytes / 8 TB/s)).
+  batch16      BASELINE configs[2]'s size (16 per GPU), 1 warm-up + 2 timed steps, beside the headline (N = 1, headline config)
   cpu_baseline the CPU oracle (a port: oracle/pbe_oracle.py, fp32 torch) timed on this box's host
                cores on a bounded sample (warm-up + 3 CFG U-Net pairs, median; VAE enc/dec + CLIP for one image),
                extrapolated to images/sec; CPU model and physical core count reported.  Rank 0, N = 1 only.
@@ -51,9 +58,11 @@ def parse_args(argv=None):
                     help="fp8 = BASELINE configs[4]: e4m3 operands for the LayerNorm-fed projections (pbe_amd.precision); not the headline config")
     ap.add_argument("--weights", default="broadcast", choices=("broadcast", "local"),
                     help="N > 1: rank 0 synthesises and broadcasts over RCCL (default, the north-star's step) or every rank synthesises its own copy")
-    ap.add_argument("--no-batch16", action="store_true", help="skip the extra BASELINE configs[2]-size (batch 16) measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the stage split, the per-kernel-class roofline, batch 16 and the CPU baseline")
+    ap.add_argument("--no-batch16", action="store_true", help="--full: skip the extra BASELINE configs[2]-size (batch 16) measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-kernel-class profiled pass (roofline)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--rehearse-launch", action="store_true",
@@ -134,6 +143,22 @@ def dump_outputs(path, arrays):
     return info
 
 
+def extra_legs(a, world, rank):
+    """The measurements this rank makes after the timed region.  None without --full; with it, every one that applies to the
+    configuration and was not switched off.  `stage` and `profile` run on every rank (a step gathers images across ranks)."""
+    if not a.full:
+        return set()
+    headline = a.image_size == 512 and a.precision == "fp16" and a.plms_steps == 50
+    legs = {"stage"}
+    if not a.no_profile:
+        legs.add("profile")
+    if world == 1 and rank == 0 and headline and not a.no_batch16 and a.batch != 16:
+        legs.add("batch16")
+    if world == 1 and rank == 0 and headline and not a.no_cpu_baseline:
+        legs.add("cpu_baseline")
+    return legs
+
+
 def log(msg):
     if int(os.environ.get("RANK", "0")) == 0:
         print(f"[bench] {msg}", file=sys.stderr, flush=True)
@@ -155,7 +180,9 @@ def build_model(device, rank, world, weights="broadcast"):
         model = instantiate_from_config(cfg)
         fill_latent_diffusion_(model)
         if world == 1:
-            cpu_sd = {k: v for k, v in model.state_dict().items()}      # fp32 CPU copy for the oracle baseline
+            # fp32 CPU copy for the oracle baseline, held on plain runs too: without it the host tensors are freed while the
+            # weights move to the device, which made set-up about 9 s slower on the MI355X host
+            cpu_sd = {k: v for k, v in model.state_dict().items()}
         model = model.to(device).eval()
     else:
         with torch.device("meta"):
@@ -298,6 +325,7 @@ def main():
     from pbe_amd.pipeline import inpaint
     from pbe_amd.shard import gather_images
 
+    legs = extra_legs(a, world, rank)
     model, cpu_sd, build_info = build_model(device, rank, world, a.weights)
     if a.precision == "fp8":
         from pbe_amd.precision import set_linear_precision
@@ -344,11 +372,13 @@ def main():
             log(f"outputs of the last timed step -> {a.dump_outputs}: " + ", ".join(f"{k} {s} ({n} written)" for k, (s, n) in info.items()))
         del last
 
-        # ---- separate passes (outside the timed region): stage split and per-kernel-class events ----
-        stage = {}
-        one_step(timings=stage)
+        # ---- --full: separate passes (outside the timed region): stage split and per-kernel-class events ----
+        stage = None
+        if "stage" in legs:
+            stage = {}
+            one_step(timings=stage)
         prof = None
-        if not a.no_profile:
+        if "profile" in legs:
             ops.prof_reset()
             ops.prof_enable(True)
             one_step()
@@ -359,7 +389,7 @@ def main():
 
         # ---- BASELINE configs[2] geometry (batch 16 per GPU, same everything else): reported beside the headline, never as `value` ----
         b16 = None
-        if world == 1 and rank == 0 and not a.no_batch16 and a.image_size == 512 and a.precision == "fp16" and a.plms_steps == 50 and B != 16:
+        if "batch16" in legs:
             inp16 = {k: v.to(device) for k, v in cases.synthetic_triples(16, 512).items()}
             run16 = lambda: inpaint(model, inp16["image"], inp16["mask"], inp16["ref"], steps=a.plms_steps, scale=a.scale, x_T=inp16["x_T"],      # noqa: E731
                                     post_eps=inp16["post_eps"])
@@ -401,8 +431,7 @@ def main():
         "dtype": "fp16" if a.precision == "fp16" else "fp8 (e4m3 linear operands) + fp16", "data": "synthetic",
         "config": {"workload": workload, "per_gpu_batch": B, "global_batch": world * B, "plms_steps": a.plms_steps, "cfg_scale": a.scale,
                    "parallelism": f"batch-sharded x{world}, no per-step collective"},
-        "unet_ms_per_step_per_image": stage.get("sampler_ms", 0.0) / a.plms_steps / B,
-        "stage_ms_per_batch": stage,
+        **({"unet_ms_per_step_per_image": stage.get("sampler_ms", 0.0) / a.plms_steps / B, "stage_ms_per_batch": stage} if stage is not None else {}),
         # reference-FLOP normalisation: what the reference's modules would execute per image (FlopCounterMode) ...
         "e2e_mfma_frac": value / world * flop_per_image / (MFMA_PEAK_TFLOPS * 1e12),
     }
@@ -447,7 +476,7 @@ def main():
                             "avg_launch_us": d["avg_launch_us"], "avg_gflop_per_launch": d["gflop_per_launch"],
                             "frac_of_binding_roofline": d["frac_of_binding_roofline"], "classes": classes}
         line["kernel_classes"] = {k: {"launches": v["launches"], "ms": v["ms"], "rate": v["achieved"], "rate_unit": v["unit"]} for k, v in classes.items()}
-    if world == 1 and not a.no_cpu_baseline and cpu_sd is not None and headline:
+    if "cpu_baseline" in legs:
         try:
             line["cpu_baseline"] = cpu_baseline(cpu_sd, max(1, min(16, os.cpu_count() or 1)))     # a 1-GPU box owns a 16-core share of the host
         except Exception as e:                                              # noqa: BLE001

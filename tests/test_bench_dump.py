@@ -1,4 +1,5 @@
-"""CPU suite (-m "not gpu"): bench.py's --dump-outputs writer and its --steps check, without a GPU."""
+"""CPU suite (-m "not gpu"): bench.py's --dump-outputs writer, its --steps check and which legs beyond the timed steps a run makes,
+without a GPU."""
 import importlib.util
 import os
 
@@ -50,3 +51,25 @@ def test_steps_must_be_positive():
     assert bench.parse_args(["--steps", "5", "--warmup", "0"]).steps == 5
     with pytest.raises(SystemExit):
         bench.parse_args(["--steps", "0"])
+
+
+def test_plain_run_makes_no_extra_legs():
+    bench = _bench()
+    for argv in ([], ["--steps", "20", "--warmup", "5"], ["--image-size", "768", "--precision", "fp8"], ["--batch", "16"]):
+        a = bench.parse_args(["--gpus", "1", *argv])
+        assert not a.full and bench.extra_legs(a, 1, 0) == set()
+    a = bench.parse_args(["--gpus", "2"])
+    assert bench.extra_legs(a, 2, 0) == set() and bench.extra_legs(a, 2, 1) == set()
+
+
+def test_full_run_legs():
+    bench = _bench()
+    legs = lambda argv, world=1, rank=0: bench.extra_legs(bench.parse_args(["--full", *argv]), world, rank)      # noqa: E731
+    assert legs([]) == {"stage", "profile", "batch16", "cpu_baseline"}
+    assert legs(["--no-profile", "--no-batch16", "--no-cpu-baseline"]) == {"stage"}
+    assert legs(["--no-profile"]) == {"stage", "batch16", "cpu_baseline"}
+    assert legs(["--batch", "16"]) == {"stage", "profile", "cpu_baseline"}           # the headline already is batch 16
+    for off_headline in (["--image-size", "768"], ["--precision", "fp8"], ["--plms-steps", "100"]):
+        assert legs(off_headline) == {"stage", "profile"}
+    for rank in (0, 1):                                                                  # every rank runs the passes that gather
+        assert legs(["--gpus", "2"], world=2, rank=rank) == {"stage", "profile"}

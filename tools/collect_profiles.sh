@@ -7,9 +7,9 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-profile --no-batch16"
+BENCH="python3 $R/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-profile --no-batch16"
 echo "[collect] kernel trace + stats"
-rocprofv3 --kernel-trace --stats -d $O/stats -o p --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-batch16 > $O/bench_under_rocprof.json 2> $O/stats.stderr.txt || exit 1
+rocprofv3 --kernel-trace --stats -d $O/stats -o p --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-batch16 > $O/bench_under_rocprof.json 2> $O/stats.stderr.txt || exit 1
 echo "[collect] FETCH_SIZE"
 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_f -o p --output-format csv -- $BENCH > /dev/null 2> $O/pmc_f.stderr.txt || exit 1
 echo "[collect] WRITE_SIZE"
@@ -24,6 +24,6 @@ cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/rocprofv3_kernel_stat
 # the big raw traces stay on the box (gpurun_out merge limit): keep the summaries only
 rm -rf $O/stats $O/pmc_f $O/pmc_w $O/pmc_m
 cp $O/igemm_traffic.json $R/profiles/igemm_traffic.json            # so that the plain bench below reports the measured traffic
-echo "[collect] plain bench (driver form)"
-python3 bench.py --steps 20 --warmup 5 > $O/bench_final.json 2> $O/bench_final.err || exit 1
+echo "[collect] full bench (driver form)"
+python3 bench.py --steps 20 --warmup 5 --full > $O/bench_final.json 2> $O/bench_final.err || exit 1
 tail -c 400 $O/traffic_summary.txt

@@ -3,9 +3,9 @@
 the two implicit-GEMM kernel classes (3x3 conv: igemm_kernel<..., MODE = 1, S>; Linear / 1x1 GEMM: MODE = 0), as bench.py's
 `roofline.traffic` / `roofline.classes.*.traffic` want it, stamped with the library source hash and the tile-table hash.  Counters collected exactly as MI355X_MICROARCH.md §HBM prescribes:
 
-    rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_bench/f -o p --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-profile --no-batch16
-    rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_bench/w -o p --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-profile --no-batch16
-    python tools/pmc_bench_traffic.py gpurun_out/pmc_bench/f gpurun_out/pmc_bench/w profiles/igemm_traffic.json
+    rocprofv3 --pmc FETCH_SIZE -d pmc_bench/f -o p --output-format csv -- python3 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-profile --no-batch16
+    rocprofv3 --pmc WRITE_SIZE -d pmc_bench/w -o p --output-format csv -- python3 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-profile --no-batch16
+    python tools/pmc_bench_traffic.py pmc_bench/f pmc_bench/w profiles/igemm_traffic.json
 
 (separate passes: FETCH_SIZE takes 3 of the 4 TCC slots, WRITE_SIZE 2).  Units and gfx950 corrections:
 both counters are KiB; FETCH_SIZE tallies 64 B per 128-B request for wide (16 B / lane) coalesced reads —
@@ -77,7 +77,7 @@ def main(fdir, wdir, outp):
                                               for k in sorted(ks)}}
     with open(os.path.join(root, "pbe_amd", "tuned_mi355x.json"), "rb") as f:
         table = hashlib.sha256(f.read()).hexdigest()[:16]
-    out = {"command": "bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-profile --no-batch16 (2 passes of the hot path)", "passes": PASSES, "source_hash": lib.source_hash(), "tuned_table_sha": table,
+    out = {"command": "bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-profile --no-batch16 (2 passes of the hot path)", "passes": PASSES, "source_hash": lib.source_hash(), "tuned_table_sha": table,
            "corrections": "FETCH_SIZE KiB x 1024 x 2 (gfx950: 64 B tallied per 128-B request); WRITE_SIZE KiB x 1024", "classes": classes}
     with open(outp, "w") as f:
         json.dump(out, f, indent=1)
