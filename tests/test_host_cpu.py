@@ -238,9 +238,11 @@ def test_fp8_plans_name_a_launchable_tile():
 
 
 def test_tuned_entries_plan_to_themselves():
-    """Every g / g8 / c entry of the tuned table is a (tile, split-K) pair the library runs as stated for its shape: no silent
-    fallback to the heuristic, no fp8 tile remapping."""
+    """Every entry of the tuned table is a (tile, split-K) pair the library runs as stated for its shape: no silent fallback to the
+    heuristic, no fp8 tile remapping.  gx entries plan with the extended epilogue their launch carries (LayerNorm fold + GEGLU,
+    LayerNorm fold + alpha columns + V^T, or residual + row vector + row statistics)."""
     import json
+    import tilecheck
     from pbe_amd import ops
     table = json.load(open(os.path.join(ROOT, "pbe_amd", "tuned_mi355x.json")))
     checked, wrong = 0, []
@@ -253,12 +255,12 @@ def test_tuned_entries_plan_to_themselves():
             B, H, W, C1, C2, Cout, stride, pad, ups = map(int, f)
             out = _plan("conv", X2=(1 << 20) if C2 else None, B=B, H=H, W=W, C1=C1, C2=C2, Cout=Cout, stride=stride, pad=pad, upsample=ups,
                         workspace=1 << 20, workspace_bytes=ops.SPLITK_WS_BYTES, tile_cfg=v, kblock=ops.conv_kblock(C1, C2))
-        else:
-            continue
+        else:                                    # gx: the extended-epilogue descriptor of the launch (tests/tilecheck.py, epilogue rule)
+            out = tilecheck.plan(tilecheck.Case(key, v))
         checked += 1
         if (out[0], out[1]) != (v & 255, v >> 8):
             wrong.append((key, v & 255, v >> 8, out[:2]))
-    assert checked == sum(k.split(":")[0] in ("g", "g8", "c") for k in table) and not wrong, wrong
+    assert checked == len(table) and not wrong, wrong
 
 
 def test_preprocessing_of_bundled_example(golden_dir):
