@@ -53,12 +53,13 @@ const char* pbe_last_error(void);
 /* sha256 (first 16 hex digits) over the sources and flags the library was built from (pbe_amd/build.py); the ctypes loader
  * recomputes it from the tree and refuses a stale binary instead of silently running old kernels. */
 const char* pbe_source_hash(void);
-/* sizeof() of the three descriptor structs as THIS binary was compiled: a binding checks its own struct layout against them
+/* sizeof() of the descriptor structs as THIS binary was compiled: a binding checks its own struct layout against them
  * at load time (pbe_amd/lib.py does; the ctypes stub of INTEGRATION.md section 2 does), so a binding written for an older
  * ABI hands over a short struct and gets an error instead of an out-of-bounds read. */
 size_t pbe_sizeof_gemm_desc(void);
 size_t pbe_sizeof_conv3x3_desc(void);
 size_t pbe_sizeof_attn_desc(void);
+size_t pbe_sizeof_attn_mx8_desc(void);
 
 /* ---------------------------------------------------------------------------------------------
  * pbe_gemm_f16 — C[m,n] = act(alpha * sum_k A[m,k] * W[n,k] + bias + rowvec[m / group_rows, n]) + R[m,n]
@@ -228,6 +229,42 @@ typedef struct pbe_attn_desc {
                             `scale` is then ignored */
 } pbe_attn_desc;
 int pbe_attention_f16(const pbe_attn_desc* d, pbe_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * MX-fp8 attention core (opt-in, pbe_amd.precision.set_attention_precision): OCP e4m3 operands with one E8M0 (power-of-two) scale
+ * per 32 consecutive contraction elements, both products on v_mfma_scale_f32_32x32x64_f8f6f4.
+ *
+ * pbe_quant_mx8_f16 — quantise fp16 rows whose contraction dim is contiguous.  Each 32-element block of one head gets the smallest
+ * power of two s with max|alpha x| / s <= 448 (an all-zero block: 1.0) and the bytes e4m3(alpha x / s), round to nearest even,
+ * saturating at +-448, never NaN.
+ *   PBE_MX8_TOKENS (q, k): X element (b, n, h, d) at X[(b*N + n)*rs + h*D + d];
+ *       Y bytes [B*N][H*DP], DP = D rounded up to 64 (zero padding); S [B][H][DP/32][NP], NP = N rounded up to 64.
+ *   PBE_MX8_VT (V^T):      X element (b, h, d, n) at X[((b*H + h)*D + d)*rs + n];
+ *       Y bytes [B*H*D][NP] (zero past N);                          S [B][H][NP/32][DV], DV = 32 * (D/32 + 1).
+ * Scale pads (tokens past N, rows past D) hold 1.0 (127).  D % 8 == 0, rs % 8 == 0, X and Y 16-byte aligned.
+ *
+ * pbe_attention_mx8 — O = softmax(scale_log2e / log2(e) * Q K^T) V from those layouts (Q and K: PBE_MX8_TOKENS at Nq / Nk,
+ * VT: PBE_MX8_VT at Nk).  O: fp16, element (b, n, h, d) at O[b*o_bs + n*o_rs + h*D + d].  D in {40, 80, 160}; anything else is
+ * PBE_EINVAL.  P = exp2(s - m) <= 2^8 is rounded to e4m3 once and feeds both the numerator and the denominator (a ones row of V^T).
+ * ------------------------------------------------------------------------------------------ */
+#define PBE_MX8_TOKENS 0
+#define PBE_MX8_VT 1
+int pbe_quant_mx8_f16(const void* X, void* Y, void* S, int32_t mode, int32_t B, int32_t H, int32_t N, int32_t D, int64_t rs, float alpha,
+                      pbe_stream_t stream);
+
+typedef struct pbe_attn_mx8_desc {
+    const void* Q;
+    const void* Q_scale;
+    const void* K;
+    const void* K_scale;
+    const void* VT;
+    const void* VT_scale;
+    void* O;
+    int32_t B, H, Nq, Nk, D;
+    int64_t o_bs, o_rs;
+    float scale_log2e; /* multiplies the scores (log2 domain): scale * log2(e), or 1 when the quantiser's alpha applied it to Q */
+} pbe_attn_mx8_desc;
+int pbe_attention_mx8(const pbe_attn_mx8_desc* d, pbe_stream_t stream);
 
 /* pbe_softmax_rows_f16 — Y[r,:] = softmax(scale * X[r,:]) over rows of `cols` fp16 (VAE mid attention,
  * model.py:193-195: one head, d = 512, N = 4096, scores kept in HBM once per image). */

@@ -134,8 +134,23 @@ class CrossAttention(HipModule):
         npad = (N + 7) // 8 * 8
         vt = torch.empty((B, inner, npad), dtype=torch.float16, device=x8.device)
         ops.gemm_f8(wv8.unsqueeze(0).expand(B, -1, -1), sv, x8.view(B, N, -1), sx.view(B, N), out=vt[:, :, :N] if npad != N else vt)
-        o = ops.attention(qk, qk[:, inner:], vt, B, self.heads, N, N, self.dim_head, self.scale,
-                          q_strides=(N * 2 * inner, 2 * inner), k_strides=(N * 2 * inner, 2 * inner), vt_strides=(inner * npad, npad))
+        return self.attention_core(qk, vt, B, N, npad)
+
+    attn_fp8 = False            # pbe_amd.precision.set_attention_precision(model, "fp8"): the self-attention core runs on MX-fp8 operands
+
+    def attention_core(self, qk, vt, B, N, vt_rs, q_prescaled=False):
+        """softmax(q k^T scale) v of every self-attention path: qk [B*N, 2*inner] holds q | k, vt [B, inner, vt_rs] holds V^T;
+        returns [B*N, inner].  fp16 core (pbe_attention_f16), or with attn_fp8 the MX-fp8 core: q, k and V^T are quantised to e4m3
+        with a power-of-two scale per 32 elements (scale log2(e) goes onto q there unless the projection already applied it)."""
+        inner, H, D = self.heads * self.dim_head, self.heads, self.dim_head
+        if self.attn_fp8:
+            c = self.scale * 1.4426950408889634
+            q8 = ops.quant_mx8(qk, B, H, N, D, rs=2 * inner, alpha=1.0 if q_prescaled else c)
+            k8 = ops.quant_mx8(qk[:, inner:], B, H, N, D, rs=2 * inner)
+            v8 = ops.quant_mx8(vt, B, H, N, D, rs=vt_rs, vt=True)
+            return ops.attention_mx8(q8, k8, v8, 1.0).view(B * N, inner)
+        o = ops.attention(qk, qk[:, inner:], vt, B, H, N, N, D, self.scale, q_strides=(N * 2 * inner, 2 * inner),
+                          k_strides=(N * 2 * inner, 2 * inner), vt_strides=(inner * vt_rs, vt_rs), q_prescaled=q_prescaled)
         return o.view(B * N, inner)
 
     # ---- fast paths used by BasicTransformerBlock -------------------------------------------
@@ -147,9 +162,7 @@ class CrossAttention(HipModule):
         npad = (N + 7) // 8 * 8
         vt = torch.empty((B, inner, npad), dtype=torch.float16, device=xn.device)
         ops.gemm(p.wv.unsqueeze(0).expand(B, -1, -1), xn.view(B, N, -1), out=vt[:, :, :N] if npad != N else vt)
-        o = ops.attention(qk, qk[:, inner:], vt, B, self.heads, N, N, self.dim_head, self.scale,
-                          q_strides=(N * 2 * inner, 2 * inner), k_strides=(N * 2 * inner, 2 * inner), vt_strides=(inner * npad, npad))
-        return o.view(B * N, inner)
+        return self.attention_core(qk, vt, B, N, npad)
 
     def self_attention_fused(self, x2d, stats, bp, B, N):
         """LayerNorm + to_q | to_k | to_v + attention core with ONE projection launch: x2d [B*N, C] is the RAW residual stream, `stats` its
@@ -160,9 +173,7 @@ class CrossAttention(HipModule):
         qk = torch.empty((B * N, 2 * inner), dtype=torch.float16, device=x2d.device)
         vt = torch.empty((B, inner, N), dtype=torch.float16, device=x2d.device)
         ops.gemm(x2d, bp.wqkv, bp.c2qkv, ln=(stats, bp.c1qkv, bp.eps1), alpha=bp.qscale, alpha_cols=inner, out=qk, vt=vt, vt_col0=2 * inner, vt_tokens=N)
-        o = ops.attention(qk, qk[:, inner:], vt, B, self.heads, N, N, self.dim_head, self.scale, q_strides=(N * 2 * inner, 2 * inner),
-                          k_strides=(N * 2 * inner, 2 * inner), vt_strides=(inner * N, N), q_prescaled=True)
-        return o.view(B * N, inner)
+        return self.attention_core(qk, vt, B, N, N, q_prescaled=True)
 
     def single_token_context(self, context):
         """context [B, 1, Dc] -> to_out(to_v(context)) as [B, C] fp16 (softmax over one key == 1)."""

@@ -41,6 +41,11 @@ class AttnDesc(C.Structure):
                 ("vt_bs", c_i64), ("vt_rs", c_i64), ("o_bs", c_i64), ("o_rs", c_i64), ("scale", c_f32), ("q_prescaled", c_i32)]
 
 
+class AttnMx8Desc(C.Structure):
+    _fields_ = [("Q", c_vp), ("Q_scale", c_vp), ("K", c_vp), ("K_scale", c_vp), ("VT", c_vp), ("VT_scale", c_vp), ("O", c_vp),
+                ("B", c_i32), ("H", c_i32), ("Nq", c_i32), ("Nk", c_i32), ("D", c_i32), ("o_bs", c_i64), ("o_rs", c_i64), ("scale_log2e", c_f32)]
+
+
 # name -> (restype, argtypes): every symbol include/pbe_hip.h declares
 SYMBOLS = {
     "pbe_abi_version": (c_i32, []),
@@ -49,6 +54,7 @@ SYMBOLS = {
     "pbe_sizeof_gemm_desc": (c_sz, []),
     "pbe_sizeof_conv3x3_desc": (c_sz, []),
     "pbe_sizeof_attn_desc": (c_sz, []),
+    "pbe_sizeof_attn_mx8_desc": (c_sz, []),
     "pbe_gemm_f16": (c_i32, [C.POINTER(GemmDesc), c_vp]),
     "pbe_conv3x3_f16": (c_i32, [C.POINTER(Conv3x3Desc), c_vp]),
     "pbe_gemm_plan": (c_i32, [C.POINTER(GemmDesc), C.POINTER(c_i32), C.POINTER(c_sz)]),
@@ -61,6 +67,8 @@ SYMBOLS = {
     "pbe_row_stats_f16": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_vp]),
     "pbe_layernorm_f8": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_f32, c_vp]),
     "pbe_attention_f16": (c_i32, [C.POINTER(AttnDesc), c_vp]),
+    "pbe_quant_mx8_f16": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_f32, c_vp]),
+    "pbe_attention_mx8": (c_i32, [C.POINTER(AttnMx8Desc), c_vp]),
     "pbe_softmax_rows_f16": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_f32, c_vp]),
     "pbe_geglu_f16": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
     "pbe_timestep_embedding_f16": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f32, c_vp]),
@@ -89,7 +97,7 @@ SYMBOLS = {
 _lib = None
 _lock = threading.Lock()
 
-SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_astat.hip", "attention.hip", "norm.hip",
+SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_astat.hip", "attention.hip", "attention_mx8.hip", "norm.hip",
            "elementwise.hip"]
 HASHED = [os.path.join("csrc", f) for f in SOURCES] + [os.path.join("csrc", "common.h"), os.path.join("csrc", "igemm_kernel.h"), os.path.join("..", "include", "pbe_hip.h"), "build.py"]
 
@@ -134,7 +142,8 @@ def load() -> C.CDLL:
         v = lib.pbe_abi_version()
         if v != ABI_VERSION:
             raise PbeError(f"libpbe_hip.so ABI version {v} != expected {ABI_VERSION}")
-        for cls, fn in ((GemmDesc, lib.pbe_sizeof_gemm_desc), (Conv3x3Desc, lib.pbe_sizeof_conv3x3_desc), (AttnDesc, lib.pbe_sizeof_attn_desc)):
+        for cls, fn in ((GemmDesc, lib.pbe_sizeof_gemm_desc), (Conv3x3Desc, lib.pbe_sizeof_conv3x3_desc), (AttnDesc, lib.pbe_sizeof_attn_desc),
+                        (AttnMx8Desc, lib.pbe_sizeof_attn_mx8_desc)):
             if C.sizeof(cls) != fn():
                 raise PbeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, libpbe_hip.so was compiled with {fn()}")
         built, want = lib.pbe_source_hash().decode(), source_hash()

@@ -528,6 +528,69 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, B: int, H: int
     return out
 
 
+MX8_TOKENS, MX8_VT = 0, 1          # include/pbe_hip.h PBE_MX8_*: q / k rows (contraction = channel) and V^T rows (contraction = token)
+
+
+class Mx8:
+    """An MX-fp8 operand as pbe_quant_mx8_f16 wrote it: e4m3 bytes + E8M0 scales (uint8 tensors) in the layout of `mode`."""
+
+    def __init__(self, data, scale, mode, B, H, N, D):
+        self.data, self.scale, self.mode, self.B, self.H, self.N, self.D = data, scale, mode, B, H, N, D
+
+
+def _extent_ok(t: torch.Tensor, elems: int) -> bool:
+    """t's storage holds `elems` elements from t's first element on (the kernel reads that far through raw pointers)."""
+    return t.storage_offset() * t.element_size() + elems * t.element_size() <= t.untyped_storage().nbytes()
+
+
+def quant_mx8(x: torch.Tensor, B: int, H: int, N: int, D: int, *, rs: int, vt: bool = False, alpha: float = 1.0) -> Mx8:
+    """fp16 rows -> MX-fp8 (OCP e4m3, one power-of-two scale per 32 contraction elements of one head), include/pbe_hip.h.
+    vt=False: element (b, n, h, d) at x[(b*N + n)*rs + h*D + d] (q or k, e.g. a column slice of the q | k projection);
+    vt=True:  element (b, h, d, n) at x[((b*H + h)*D + d)*rs + n] (V^T).  alpha multiplies the values before rounding."""
+    _h(x, "quant_mx8 x")
+    if D % 8 or rs % 8 or B <= 0 or H <= 0 or N <= 0 or D <= 0:
+        raise _l.PbeError(f"quant_mx8: need D % 8 == 0 and rs % 8 == 0 (D={D}, rs={rs})")
+    NP = (N + 63) // 64 * 64
+    if vt:
+        if rs < (N + 7) // 8 * 8 or not _extent_ok(x, (B * H * D - 1) * rs + N):
+            raise _l.PbeError("quant_mx8: V^T rows out of the tensor's storage")
+        DV = (D // 32 + 1) * 32
+        data = torch.empty((B * H * D, NP), dtype=torch.uint8, device=x.device)
+        scale = torch.empty((B, H, NP // 32, DV), dtype=torch.uint8, device=x.device)
+    else:
+        if rs < H * D or not _extent_ok(x, (B * N - 1) * rs + H * D):
+            raise _l.PbeError("quant_mx8: token rows out of the tensor's storage")
+        DP = (D + 63) // 64 * 64
+        data = torch.empty((B * N, H * DP), dtype=torch.uint8, device=x.device)
+        scale = torch.empty((B, H, DP // 32, NP), dtype=torch.uint8, device=x.device)
+    mode = MX8_VT if vt else MX8_TOKENS
+    with _timed(f"q8:{mode}:{B}:{H}:{N}:{D}"):
+        _l.check(_l.load().pbe_quant_mx8_f16(_p(x), _p(data), _p(scale), mode, B, H, N, D, rs, float(alpha), _stream()), "pbe_quant_mx8_f16")
+    return Mx8(data, scale, mode, B, H, N, D)
+
+
+def attention_mx8(q: Mx8, k: Mx8, vt: Mx8, scale_log2e: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(scale_log2e / log2(e) * q k^T) v -> [B, Nq, H*D] fp16 on the MX-fp8 core (pbe_attention_mx8).  q / k from
+    quant_mx8(vt=False), vt from quant_mx8(vt=True); pass scale_log2e = 1 when q was quantised with alpha = scale * log2(e)."""
+    for t, m, what in ((q, MX8_TOKENS, "q"), (k, MX8_TOKENS, "k"), (vt, MX8_VT, "vt")):
+        if not isinstance(t, Mx8) or t.mode != m:
+            raise _l.PbeError(f"attention_mx8: {what} must be a quant_mx8 result of mode {m}")
+        _req(t.data, torch.uint8, f"attention_mx8 {what}")
+    B, H, D = q.B, q.H, q.D
+    if (k.B, k.H, k.D) != (B, H, D) or (vt.B, vt.H, vt.D) != (B, H, D) or vt.N != k.N:
+        raise _l.PbeError("attention_mx8: q / k / vt shapes disagree")
+    if out is None:
+        out = torch.empty((B, q.N, H * D), dtype=torch.float16, device=q.data.device)
+    _h(out, "attention_mx8 out")
+    if out.dim() != 3 or out.shape != (B, q.N, H * D) or out.stride(2) != 1:
+        raise _l.PbeError("attention_mx8: out must be [B, Nq, H*D] with unit stride in the last dim")
+    d = _l.AttnMx8Desc(_p(q.data), _p(q.scale), _p(k.data), _p(k.scale), _p(vt.data), _p(vt.scale), _p(out), B, H, q.N, k.N, D,
+                       out.stride(0), out.stride(1), float(scale_log2e))
+    with _timed(f"a8:{B}:{H}:{q.N}:{k.N}:{D}"):
+        _l.check(_l.load().pbe_attention_mx8(C.byref(d), _stream()), "pbe_attention_mx8")
+    return out
+
+
 def softmax_rows(x: torch.Tensor, scale: float) -> torch.Tensor:
     _h(x, "softmax_rows x")
     x2 = x.reshape(-1, x.shape[-1])
