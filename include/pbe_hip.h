@@ -60,6 +60,7 @@ size_t pbe_sizeof_gemm_desc(void);
 size_t pbe_sizeof_conv3x3_desc(void);
 size_t pbe_sizeof_attn_desc(void);
 size_t pbe_sizeof_attn_mx8_desc(void);
+size_t pbe_sizeof_mx8_out_desc(void);
 
 /* ---------------------------------------------------------------------------------------------
  * pbe_gemm_f16 — C[m,n] = act(alpha * sum_k A[m,k] * W[n,k] + bias + rowvec[m / group_rows, n]) + R[m,n]
@@ -265,6 +266,35 @@ typedef struct pbe_attn_mx8_desc {
     float scale_log2e; /* multiplies the scores (log2 domain): scale * log2(e), or 1 when the quantiser's alpha applied it to Q */
 } pbe_attn_mx8_desc;
 int pbe_attention_mx8(const pbe_attn_mx8_desc* d, pbe_stream_t stream);
+
+/* pbe_gemm_mx8out_f16 — the GEMM of pbe_gemm_f16 whose output columns leave as MX-fp8 operands of pbe_attention_mx8 instead of fp16:
+ * every 32-element block of a range is quantised in the epilogue from the fp16 value pbe_gemm_f16 would store, multiplied by the range's
+ * alpha in fp32, so the bytes and scales are exactly those of pbe_gemm_f16 followed by pbe_quant_mx8_f16 (padding included).
+ * d->C and d->VT are not written and may be null.  Two forms:
+ *   channel_rows = 0: the LayerNorm-folded q | k | v projection (fp16 operands, ln_stats, vt_col0 / vt_tokens as in pbe_gemm_f16) or an
+ *       fp8-operand q | k projection: GEMM rows are the B*N tokens; a TOKENS range covers H*D columns from col0, a VT range the H*D
+ *       columns from col0 = d->vt_col0 (fp16 form only).  The fp16 form takes exactly three ranges: q (TOKENS, col0 0), k (TOKENS,
+ *       col0 H*D) and V^T (VT, col0 2*H*D) of an N = 3*H*D output;
+ *   channel_rows = 1: the swapped V^T projection (fp8 operands, batch = B, M = H*D rows = channels, N columns = tokens): one VT range.
+ * Refused (PBE_EINVAL): N % 64 != 0, D not in {40, 80, 160}, ranges with different B / H / N / D, targets not 16-byte aligned, split-K,
+ * a residual, GEGLU, row statistics, an fp16 problem without the LayerNorm fold or without all three ranges, and a requested tile
+ * with an MX block across a tile boundary (a planned tile never has one).
+ * pbe_gemm_mx8out_plan: the tile that launches (out6 as pbe_gemm_plan), host only; PBE_EINVAL where pbe_gemm_mx8out_f16 refuses. */
+typedef struct pbe_mx8_out_range {
+    void* data;            /* e4m3 bytes in the layout of pbe_quant_mx8_f16 */
+    void* scale;           /* E8M0 scales, same (data and scale 16-byte aligned) */
+    int32_t layout;        /* PBE_MX8_TOKENS or PBE_MX8_VT */
+    int32_t col0;          /* first GEMM output column of the range */
+    float alpha;           /* multiplies the fp16 value before rounding (pbe_quant_mx8_f16's alpha) */
+    int32_t B, H, N, D;
+} pbe_mx8_out_range;
+typedef struct pbe_mx8_out_desc {
+    int32_t nranges;       /* 1 .. 3 */
+    int32_t channel_rows;  /* see above */
+    pbe_mx8_out_range r[3];
+} pbe_mx8_out_desc;
+int pbe_gemm_mx8out_f16(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, pbe_stream_t stream);
+int pbe_gemm_mx8out_plan(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, int32_t* out6);
 
 /* pbe_softmax_rows_f16 — Y[r,:] = softmax(scale * X[r,:]) over rows of `cols` fp16 (VAE mid attention,
  * model.py:193-195: one head, d = 512, N = 4096, scores kept in HBM once per image). */

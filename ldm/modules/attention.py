@@ -130,6 +130,9 @@ class CrossAttention(HipModule):
             p.f8 = (ops.pack_linear_f8(torch.cat([self.to_q.weight, self.to_k.weight], 0)), ops.pack_linear_f8(self.to_v.weight))
         (wqk8, sqk), (wv8, sv) = p.f8
         inner = self.heads * self.dim_head
+        if self._mx8_out(N):                     # both projections write the MX-fp8 operands directly (no fp16 q | k / V^T)
+            q8, k8, v8 = ops.qkv_mx8_f8(x8, sx, wqk8, sqk, wv8, sv, B=B, H=self.heads, N=N, D=self.dim_head, q_alpha=self.scale * 1.4426950408889634)
+            return ops.attention_mx8(q8, k8, v8, 1.0).view(B * N, inner)
         qk = ops.gemm_f8(x8, sx, wqk8, sqk)
         npad = (N + 7) // 8 * 8
         vt = torch.empty((B, inner, npad), dtype=torch.float16, device=x8.device)
@@ -137,6 +140,13 @@ class CrossAttention(HipModule):
         return self.attention_core(qk, vt, B, N, npad)
 
     attn_fp8 = False            # pbe_amd.precision.set_attention_precision(model, "fp8"): the self-attention core runs on MX-fp8 operands
+    mx8_from_projection = True  # with attn_fp8: the folded / fp8 q|k|v^T projections write the MX-fp8 operands (pbe_gemm_mx8out_f16);
+                                # False: fp16 projection + pbe_quant_mx8_f16 (A/B runs, tests) - the same bytes
+
+    def _mx8_out(self, N):
+        """The projection emits the MX-fp8 operands: attention fp8 on, the switch on, and a shape the MX copy-out takes (whole samples
+        of 64 tokens, head dims of pbe_attention_mx8); other shapes keep the quantiser path."""
+        return self.attn_fp8 and self.mx8_from_projection and N % 64 == 0 and self.dim_head in (40, 80, 160)
 
     def attention_core(self, qk, vt, B, N, vt_rs, q_prescaled=False):
         """softmax(q k^T scale) v of every self-attention path: qk [B*N, 2*inner] holds q | k, vt [B, inner, vt_rs] holds V^T;
@@ -170,6 +180,10 @@ class CrossAttention(HipModule):
         The GEMM folds the LayerNorm into its epilogue, multiplies the q columns by scale log2(e) in fp32 (the attention kernel then
         runs exp2 on the MFMA output directly) and stores the v columns transposed (V^T, what the attention kernel streams)."""
         inner = self.heads * self.dim_head
+        if self._mx8_out(N):                     # MX-fp8 copy-out: q | k | V^T leave the epilogue as the attention core's operands
+            q8, k8, v8 = ops.qkv_mx8(x2d, bp.wqkv, bp.c2qkv, ln=(stats, bp.c1qkv, bp.eps1), B=B, H=self.heads, N=N, D=self.dim_head,
+                                     alpha=bp.qscale, alpha_cols=inner)
+            return ops.attention_mx8(q8, k8, v8, 1.0).view(B * N, inner)
         qk = torch.empty((B * N, 2 * inner), dtype=torch.float16, device=x2d.device)
         vt = torch.empty((B, inner, N), dtype=torch.float16, device=x2d.device)
         ops.gemm(x2d, bp.wqkv, bp.c2qkv, ln=(stats, bp.c1qkv, bp.eps1), alpha=bp.qscale, alpha_cols=inner, out=qk, vt=vt, vt_col0=2 * inner, vt_tokens=N)

@@ -109,3 +109,35 @@ static inline void pbe_raise_dynamic_lds(std::atomic<uint64_t>& done, const void
     (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     done.fetch_or(bit, std::memory_order_release);
 }
+
+// ---- MX-fp8 (OCP e4m3 + E8M0 per 32 elements): the quantiser (attention_mx8.hip) and the GEMM epilogue's MX copy-out (igemm_kernel.h,
+//      mx8_block_lds) share this code ----
+// OCP e4m3 of y, round to nearest even, saturating at +-448 (never NaN), subnormals kept (quantum 2^-9).  Integer / power-of-two
+// arithmetic only: v_cvt_pk_fp8_f32 disagreed with this rounding on some of the adversarial blocks (outliers, fp16 subnormals) of the
+// bit-exact test in tests/test_attention_mx8_gpu.py.  The attention kernel keeps the fast convert for P; its accuracy tests bound that.
+__device__ __forceinline__ unsigned mx8_e4m3(float y) {
+    const unsigned sgn = y < 0.f ? 0x80u : 0u;
+    float a = fminf(fabsf(y), 448.f);
+    const int e = a >= 0.015625f ? (int)((__float_as_uint(a) >> 23) & 255) - 127 : -6;     // exponent of the quantum's binade
+    const float q = __uint_as_float((unsigned)(e - 3 + 127) << 23);                          // 2^(e-3): one e4m3 ulp
+    const float iq = __uint_as_float((unsigned)(127 - e + 3) << 23);                         // 1 / q, exact
+    a = fminf(rintf(a * iq) * q, 448.f);                                                     // exact: q is a power of two
+    unsigned code;
+    if (a < 0.015625f) code = (unsigned)(a * 512.f);                                         // subnormal: m * 2^-9 (8 -> 0x08 = 2^-6)
+    else code = (((__float_as_uint(a) >> 23) & 255) - 127 + 7) << 3 | ((__float_as_uint(a) >> 20) & 7);
+    return code | sgn;
+}
+
+// E8M0 exponent of the smallest power of two s with amax / s <= 448 (amax = 0: 127, i.e. 1.0)
+__device__ __forceinline__ int mx8_scale_exp(float amax) {
+    if (!(amax > 0.f)) return 127;
+    const unsigned u = __float_as_uint(amax);
+    int E = (int)((u >> 23) & 255) - 127;
+    unsigned man = u & 0x7fffff;
+    if (E == -127) {                                                                         // fp32 subnormal amax
+        const int lz = __builtin_clz(man) - 8;
+        E = -126 - lz; man = (man << lz) & 0x7fffff;
+    }
+    const int e = man <= 0x600000 ? E - 8 : E - 7;                                           // 448 = 1.75 * 2^8
+    return min(max(e + 127, 1), 254);
+}

@@ -184,3 +184,110 @@ extern "C" int pbe_conv3x3_plan(const pbe_conv3x3_desc* d, int32_t* out6, size_t
     *workspace_needed = out6[1] > 1 ? (size_t)out6[1] * p.M * p.N * sizeof(float) : 0;
     return PBE_OK;
 }
+
+// ---- MX-fp8 output (pbe_gemm_mx8out_f16): the GEMM's output columns leave as pbe_attention_mx8 operands ----
+static int fill_mx8(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, IGemmP& p, const char* who) {
+    PBE_REQUIRE(d && mx, "%s: null descriptor", who);
+    PBE_REQUIRE(mx->nranges >= 1 && mx->nranges <= 3 && (mx->channel_rows == 0 || mx->channel_rows == 1), "%s: 1 .. 3 ranges, channel_rows 0 / 1", who);
+    const pbe_mx8_out_range& r0 = mx->r[0];
+    const int B = r0.B, H = r0.H, N = r0.N, D = r0.D;
+    PBE_REQUIRE(D == 40 || D == 80 || D == 160, "%s: head dim %d (pbe_attention_mx8 takes 40, 80, 160)", who, D);
+    PBE_REQUIRE(B > 0 && H > 0 && N > 0 && N % 64 == 0, "%s: N=%d must be a positive multiple of 64 (whole samples of MX blocks)", who, N);
+    const bool f8 = d && d->operand_dtype == PBE_DTYPE_F8E4M3;
+    PBE_REQUIRE(!d->resid, "%s: no residual (the output is not stored as fp16)", who);
+    PBE_REQUIRE(!d->row_stats_out, "%s: no row statistics (the output is not stored as fp16)", who);
+    PBE_REQUIRE(d->act == PBE_ACT_NONE, "%s: no activation (GEGLU or other: act %d)", who, d->act);
+    PBE_REQUIRE(!d->rowvec && !d->bias_per_row && !d->A2, "%s: no row vector, per-row bias or second source", who);
+    PBE_REQUIRE(d->tile_cfg < 0 || ((d->tile_cfg >> 8) & 255) <= 1, "%s: split-K is not available (tile_cfg 0x%x)", who, d->tile_cfg);
+    pbe_gemm_desc dd = *d;                                   // C / VT are never written: stand-ins pass the fp16 checks
+    dd.C = r0.data; dd.ldc = (dd.VT || (!mx->channel_rows && d->vt_col0 > 0)) ? ((d->vt_col0 + 7) & ~7) : ((d->N + 7) & ~7); dd.strideC = 0;
+    dd.workspace = nullptr; dd.workspace_bytes = 0;
+    if (!f8) {
+        PBE_REQUIRE(d->ln_stats && !mx->channel_rows && d->vt_col0 > 0 && d->batch == 1,
+                    "%s: fp16 operands: the LayerNorm-folded q|k|v^T projection only (ln_stats, vt_col0, batch 1)", who);
+        dd.VT = r0.data; dd.vt_rs = (d->vt_tokens + 7) & ~7; dd.vt_bs = 0;
+    } else {
+        PBE_REQUIRE(!d->ln_stats && !d->VT && !d->vt_col0 && !d->alpha_cols, "%s: fp8 operands take no extended epilogue", who);
+    }
+    const int rc = fill_gemm(&dd, p, who);
+    if (rc != PBE_OK) return rc;
+    const long HD = (long)H * D;
+    // the fp16 form is the q | k | v^T projection and nothing else: the A-stationary tile's form 2 relies on every column tile belonging to
+    // one of these three ranges (its persistent loop counts the copy-out's stores, igemm_astat.hip)
+    PBE_REQUIRE(f8 || (mx->nranges == 3 && mx->r[0].layout == PBE_MX8_TOKENS && mx->r[0].col0 == 0 && mx->r[1].layout == PBE_MX8_TOKENS &&
+                       mx->r[1].col0 == HD && mx->r[2].layout == PBE_MX8_VT && mx->r[2].col0 == 2 * HD && d->N == 3 * HD),
+                "%s: fp16 operands: exactly the q (TOKENS, column 0), k (TOKENS, column H*D) and V^T (VT, column 2*H*D) ranges of an N = 3*H*D output", who);
+    for (int i = 0; i < mx->nranges; ++i) {
+        const pbe_mx8_out_range& r = mx->r[i];
+        PBE_REQUIRE(r.B == B && r.H == H && r.N == N && r.D == D, "%s: range %d: B, H, N, D differ from range 0", who, i);
+        PBE_REQUIRE(r.data && r.scale && al16(r.data) && al16(r.scale), "%s: range %d: null or unaligned target (16 bytes)", who, i);
+        PBE_REQUIRE(r.layout == PBE_MX8_TOKENS || r.layout == PBE_MX8_VT, "%s: range %d: layout %d unknown", who, i, r.layout);
+        if (mx->channel_rows) {
+            PBE_REQUIRE(f8 && mx->nranges == 1 && r.layout == PBE_MX8_VT && r.col0 == 0 && d->M == HD && d->N == N && d->batch == B,
+                        "%s: channel_rows: one VT range over a batch of B [H*D, N] problems (fp8 operands)", who);
+        } else {
+            PBE_REQUIRE(d->M == (long)B * N && d->batch == 1, "%s: token rows: M = B*N, batch 1", who);
+            PBE_REQUIRE(r.col0 >= 0 && r.col0 + HD <= d->N, "%s: range %d outside the output columns", who, i);
+            if (r.layout == PBE_MX8_VT)
+                PBE_REQUIRE(!f8 && r.col0 == d->vt_col0 && d->vt_tokens == N && r.col0 + HD == d->N, "%s: range %d: VT from token rows is the last range, at vt_col0, vt_tokens = N", who, i);
+            else
+                PBE_REQUIRE(f8 || r.col0 + HD <= d->vt_col0, "%s: range %d: TOKENS range overlaps the V^T columns", who, i);
+        }
+        for (int j = 0; j < i; ++j)
+            PBE_REQUIRE(mx->r[j].col0 + HD <= r.col0 || r.col0 + HD <= mx->r[j].col0, "%s: ranges %d and %d overlap", who, j, i);
+        p.mx_data[i] = (unsigned char*)r.data; p.mx_scale[i] = (unsigned char*)r.scale;
+        p.mx_c0[i] = r.col0; p.mx_layout[i] = r.layout; p.mx_alpha[i] = r.alpha;
+    }
+    p.mx_nr = mx->nranges; p.mx_crow = mx->channel_rows;
+    p.mx_H = H; p.mx_N = N; p.mx_D = D; p.mx_DP = (D + 63) / 64 * 64; p.mx_DV = (D / 32 + 1) * 32;
+    p.ws = nullptr;
+    return PBE_OK;
+}
+
+// the tile that launches; PBE_EINVAL when no tile keeps every MX block whole (plan_igemm falls back to its heuristic among the aligned
+// tiles when the requested / tuned tile splits a block: its best score stays negative only when none is aligned)
+static int plan_mx8(const IGemmP& p, int batch, int want_cfg, Plan& pl, const char* who) {
+    if (want_cfg >= 0 && (want_cfg & 255) < kNCfg) {       // an explicitly requested tile that would split a block: refused, never replaced
+        const int c = want_cfg & 255;
+        PBE_REQUIRE(mx_tile_ok(p, kTiles[p.sa ? kTiles[c].f8 : c]), "%s: tile %d splits an MX block (N=%d, D=%d)", who, c, p.N, p.mx_D);
+    }
+    pl = plan_igemm(p, batch, 0, want_cfg, 0);
+    const TileCfg& t = kTiles[pl.cfg];
+    const bool form_ok = (p.sa ? (t.forms & F_F8) : (t.forms & (F_EX | F_ASTAT))) != 0 && (!(t.forms & F_ASTAT) || pbe_astat_ok(p, batch, pl.cfg));
+    PBE_REQUIRE(form_ok && mx_tile_ok(p, t) && pl.splits == 1, "%s: no tile keeps every MX block whole (N=%d, D=%d)", who, p.N, p.mx_D);
+    return PBE_OK;
+}
+
+extern "C" int pbe_gemm_mx8out_f16(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, pbe_stream_t stream) {
+    IGemmP p;
+    int rc = fill_mx8(d, mx, p, "pbe_gemm_mx8out_f16");
+    if (rc != PBE_OK) return rc;
+    Plan pl;
+    rc = plan_mx8(p, d->batch, d->tile_cfg, pl, "pbe_gemm_mx8out_f16");
+    if (rc != PBE_OK) return rc;
+    p.splits = 1;
+    hipStream_t s = (hipStream_t)stream;
+#ifdef PBE_STAMPS
+    p.stamps = g_pbe_stamps;
+#endif
+    if (kTiles[pl.cfg].forms & F_ASTAT) pbe_launch_astat(pl.cfg, p, s);
+    else rc = p.sa ? pbe_launch_f8_mx8(pl.cfg, p, d->batch, s) : pbe_launch_ex_qkv_mx8(pl.cfg, p, d->batch, s);
+    if (rc != PBE_OK) return rc;
+    PBE_LAUNCH_CHECK("pbe_gemm_mx8out_f16");
+    return PBE_OK;
+}
+
+extern "C" int pbe_gemm_mx8out_plan(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, int32_t* out6) {
+    PBE_REQUIRE(out6, "pbe_gemm_mx8out_plan: null output");
+    IGemmP p;
+    int rc = fill_mx8(d, mx, p, "pbe_gemm_mx8out_plan");
+    if (rc != PBE_OK) return rc;
+    Plan pl;
+    rc = plan_mx8(p, d->batch, d->tile_cfg, pl, "pbe_gemm_mx8out_plan");
+    if (rc != PBE_OK) return rc;
+    const TileCfg& t = kTiles[pl.cfg];
+    out6[0] = pl.cfg; out6[1] = 1; out6[2] = t.bm; out6[3] = t.bn;
+    out6[4] = cdiv(p.M, t.bm) * cdiv(p.N, t.bn) * d->batch;
+    out6[5] = cdiv(p.N, t.bn);
+    return PBE_OK;
+}

@@ -24,6 +24,8 @@ constexpr int ABM = 128, AKT = 5;
 
 // FORM 0: GEGLU output (the FeedForward projection).  FORM 1: q | k | v^T of the fused self-attention projection - plain fp16 columns, alpha on
 // the columns below alpha_cols only, the tiles at and beyond vt_col0 stored transposed (IGemmP.vt), as the EX_LN | EX_VT streaming form does.
+// FORM 2: FORM 1 with the MX-fp8 copy-out (pbe_gemm_mx8out_f16): the same staged fp16 rows leave as pbe_attention_mx8's operands - an
+// 80-column q | k half row is two d = 40 heads, a transposed staging row 32 tokens, i.e. one MX block (igemm_kernel.h, mx8_*).
 template <int TN, int FORM>
 __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int run, int tiles_m) {
     constexpr int TM = 2, BN = 16 * TN, PW = BN / 8 / 4;          // PW = weight pieces (8 rows x 128 B) per wave and k-tile
@@ -34,6 +36,11 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
     constexpr int VROW = 40;                                       // halfs per row of the transposed staging (32 tokens + pad)
     // stores a tile's epilogue leaves in the vmcnt queue: GEGLU 2 NST; plain 4 NST, transposed TN (the counted waits take the smaller)
     constexpr int EST = FORM == 0 ? 2 * NST : (4 * NST < TN ? 4 * NST : TN);
+    // Form 2 issues at least as many: pbe_gemm_mx8out_f16 admits exactly the q | k | V^T ranges covering every column, so each of a q|k tile's
+    // four half-row passes stores >= 1 block per lane group (2 x 16-byte data + 1 scale store: >= 12) and each of a V^T tile's TN / 2 passes
+    // one block per lane pair (1 x 16-byte data + 1 scale store: >= TN), both >= EST.  A pass that stored nothing would let the counted
+    // waits of the next tile's first two k-tiles pass before their weight slot has landed.
+    static_assert(FORM != 2 || (EST <= 12 && EST <= 2 * (TN / 2)), "form 2: the MX copy-out must issue at least EST stores per tile");
     static_assert(FORM == 0 || (TN % 2 == 0 && 32 * VROW * 2 <= 16 * (BN / 2 + 8) * 2), "transposed staging: two 16-column groups at a time");
     static_assert(BN % 32 == 0 && RS * SLOT + 4 * STGW + 2 * 2 * BN * 4 <= 80 * 1024, "two workgroups per CU");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -232,13 +239,18 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
                             *reinterpret_cast<h16x4*>(stg + fr * STGR + ii * 16 + fq * 4) = o;
                         }
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        if constexpr (FORM == 2) {
+                            const int x0 = n0 + hf * (BN / 2), r = mx8_range(p, x0);
+                            if (r >= 0) mx8_token_blocks(p, r, stg, STGR, 16, x0, BN / 2, m0 + wm * 32 + j * 16, lane, 64);
+                        } else {
 #pragma unroll
-                        for (int h = 0; h < NST; ++h) {
-                            const int idx = lane + 64 * h;
-                            if (idx < 16 * CPR) {
-                                const int row = idx / CPR, ch = idx - row * CPR;
-                                const h16x8 val = *reinterpret_cast<const h16x8*>(stg + row * STGR + ch * 8);
-                                *reinterpret_cast<h16x8*>(p.C + (long)(m0 + wm * 32 + j * 16 + row) * p.ldc + n0 + hf * (BN / 2) + ch * 8) = val;
+                            for (int h = 0; h < NST; ++h) {
+                                const int idx = lane + 64 * h;
+                                if (idx < 16 * CPR) {
+                                    const int row = idx / CPR, ch = idx - row * CPR;
+                                    const h16x8 val = *reinterpret_cast<const h16x8*>(stg + row * STGR + ch * 8);
+                                    *reinterpret_cast<h16x8*>(p.C + (long)(m0 + wm * 32 + j * 16 + row) * p.ldc + n0 + hf * (BN / 2) + ch * 8) = val;
+                                }
                             }
                         }
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -258,11 +270,17 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
                             for (int r = 0; r < 4; ++r) stg[(ii * 16 + fq * 4 + r) * VROW + j * 16 + fr] = (h16)v[r];
                         }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if constexpr (FORM == 2) {                        // one channel (32 tokens, one MX block) per lane pair (l, l + 32)
+                        const int r = mx8_range(p, n0);          // (the V^T range: the host admits no other layout here)
+                        if (r >= 0 && p.mx_layout[r] == PBE_MX8_VT)
+                            mx8_vt_block_pair(p, r, stg + (lane & 31) * VROW, bsmp, n0 - p.mx_c0[r] + ps * 32 + (lane & 31), tok0, lane >> 5);
+                    } else {
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const int idx = lane + 64 * h, crow = idx >> 2, tch = idx & 3;
-                        const h16x8 val = *reinterpret_cast<const h16x8*>(stg + crow * VROW + tch * 8);
-                        *reinterpret_cast<h16x8*>(vdst + (long)(n0 - p.vt_col0 + ps * 32 + crow) * p.vt_rs + tch * 8) = val;
+                        for (int h = 0; h < 2; ++h) {
+                            const int idx = lane + 64 * h, crow = idx >> 2, tch = idx & 3;
+                            const h16x8 val = *reinterpret_cast<const h16x8*>(stg + crow * VROW + tch * 8);
+                            *reinterpret_cast<h16x8*>(vdst + (long)(n0 - p.vt_col0 + ps * 32 + crow) * p.vt_rs + tch * 8) = val;
+                        }
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 }
@@ -301,7 +319,8 @@ bool pbe_astat_ok(const IGemmP& p, int batch, int cfg) {
 }
 
 void pbe_launch_astat(int cfg, IGemmP p, hipStream_t s) {
-    if (p.act != PBE_ACT_GEGLU) launch_regs<10, 1>(p, s);
+    if (p.mx_nr) launch_regs<10, 2>(p, s);                // (pbe_gemm_mx8out_f16: tile 20, q | k | v^T only)
+    else if (p.act != PBE_ACT_GEGLU) launch_regs<10, 1>(p, s);
     else if (cfg == 19) launch_regs<8, 0>(p, s);
     else launch_regs<10, 0>(p, s);
 }

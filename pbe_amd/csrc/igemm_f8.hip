@@ -8,3 +8,6 @@ int pbe_dispatch_f8(IGemmP p, int batch, hipStream_t s, int want_cfg) {
     p.splits = 1;
     return launch_tile<F_F8, 0, true>(pl.cfg, p, batch, s);
 }
+
+// the same tiles with the MX-fp8 copy-out (pbe_gemm_mx8out_f16: q | k, or V^T from the swapped projection)
+int pbe_launch_f8_mx8(int cfg, IGemmP p, int batch, hipStream_t s) { return launch_tile<F_F8, 0, true, EX_MX>(cfg, p, batch, s); }

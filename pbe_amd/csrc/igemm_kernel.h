@@ -64,6 +64,12 @@ struct IGemmP {
     // residual add), in pbe_groupnorm_f16's partial layout [B][blocks][groups][2] - the norm's statistics pass is then not launched
     float* gstat; int gs_cg, gs_groups, gs_hw;      // channels per group, groups of the whole tensor, output pixels per sample
     int* gs_report;                                 // HOST pointer (launch_cfg): row blocks per sample the launch writes partials for, 0 = this tile cannot
+    // MX-fp8 output (EX_MX instantiations, pbe_gemm_mx8out_f16): column ranges [mx_c0, mx_c0 + width) of the output leave as OCP e4m3 bytes
+    // + E8M0 scales in pbe_quant_mx8_f16's layouts (include/pbe_hip.h) instead of fp16; C is not written.  Shared B, H, N, D (N % 64 == 0);
+    // mx_crow: rows are the H*D channels of V^T, columns its N tokens, blockIdx.y = sample (the swapped V^T GEMM); else rows are tokens
+    unsigned char* mx_data[3]; unsigned char* mx_scale[3];
+    int mx_c0[3], mx_layout[3]; float mx_alpha[3]; int mx_nr, mx_crow;
+    int mx_H, mx_N, mx_D, mx_DP, mx_DV;
     int sv_ok;      // bias + row vector of a tile come from LDS (set per tile shape in launch_cfg)
     int m_fast;     // an XCD's run of tiles walks m fastest (one weight panel, many activation rows) instead of n fastest (launch_cfg)
 #ifdef PBE_STAMPS
@@ -119,6 +125,7 @@ static __device__ __attribute__((aligned(16))) unsigned int g_pbe_zero16[4] = {0
 #define EX_LN 1
 #define EX_ST 2
 #define EX_VT 4
+#define EX_MX 8        // MX-fp8 copy-out (IGemmP.mx_*): a compile-time form of copy_out, never a run-time branch of the fp16 kernels
 #define PBE_GLDS16(gsrc, ldst)                                                                     \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc),         \
                                      (__attribute__((address_space(3))) void*)(ldst), 16, 0, 0)
@@ -146,6 +153,132 @@ __device__ __forceinline__ f32x4 mfma_pair_f8(const h16x8& w, const h16x8& a, f3
     return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(wv[1], av[1], acc, 0, 0, 0);
 }
 
+// ---- MX-fp8 copy-out (EX_MX; also the A-stationary tile's form 2): staged fp16 values -> pbe_quant_mx8_f16's bytes and scales ----
+// A block's values are the fp16 values pbe_gemm_f16 would store, times the range's alpha in fp32, then pbe_quant_mx8_f16's arithmetic
+// (mx8_scale_exp / mx8_e4m3, common.h) to pbe_quant_mx8_f16's addresses: bit-identical to the two-launch path by construction.
+// One block straight from the staged values at src (len in {8, 16, 24, 32}: whole 16-byte chunks; zeros past it, as the quantiser pads):
+// the amax in a first pass over the LDS, then the bytes 16 values at a time - 16 live floats instead of 32 (the A-stationary tile's
+// epilogue holds its A block and accumulators in registers: the whole-block form spilled 100 bytes per lane there).
+__device__ __forceinline__ int mx8_block_lds(const h16* src, int len, float al, unsigned char* dst) {
+    typedef int i32x4_ __attribute__((ext_vector_type(4)));
+    float amax = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (8 * c < len) {
+            const h16x8 x = *reinterpret_cast<const h16x8*>(src + 8 * c);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf((float)x[e] * al));
+        }
+    }
+    const int se = mx8_scale_exp(amax);
+    const float inv = __uint_as_float((unsigned)(254 - se) << 23);                          // 1 / 2^(se - 127), exact
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        i32x4_ w;
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+            const int c = 2 * hf + cc;
+            h16x8 x = {};
+            if (8 * c < len) x = *reinterpret_cast<const h16x8*>(src + 8 * c);
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                unsigned word = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float v = 8 * c + 4 * q + e < len ? (float)x[4 * q + e] * al : 0.f;
+                    word |= mx8_e4m3(v * inv) << (8 * e);
+                }
+                w[2 * cc + q] = (int)word;
+            }
+        }
+        *reinterpret_cast<i32x4_*>(dst + 16 * hf) = w;
+    }
+    return se;
+}
+
+// the range holding output column n (the last one starting at or left of it), -1: none
+__device__ __forceinline__ int mx8_range(const IGemmP& p, int n) {
+    int r = -1;
+    for (int q = 0; q < p.mx_nr; ++q)
+        if (p.mx_c0[q] <= n && (r < 0 || p.mx_c0[q] > p.mx_c0[r])) r = q;
+    return r;
+}
+
+// V^T scale of block (sample b, channel c of the range, tokens tok .. tok + 31) at (b, h, tok / 32, d).  The last channel of a head also writes
+// the head's scale pad rows [D, DV) as 1.0 (pbe_attention_mx8 reads them: pad rows and the ones row): 8 bytes at a time (the scale rows
+// are 16-byte aligned, DV % 32 == 0, D % 8 == 0)
+__device__ __forceinline__ void mx8_vt_scale(const IGemmP& p, int r, int b, int c, int tok, int se) {
+    const int D = p.mx_D, DV = p.mx_DV;
+    const int h = c / D, d = c - h * D;
+    unsigned char* sp = p.mx_scale[r] + (((long)b * p.mx_H + h) * (p.mx_N >> 5) + (tok >> 5)) * DV;
+    sp[d] = (unsigned char)se;
+    if (d == D - 1)
+        for (int q = D; q < DV; q += 8) *reinterpret_cast<unsigned long long*>(sp + q) = 0x7f7f7f7f7f7f7f7full;
+}
+
+// V^T block (sample b, channel c of the range, 32 staged tokens from token tok): bytes row b H D + c, then its scale
+__device__ __forceinline__ void mx8_vt_block(const IGemmP& p, int r, const h16* src, int b, int c, int tok) {
+    const int se = mx8_block_lds(src, 32, p.mx_alpha[r], p.mx_data[r] + ((long)b * p.mx_H * p.mx_D + c) * p.mx_N + tok);
+    mx8_vt_scale(p, r, b, c, tok, se);
+}
+
+// The same block over a lane pair (l, l ^ 32) of one wave: half hf = l >> 5 holds tokens 16 hf .. 16 hf + 15, the amax meets over the pair
+// (a maximum: exact in any order), each half converts and stores its 16 bytes, the lower lane the scale - every lane of the wave busy where
+// a lane per block would leave half of them idle (the A-stationary tile's 32-channel passes)
+__device__ __forceinline__ void mx8_vt_block_pair(const IGemmP& p, int r, const h16* src, int b, int c, int tok, int hf) {
+    typedef int i32x4_ __attribute__((ext_vector_type(4)));
+    const float al = p.mx_alpha[r];
+    const h16x8 x[2] = {*reinterpret_cast<const h16x8*>(src + 16 * hf), *reinterpret_cast<const h16x8*>(src + 16 * hf + 8)};
+    float amax = 0.f;
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf((float)x[c2][e] * al));
+    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+    const int se = mx8_scale_exp(amax);
+    const float inv = __uint_as_float((unsigned)(254 - se) << 23);                          // 1 / 2^(se - 127), exact
+    i32x4_ w;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        unsigned word = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) word |= mx8_e4m3((float)x[q >> 1][4 * (q & 1) + e] * al * inv) << (8 * e);
+        w[q] = (int)word;
+    }
+    *reinterpret_cast<i32x4_*>(p.mx_data[r] + ((long)b * p.mx_H * p.mx_D + c) * p.mx_N + tok + 16 * hf) = w;
+    if (hf == 0) mx8_vt_scale(p, r, b, c, tok, se);
+}
+
+// TOKENS blocks of `rows` staged rows (LDS row stride ld halfs, output rows mrow0 ..) x `cols` columns from output column x0, all inside
+// range r: block (h, j) = columns h D + 32 j .. + min(32, D - 32 j) of the range; the head's last block also writes the all-padding block
+// behind it (DP / 32 - blocks per head <= 1: zero bytes, scale 1.0).  Threads t0, t0 + nt, ... take one (row, block) each, blocks fastest.
+__device__ __forceinline__ void mx8_token_blocks(const IGemmP& p, int r, const h16* st, int ld, int rows, int x0, int cols, int mrow0, int t0, int nt) {
+    const int D = p.mx_D, Hh = p.mx_H, Nt = p.mx_N, DP = p.mx_DP;
+    const int nbh = (D + 31) >> 5, npb = DP >> 5;
+    auto nblk = [&](int x) { const int hh = x / D; return hh * nbh + (x - hh * D + 31) / 32; };           // blocks left of column x
+    const int c0 = p.mx_c0[r], rel0 = x0 - c0, rel1 = min(x0 + cols, c0 + Hh * D) - c0;
+    if (rel1 <= rel0) return;
+    const int b0 = nblk(rel0), cnt = nblk(rel1) - b0;
+    const float al = p.mx_alpha[r];
+    for (int idx = t0; idx < rows * cnt; idx += nt) {
+        const int row = idx / cnt, gb = b0 + (idx - row * cnt);
+        const int m = mrow0 + row;
+        if (m >= p.M) continue;
+        const int h = gb / nbh, j = gb - h * nbh, len = min(32, D - 32 * j);
+        unsigned char* dst = p.mx_data[r] + (long)m * Hh * DP + h * DP + 32 * j;
+        const int se = mx8_block_lds(st + row * ld + (c0 + h * D + 32 * j - x0), len, al, dst);
+        const int b = m / Nt, n = m - b * Nt;
+        unsigned char* sp = p.mx_scale[r] + (((long)b * Hh + h) * npb + j) * Nt + n;
+        sp[0] = (unsigned char)se;
+        if (j == nbh - 1 && npb > nbh) {
+            typedef int i32x4_ __attribute__((ext_vector_type(4)));
+            *reinterpret_cast<i32x4_*>(dst + 32) = (i32x4_){0, 0, 0, 0};
+            *reinterpret_cast<i32x4_*>(dst + 48) = (i32x4_){0, 0, 0, 0};
+            sp[Nt] = 127;
+        }
+    }
+}
+
 // (the 4-wave tiles live two workgroups per CU - two waves per SIMD, 256 registers each.  The V^T form of the 128x160 tile would take 268
 //  and halve the occupancy: its bound is declared; the LayerNorm-only (252) and statistics-only (228) forms fit unconstrained and
 //  keep their natural allocation - capped to 192 registers the GEGLU projection ran 11 % slower)
@@ -158,7 +291,8 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     // EX_LN LayerNorm folded in, EX_ST row statistics out, EX_VT column-range alpha + transposed V^T tiles (see IGemmP).  Separate
     // instantiations per combination in use (GEGLU: EX_LN; proj_in / to_out: EX_ST; q|k|v^T: EX_LN | EX_VT): a kernel's registers are
     // the maximum over its paths, and the all-in-one form ran the GEGLU projection 11 % slower than the plain tile (tools/gemm_ex_ab.py).
-    constexpr bool EXL = (EX & 1) != 0, EXS = (EX & 2) != 0, EXV = (EX & 4) != 0;
+    constexpr bool EXL = (EX & 1) != 0, EXS = (EX & 2) != 0, EXV = (EX & 4) != 0, EXM = (EX & EX_MX) != 0;
+    constexpr int EXF = EX & 7;                       // the fp16 extended-epilogue features (EX_MX only changes the copy-out)
     // F8 (MODE 0 only): A and W hold OCP e4m3 bytes, a k-tile row of 128 B is 128 k-values; v_mfma_f32_16x16x32_fp8_fp8 runs at
     // the fp16 MFMA's rate, the gain is half the bytes through the fill path that bounds these GEMMs.  The epilogue multiplies
     // by the per-row scale of A and the per-row scale of W (per output column) before bias / activation / residual.
@@ -184,7 +318,8 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     constexpr int RING = MODE == 2 ? 2 * HPA * 128 + S * W_BYTES : S * STAGE;
     static_assert(S >= 2 && S <= 4 && PA % NW == 0 && BM % 16 == 0 && BN % 16 == 0, "A pieces must divide over the waves (weight pieces may be padded)");
     static_assert(MODE != 2 || (HPA % 8 == 0 && HPA >= BM), "halo image must hold the tile");
-    static_assert(EX == 0 || (MODE == 0 && !F8), "extended epilogue: dense fp16 tiles only");
+    static_assert(EXF == 0 || (MODE == 0 && !F8), "extended epilogue: dense fp16 tiles only");
+    static_assert(!EXM || (MODE == 0 && !EXS && (F8 || EXF == (EX_LN | EX_VT))), "MX-fp8 copy-out: the fp8 tiles and the q|k|v^T form");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -869,7 +1004,8 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     // activation stays a uniform run-time branch per quad.
     constexpr bool ARMS = TM * TN * 4 <= 96;
     constexpr int CLDT = GR + 8;                      // EX: row stride of the transposed C tile (V^T tiles)
-    static_assert(EX == 0 || (ONE_PASS && (size_t)BN * CLDT * 2 <= (size_t)S * STAGE), "extended epilogue: whole C tile (either orientation) in the ring's LDS");
+    static_assert(EXF == 0 || (ONE_PASS && (size_t)BN * CLDT * 2 <= (size_t)S * STAGE), "extended epilogue: whole C tile (either orientation) in the ring's LDS");
+    static_assert(!EXM || ONE_PASS, "MX-fp8 copy-out: whole C tile in LDS");
     const bool vtile = EXV && p.vt && n0 >= p.vt_col0;     // uniform: this tile's columns belong to the transposed output
     auto stage = [&](int g, auto FAST, auto ACT, auto VTT) {
         constexpr bool F = decltype(FAST)::value, VT = decltype(VTT)::value;
@@ -880,7 +1016,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
         asm volatile("" : "+s"(al));
         float ln_rs[EXL ? TM : 1], ln_nm[EXL ? TM : 1];    // LayerNorm fold: this lane's rows' rstd and -mean rstd (LDS, read once)
         if constexpr (EXL) {
-            if (EX != 7 || p.ln_stat) {
+            if (EXF != 7 || p.ln_stat) {
 #pragma unroll
                 for (int j = 0; j < TM; ++j) {
                     const int ml = (ONE_PASS ? wm * WM : 0) + j * 16 + fr;
@@ -895,7 +1031,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
             float ali = al, c1a[4] = {0.f, 0.f, 0.f, 0.f};
             if constexpr (EXV) ali = (p.alpha_cols > 0 && n >= p.alpha_cols) ? 1.f : al;
             if constexpr (EXL) {
-                if (EX != 7 || p.ln_stat) {
+                if (EXF != 7 || p.ln_stat) {
                     const f32x4 c1 = *reinterpret_cast<const f32x4*>(lnc + nl);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) c1a[r] = ali * c1[r];
@@ -935,12 +1071,12 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
                     const f32x4 sn = *reinterpret_cast<const f32x4*>(scw + nl);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(acc[i][j][r], sm * sn[r], add[r]);
-                } else if constexpr (EX != 0) {
+                } else if constexpr (EXF != 0) {
                     // NO run-time branch inside the unrolled body: a uniform branch per quad splits it into 40 basic blocks and the
                     // GELU chains (rcp -> 4 fma -> exp) of different quads can no longer be interleaved (the GEGLU projection ran 12 % slower).
                     // The LayerNorm-only / q|k|v forms therefore ALWAYS fold (their dispatch guarantees ln_stat), the V^T orientation is a
                     // compile-time argument of stage(); only the catch-all form (EX = 7) decides at run time.
-                    if constexpr (EXL && EX != 7) {          // LN(x) W^T = rstd (x W'^T - mean colsum(W')) with W' = W gamma (bias holds W beta + b)
+                    if constexpr (EXL && EXF != 7) {          // LN(x) W^T = rstd (x W'^T - mean colsum(W')) with W' = W gamma (bias holds W beta + b)
                         const float ars = ali * ln_rs[j];    //   alpha (rstd acc - mean rstd colsum) + bias  =  acc (alpha rstd) + ((-mean rstd) (alpha colsum) + bias)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(acc[i][j][r], ars, __builtin_fmaf(ln_nm[j], c1a[r], add[r]));
@@ -990,6 +1126,37 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
         // (tiles whose accumulators stay live across the passes - NG > 1 - have no registers for a deep batch)
         constexpr int UB = !ONE_PASS ? (IT % 2 == 0 ? 2 : 1) : (IT % 5 == 0 ? 5 : (IT % 4 == 0 ? 4 : (IT % 3 == 0 ? 3 : (IT % 2 == 0 ? 2 : 1))));
         const int Nout = gg ? p.N >> 1 : p.N, nb = gg ? n0 >> 1 : n0;
+        if constexpr (EXM && !gg) {
+            // MX-fp8 copy-out: one thread per 32-element block of the staged fp16 tile (mx8_*_blocks).  The planner guarantees that no block
+            // crosses a tile boundary and that every tile lies inside one range (mx_tile_ok).
+            if (p.mx_crow) {                                 // rows = channels, columns = tokens (one VT range, sample bz)
+                constexpr int BPR = BN / 32;
+                for (int idx = tid; idx < GR * BPR; idx += NT) {
+                    const int row = idx / BPR, cb = idx - row * BPR;
+                    const int m = m0 + g * GR + row, n = n0 + cb * 32;
+                    if (m >= p.M || n >= p.N) continue;
+                    mx8_vt_block(p, 0, sC + row * CLD + cb * 32, (int)bz, m, n);
+                }
+                return;
+            }
+            const int r = mx8_range(p, n0);
+            if (r < 0) return;
+            if (p.mx_layout[r] == PBE_MX8_VT) {              // transposed tile (EX_VT): LDS row = channel, GR tokens per row
+                if constexpr (EXV) {
+                    constexpr int BPR = GR / 32;
+                    for (int idx = tid; idx < BN * BPR; idx += NT) {
+                        const int crow = idx / BPR, tb = idx - crow * BPR;
+                        const int m = m0 + tb * 32;
+                        if (m >= p.M || n0 + crow >= p.N) continue;
+                        const int b = m / p.mx_N;
+                        mx8_vt_block(p, r, sC + crow * CLDT + tb * 32, b, n0 - p.mx_c0[r] + crow, m - b * p.mx_N);
+                    }
+                }
+                return;
+            }
+            mx8_token_blocks(p, r, sC, CLD, GR, n0, BN, m0 + g * GR, tid, NT);
+            return;
+        }
         if constexpr (EXV && !gg) {
             if (vtile) {
                 // transposed tile: LDS row = output channel, 16-byte chunks of 8 consecutive tokens -> vt[b][channel][token] rows
@@ -1344,6 +1511,25 @@ static int halo_rows(const IGemmP& p, int mode, int bm, int hpa) {
 }
 
 bool pbe_astat_ok(const IGemmP& p, int batch, int cfg);      // igemm_astat.hip: can tile 19 / 20 run this problem?
+
+// MX-fp8 copy-out (IGemmP.mx_*): can tile t write its blocks without any 32-element MX block crossing a tile boundary?  Every range starts
+// on a column tile, TOKENS ranges end on one too, every column-tile boundary inside a TOKENS range is a block boundary (h D + 32 j) - at
+// half-tile granularity for the A-stationary tile, whose q|k rows leave BN / 2 columns at a time - and V^T blocks of 32 tokens start on
+// 32-token boundaries (rows: every tile height is a multiple of 32; columns of the channel-row form: every tile width is).
+static inline bool mx_tile_ok(const IGemmP& p, const TileCfg& t) {
+    if (t.bm % 32 || t.bn % 32) return false;
+    if (p.mx_crow) return true;
+    const int D = p.mx_D, w = (t.forms & F_ASTAT) ? t.bn / 2 : t.bn;
+    for (int r = 0; r < p.mx_nr; ++r) {
+        if (p.mx_c0[r] % t.bn) return false;
+        if (p.mx_layout[r] != PBE_MX8_TOKENS) continue;
+        const int width = p.mx_H * D;
+        if ((p.mx_c0[r] + width) % t.bn && p.mx_c0[r] + width != p.N) return false;
+        for (int x = w; x < width; x += w)
+            if ((x % D) % 32) return false;
+    }
+    return true;
+}
 static inline bool ex_needed(const IGemmP& p) { return p.alpha_cols > 0 || p.ln_stat || p.rstat || p.vt; }
 
 // want_cfg: -1 = heuristic; else (tile config index) | (split-K factor << 8), factor 0 = heuristic factor for that tile.
@@ -1365,6 +1551,7 @@ static Plan plan_igemm(const IGemmP& p, int batch, size_t ws_bytes, int want_cfg
         if (!(t.forms & forms) || ((t.forms & F_FORCED) && forced != c)) continue;
         if ((t.forms & F_ASTAT) && !pbe_astat_ok(p, batch, c)) continue;
         if (p.vt && p.vt_col0 % t.bn) continue;                              // extended epilogue: V^T columns start on a tile
+        if (p.mx_nr && !mx_tile_ok(p, kTiles[p.sa ? t.f8 : c])) continue;    // MX-fp8 copy-out: the tile that launches keeps every block whole
         if (t.hpa && !halo_rows(p, mode, t.bm, t.hpa)) continue;              // a forced halo tile that does not apply falls back below
         if (t.hpa && p.N % 8) continue;
         const long tm = (p.M + t.bm - 1) / t.bm, tn = (p.N + t.bn - 1) / t.bn;
@@ -1398,8 +1585,8 @@ static void launch_cfg(IGemmP p, int batch, hipStream_t s) {
     constexpr size_t ring = MODE == 2 ? (size_t)2 * HPA * 128 + (size_t)S * BN * 128 : (size_t)S * (BM + BN) * 128;
     constexpr size_t c_bytes = (size_t)(BM / NWM) * (BN + 8) * 2;
     constexpr int SVR = (ring > c_bytes ? ring : c_bytes) + 4 * BN * sizeof(float) <= 160 * 1024 ? 4 : 3;                              // svec rows (samples per tile)
-    constexpr size_t lds = (ring > c_bytes ? ring : c_bytes) + (MODE == 1 ? 9 * BM * sizeof(int) : 0) + (EX != 0 ? 4 : SVR) * BN * sizeof(float) +     // + svec[SVR][BN]
-                           (F8 ? (BM + BN) * sizeof(float) : 0) + (EX != 0 ? (2 * BM + BN) * sizeof(float) : 0);                            // + operand scales / LayerNorm rows + colsum
+    constexpr size_t lds = (ring > c_bytes ? ring : c_bytes) + (MODE == 1 ? 9 * BM * sizeof(int) : 0) + ((EX & 7) != 0 ? 4 : SVR) * BN * sizeof(float) +     // + svec[SVR][BN]
+                           (F8 ? (BM + BN) * sizeof(float) : 0) + ((EX & 7) != 0 ? (2 * BM + BN) * sizeof(float) : 0);                            // + operand scales / LayerNorm rows + colsum
     p.sv_ok = !p.rowvec || p.group_rows % BM == 0 || (BM % p.group_rows == 0 && BM / p.group_rows <= SVR);
     static_assert(lds <= 160 * 1024, "tile does not fit the 160 KiB LDS");
     static std::atomic<uint64_t> attr_done{0};
@@ -1478,3 +1665,6 @@ int pbe_launch_ex_st(int cfg, IGemmP p, int batch, hipStream_t s);
 int pbe_launch_ex_qkv(int cfg, IGemmP p, int batch, hipStream_t s);
 int pbe_launch_ex_all(int cfg, IGemmP p, int batch, hipStream_t s);
 void pbe_launch_astat(int cfg, IGemmP p, hipStream_t s);                                                  // tiles 19 / 20 (igemm_astat.hip)
+// MX-fp8 copy-out forms (pbe_gemm_mx8out_f16): the q|k|v^T tiles (igemm_ex_qkv.hip, A-stationary tile 20 in igemm_astat.hip) and the fp8 tiles
+int pbe_launch_ex_qkv_mx8(int cfg, IGemmP p, int batch, hipStream_t s);
+int pbe_launch_f8_mx8(int cfg, IGemmP p, int batch, hipStream_t s);

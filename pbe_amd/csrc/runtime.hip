@@ -26,6 +26,7 @@ extern "C" size_t pbe_sizeof_gemm_desc(void) { return sizeof(pbe_gemm_desc); }
 extern "C" size_t pbe_sizeof_conv3x3_desc(void) { return sizeof(pbe_conv3x3_desc); }
 extern "C" size_t pbe_sizeof_attn_desc(void) { return sizeof(pbe_attn_desc); }
 extern "C" size_t pbe_sizeof_attn_mx8_desc(void) { return sizeof(pbe_attn_mx8_desc); }
+extern "C" size_t pbe_sizeof_mx8_out_desc(void) { return sizeof(pbe_mx8_out_desc); }
 
 // ---- per-class timing: hipEvents recorded on the launch stream around each entry point ---------
 // Off by default (zero overhead: one relaxed load).  bench.py turns it on for ONE profiled pass

@@ -46,6 +46,14 @@ class AttnMx8Desc(C.Structure):
                 ("B", c_i32), ("H", c_i32), ("Nq", c_i32), ("Nk", c_i32), ("D", c_i32), ("o_bs", c_i64), ("o_rs", c_i64), ("scale_log2e", c_f32)]
 
 
+class Mx8OutRange(C.Structure):
+    _fields_ = [("data", c_vp), ("scale", c_vp), ("layout", c_i32), ("col0", c_i32), ("alpha", c_f32), ("B", c_i32), ("H", c_i32), ("N", c_i32), ("D", c_i32)]
+
+
+class Mx8OutDesc(C.Structure):
+    _fields_ = [("nranges", c_i32), ("channel_rows", c_i32), ("r", Mx8OutRange * 3)]
+
+
 # name -> (restype, argtypes): every symbol include/pbe_hip.h declares
 SYMBOLS = {
     "pbe_abi_version": (c_i32, []),
@@ -55,6 +63,7 @@ SYMBOLS = {
     "pbe_sizeof_conv3x3_desc": (c_sz, []),
     "pbe_sizeof_attn_desc": (c_sz, []),
     "pbe_sizeof_attn_mx8_desc": (c_sz, []),
+    "pbe_sizeof_mx8_out_desc": (c_sz, []),
     "pbe_gemm_f16": (c_i32, [C.POINTER(GemmDesc), c_vp]),
     "pbe_conv3x3_f16": (c_i32, [C.POINTER(Conv3x3Desc), c_vp]),
     "pbe_gemm_plan": (c_i32, [C.POINTER(GemmDesc), C.POINTER(c_i32), C.POINTER(c_sz)]),
@@ -69,6 +78,8 @@ SYMBOLS = {
     "pbe_attention_f16": (c_i32, [C.POINTER(AttnDesc), c_vp]),
     "pbe_quant_mx8_f16": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_f32, c_vp]),
     "pbe_attention_mx8": (c_i32, [C.POINTER(AttnMx8Desc), c_vp]),
+    "pbe_gemm_mx8out_f16": (c_i32, [C.POINTER(GemmDesc), C.POINTER(Mx8OutDesc), c_vp]),
+    "pbe_gemm_mx8out_plan": (c_i32, [C.POINTER(GemmDesc), C.POINTER(Mx8OutDesc), C.POINTER(c_i32)]),
     "pbe_softmax_rows_f16": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_f32, c_vp]),
     "pbe_geglu_f16": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
     "pbe_timestep_embedding_f16": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f32, c_vp]),
@@ -143,7 +154,7 @@ def load() -> C.CDLL:
         if v != ABI_VERSION:
             raise PbeError(f"libpbe_hip.so ABI version {v} != expected {ABI_VERSION}")
         for cls, fn in ((GemmDesc, lib.pbe_sizeof_gemm_desc), (Conv3x3Desc, lib.pbe_sizeof_conv3x3_desc), (AttnDesc, lib.pbe_sizeof_attn_desc),
-                        (AttnMx8Desc, lib.pbe_sizeof_attn_mx8_desc)):
+                        (AttnMx8Desc, lib.pbe_sizeof_attn_mx8_desc), (Mx8OutDesc, lib.pbe_sizeof_mx8_out_desc)):
             if C.sizeof(cls) != fn():
                 raise PbeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, libpbe_hip.so was compiled with {fn()}")
         built, want = lib.pbe_source_hash().decode(), source_hash()

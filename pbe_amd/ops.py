@@ -591,6 +591,143 @@ def attention_mx8(q: Mx8, k: Mx8, vt: Mx8, scale_log2e: float, out: Optional[tor
     return out
 
 
+def _mx8_target(mode, B, H, N, D, device, out=None) -> Mx8:
+    """MX-fp8 operand of quant_mx8's shape (N % 64 == 0: no token padding): `out` if given (checked), else empty tensors."""
+    if out is not None:
+        ref = _mx8_target(mode, B, H, N, D, "meta")
+        if not isinstance(out, Mx8) or out.mode != mode or (out.B, out.H, out.N, out.D) != (B, H, N, D):
+            raise _l.PbeError(f"MX-fp8 output: expected an Mx8 of mode {mode} for B={B} H={H} N={N} D={D}")
+        for t, r, what in ((out.data, ref.data, "data"), (out.scale, ref.scale, "scale")):
+            _req(t, torch.uint8, f"MX-fp8 output {what}")
+            if t.shape != r.shape or not t.is_contiguous():
+                raise _l.PbeError(f"MX-fp8 output {what}: expected a contiguous {tuple(r.shape)} tensor, got {tuple(t.shape)}")
+        return out
+    if mode == MX8_VT:
+        return Mx8(torch.empty((B * H * D, N), dtype=torch.uint8, device=device),
+                   torch.empty((B, H, N // 32, (D // 32 + 1) * 32), dtype=torch.uint8, device=device), MX8_VT, B, H, N, D)
+    DP = (D + 63) // 64 * 64
+    return Mx8(torch.empty((B * N, H * DP), dtype=torch.uint8, device=device),
+               torch.empty((B, H, DP // 32, N), dtype=torch.uint8, device=device), MX8_TOKENS, B, H, N, D)
+
+
+def _mx8_desc(ranges, channel_rows: bool):
+    mx = _l.Mx8OutDesc()
+    mx.nranges, mx.channel_rows = len(ranges), 1 if channel_rows else 0
+    for i, (t, col0, alpha) in enumerate(ranges):
+        mx.r[i] = _l.Mx8OutRange(_p(t.data), _p(t.scale), t.mode, int(col0), float(alpha), t.B, t.H, t.N, t.D)
+    return mx
+
+
+def _mx8_plan(d, mx):
+    """Host-only plan query of pbe_gemm_mx8out_f16: [tile config, split-K (1), BM, BN, workgroups, column tiles]; raises where refused."""
+    out = (C.c_int32 * 6)()
+    _l.check(_l.load().pbe_gemm_mx8out_plan(C.byref(d), C.byref(mx), out), "pbe_gemm_mx8out_plan")
+    return list(out)
+
+
+_MX8_TUNED = {}
+
+
+def _mx8_tile_cfg(d, mx, key: str, D: int) -> int:
+    """The tuned tile of `key` where it keeps every MX block whole, else -1: the planner then chooses among the aligned tiles
+    (pbe_gemm_mx8out_f16 refuses an explicitly requested tile that splits a block).  Cached per shape."""
+    want = _tile_cfg(key)
+    ck = (key, D, mx.channel_rows, want)
+    hit = _MX8_TUNED.get(ck)
+    if hit is None:
+        hit = want
+        if want >= 0:
+            t = _l.GemmDesc.from_buffer_copy(d)
+            t.tile_cfg = want
+            out = (C.c_int32 * 6)()
+            if _l.load().pbe_gemm_mx8out_plan(C.byref(t), C.byref(mx), out) != 0:
+                hit = -1
+        _MX8_TUNED[ck] = hit
+    return hit
+
+
+def _gemm_mx8out(d, mx, key: str, what: str):
+    """Launch pbe_gemm_mx8out_f16 (d.tile_cfg from the tuned table; under pinned_batch_scale the MX tile of the scaled layer)."""
+    if _PLANS is not None:
+        _PLANS.append((key, *_mx8_plan(d, mx)[:5]))
+    with _timed(f"{key}|mx8"):
+        _l.check(_l.load().pbe_gemm_mx8out_f16(C.byref(d), C.byref(mx), _stream()), what)
+
+
+def qkv_mx8(x2d: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, ln, B: int, H: int, N: int, D: int,
+            alpha: float = 1.0, alpha_cols: int = 0, out=None):
+    """The LayerNorm-folded q | k | v projection of gemm(x2d, w, bias, ln=ln, alpha=alpha, alpha_cols=alpha_cols, vt=..., vt_col0=2*H*D,
+    vt_tokens=N) with its output written as MX-fp8 (pbe_gemm_mx8out_f16): returns (q, k, vt) Mx8 operands, byte for byte what
+    quant_mx8 makes of that gemm's fp16 q | k and V^T (alpha 1).  out: optional (q, k, vt) Mx8 targets to write into."""
+    _h(x2d, "qkv_mx8 x"); _h(w, "qkv_mx8 w")
+    M, K, lda = _rows(x2d, "qkv_mx8 x")
+    Nw, Kw, ldw = _rows(w, "qkv_mx8 w")
+    inner = H * D
+    if Kw != K or Nw != 3 * inner or M != B * N:
+        raise _l.PbeError(f"qkv_mx8: need w [3*H*D, K] and x [B*N, K], got {tuple(w.shape)} / {tuple(x2d.shape)}")
+    if bias is not None:
+        _f(bias, "qkv_mx8 bias")
+    st, colsum, eps = ln
+    _f(colsum, "qkv_mx8 ln colsum")
+    if colsum.numel() != Nw or st.ld - st.row0 < M:
+        raise _l.PbeError("qkv_mx8: LayerNorm fold needs colsum [3*H*D] and row statistics for every row of x")
+    q, k, v = (_mx8_target(m, B, H, N, D, x2d.device, o) for m, o in zip((MX8_TOKENS, MX8_TOKENS, MX8_VT), out or (None,) * 3))
+    key = f"gx:{M}:{Nw}:{K}:1"
+    d = _l.GemmDesc(_p(x2d), None, _p(w), None, _p(bias), None, None, M, Nw, K, K, lda, 0, ldw, 0, 0, 0, 1, 0, 0, 0, 0, 1, float(alpha), ACT_NONE, 0,
+                    None, 0, -1)
+    d.alpha_cols = int(alpha_cols)
+    d.ln_stats, d.ln_parts, d.ln_stats_ld, d.ln_colsum, d.ln_eps = st.ptr(), st.parts, st.ld, _p(colsum), float(eps)
+    d.vt_col0, d.vt_tokens = 2 * inner, N
+    mx = _mx8_desc([(q, 0, 1.0), (k, inner, 1.0), (v, 2 * inner, 1.0)], False)
+    d.tile_cfg = _mx8_tile_cfg(d, mx, key, D)
+    if _PIN_SCALE != 1:                         # run_paired: the MX tile of the batch-2B layer (no split-K: the bits do not depend on it)
+        sc = _PIN_SCALE
+        ck = ("mx8", f"gx:{M * sc}:{Nw}:{K}:1", D, _FORCE_CFG)
+        hit = _PIN_CACHE.get(ck)
+        if hit is None:
+            big = _l.GemmDesc.from_buffer_copy(d)
+            big.M, big.ln_stats_ld = M * sc, max(st.ld, M * sc)
+            bmx = _l.Mx8OutDesc.from_buffer_copy(mx)
+            for i in range(3):
+                bmx.r[i].B = B * sc
+            big.tile_cfg = _mx8_tile_cfg(big, bmx, ck[1], D)
+            hit = _PIN_CACHE[ck] = _mx8_plan(big, bmx)[0]
+        d.tile_cfg = hit
+    _gemm_mx8out(d, mx, key, "pbe_gemm_mx8out_f16 (q|k|v^T)")
+    return q, k, v
+
+
+def qkv_mx8_f8(x8: torch.Tensor, sx: torch.Tensor, wqk8: torch.Tensor, sqk: torch.Tensor, wv8: torch.Tensor, sv: torch.Tensor, *,
+               B: int, H: int, N: int, D: int, q_alpha: float, out=None):
+    """The two fp8-operand projections of the linear-fp8 self-attention with MX-fp8 output: q | k = gemm_f8(x8, sx, wqk8, sqk) and
+    V^T = gemm_f8(wv8 per sample, sv, x8 per sample, sx) -> (q, k, vt) Mx8 operands, byte for byte quant_mx8 of those fp16 outputs
+    (q with alpha q_alpha).  out: optional (q, k, vt) Mx8 targets to write into."""
+    for t, what in ((x8, "x8"), (wqk8, "wqk8"), (wv8, "wv8")):
+        _req(t, torch.uint8, f"qkv_mx8_f8 {what}")
+    for t, what in ((sx, "sx"), (sqk, "sqk"), (sv, "sv")):
+        _f(t, f"qkv_mx8_f8 {what}")
+    M, K, lda = _rows(x8, "qkv_mx8_f8 x8")
+    Nqk, Kw, ldw = _rows(wqk8, "qkv_mx8_f8 wqk8")
+    Nv, Kv, ldv = _rows(wv8, "qkv_mx8_f8 wv8")
+    inner = H * D
+    if Kw != K or Kv != K or Nqk != 2 * inner or Nv != inner or M != B * N or sx.numel() < M or sqk.numel() < Nqk or sv.numel() < Nv:
+        raise _l.PbeError("qkv_mx8_f8: need x8 [B*N, K], wqk8 [2*H*D, K], wv8 [H*D, K], sx [B*N], sqk [2*H*D], sv [H*D]")
+    q, k, v = (_mx8_target(m, B, H, N, D, x8.device, o) for m, o in zip((MX8_TOKENS, MX8_TOKENS, MX8_VT), out or (None,) * 3))
+    key = f"g8:{M}:{Nqk}:{K}:1"
+    d = _l.GemmDesc(_p(x8), None, _p(wqk8), None, None, None, None, M, Nqk, K, K, lda, 0, ldw, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1.0, ACT_NONE, 0,
+                    None, 0, -1, _p(sx), _p(sqk), 0, 0, 1)
+    mx = _mx8_desc([(q, 0, q_alpha), (k, inner, 1.0)], False)
+    d.tile_cfg = _mx8_tile_cfg(d, mx, key, D)
+    _gemm_mx8out(d, mx, key, "pbe_gemm_mx8out_f16 (fp8 q|k)")
+    key = f"g8:{inner}:{N}:{K}:{B}"               # swapped operands: rows = channels, columns = tokens, one sample per batch entry
+    d = _l.GemmDesc(_p(wv8), None, _p(x8), None, None, None, None, inner, N, K, K, ldv, 0, lda, 0, 0, 0, 0, 0, N * lda, 0, 0, B, 1.0, ACT_NONE, 0,
+                    None, 0, -1, _p(sv), _p(sx), 0, N, 1)
+    mx = _mx8_desc([(v, 0, 1.0)], True)
+    d.tile_cfg = _mx8_tile_cfg(d, mx, key, D)
+    _gemm_mx8out(d, mx, key, "pbe_gemm_mx8out_f16 (fp8 V^T)")
+    return q, k, v
+
+
 def softmax_rows(x: torch.Tensor, scale: float) -> torch.Tensor:
     _h(x, "softmax_rows x")
     x2 = x.reshape(-1, x.shape[-1])

@@ -12,6 +12,10 @@ set_attention_precision switches the self-attention CORE (softmax(q k^T) v of ev
 "fp8":  q, k and V^T are quantised to MX-fp8 (OCP e4m3 with one power-of-two scale per 32 contraction elements, pbe_quant_mx8_f16)
         and both products run v_mfma_scale_f32_32x32x64_f8f6f4 (pbe_attention_mx8); P = exp2(s - m) <= 2^8 is rounded to e4m3 at
         scale 1 and shared by the numerator and the denominator.  attn2 (one-token context, no attention kernel) is unchanged.
+        Where the q|k|v^T projection is the LayerNorm-folded fp16 launch (linear fp16) or the two fp8-operand launches (linear fp8),
+        the projection writes the MX-fp8 operands itself (pbe_gemm_mx8out_f16: its epilogue quantises the fp16 values it would have
+        stored), so no fp16 q|k / V^T is written and no quantiser runs; the bytes are those of the quantiser path, which stays for
+        other shapes (N % 64 != 0), the unfolded projection and CrossAttention.mx8_from_projection = False (A/B runs).
         Tolerances: tests/test_attention_mx8_gpu.py.  Timing: tools/attn_mx8_ab.py.
 """
 from __future__ import annotations
