@@ -7,6 +7,7 @@ Activations are fp16; ``[B, H, W, C]`` / ``[rows, C]`` (channels last, contiguou
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import Optional, Tuple
 
 import torch
@@ -58,7 +59,7 @@ except (OSError, ValueError):
 _RECORD = None            # set to a dict by tools/autotune.py to collect the shapes a workload uses
 _PLANS = None             # set to a list by tools/layer_diff.py: (key, tile config, split-K factor, BM, BN, workgroups) per GEMM / conv launch
 _PIN_SCALE = 1            # see pinned_batch_scale
-_PIN_CACHE = {}
+_PIN_CACHE = {}           # the tile decisions of _tile that take a plan query (pinned_batch_scale, MX-fp8 tile rule)
 _PIN_MISSES = []         # (key, tile, split-K planned at the scaled batch, tile, split-K the sub-batch launch takes instead)
 
 
@@ -81,52 +82,6 @@ class pinned_batch_scale:
         return False
 
 
-def _plan_of(desc, conv: bool):
-    out, need = (C.c_int32 * 6)(), C.c_size_t()
-    lib = _l.load()
-    _l.check((lib.pbe_conv3x3_plan if conv else lib.pbe_gemm_plan)(C.byref(desc), out, C.byref(need)), "plan")
-    return list(out), int(need.value)
-
-
-def _pinned_cfg(desc, key_fn, conv: bool, field: str = "M") -> int:
-    """tile_cfg for `desc` under pinned_batch_scale: the plan of the scaled problem, cached per (shape key + every other input of
-    the plan: fused residual / output alignment, second source, workspace, forced tile).  If the launch cannot take the pinned
-    (tile, split-K) pair - the library falls back to its heuristic, which changes the fp32 summation order - the miss is recorded
-    in _PIN_MISSES and warned about once per shape (the result is still correct, only not bit-identical to the full batch)."""
-    key = key_fn(_PIN_SCALE)
-    ck = (key, bool(desc.resid), int(getattr(desc, "ldc", 0)) & 3, int(getattr(desc, "ldr", 0)) & 3, bool(getattr(desc, "A2", None) or getattr(desc, "X2", None)),
-          bool(desc.workspace), int(desc.workspace_bytes), _FORCE_CFG)
-    hit = _PIN_CACHE.get(ck)
-    if hit is None:
-        big = type(desc).from_buffer_copy(desc)
-        if conv:
-            big.B = desc.B * _PIN_SCALE
-        else:
-            setattr(big, field, getattr(desc, field) * _PIN_SCALE)
-            if field == "M":                     # extended epilogue: the scaled problem's statistics planes are as long as its rows
-                if big.ln_stats:
-                    big.ln_stats_ld = max(big.ln_stats_ld, big.M)
-                if big.row_stats_out:
-                    big.row_stats_ld = max(big.row_stats_ld, big.M)
-        big.tile_cfg = int(_FORCE_CFG) if _FORCE_CFG is not None else int(_TUNED.get(key, -1))
-        pl, _ = _plan_of(big, conv)
-        hit = pl[0] | (max(1, pl[1]) << 8)
-        small = type(desc).from_buffer_copy(desc)
-        small.tile_cfg = hit
-        got, _ = _plan_of(small, conv)
-        if got[1] != max(1, pl[1]):
-            import warnings
-            _PIN_MISSES.append((key, pl[0], pl[1], got[0], got[1]))
-            warnings.warn(f"pinned_batch_scale({_PIN_SCALE}): {key} plans tile {pl[0]} / split-K {pl[1]} at the scaled batch but the "
-                          f"sub-batch launch runs tile {got[0]} / split-K {got[1]} (different fp32 summation order)")
-        _PIN_CACHE[ck] = hit
-    return hit
-
-
-def _launch_note(desc, key: str, conv: bool):
-    if _PLANS is not None:
-        pl, _ = _plan_of(desc, conv)
-        _PLANS.append((key, *pl[:5]))
 _TIMES = None             # set to a dict by tools/shape_profile.py: key -> [(start event, end event), ...] around each launch
 
 
@@ -158,6 +113,140 @@ def _tile_cfg(key: str) -> int:
     if _FORCE_CFG is not None:
         return int(_FORCE_CFG)
     return int(_TUNED.get(key, -1))
+
+
+# ---- tiled launches, kind "gemm" / "batch" (2-D / 3-D strided batch pbe_gemm_f16), "conv" (pbe_conv3x3_f16), "mx8" (pbe_gemm_mx8out_f16) ----
+def _key(kind: str, d, stats: bool = False) -> str:
+    """Shape key of a launch (tuned table, _RECORD, _PLANS); stats: the GEMM also writes row statistics (row_stats_out is set later)."""
+    if kind == "conv":
+        return f"c:{d.B}:{d.H}:{d.W}:{d.C1}:{d.C2}:{d.Cout}:{d.stride}:{d.pad}:{d.upsample}"
+    ex = stats or d.alpha_cols or d.ln_stats or d.VT                # the extended-epilogue tiles are tuned under their own keys
+    return f"{'g8' if d.operand_dtype else 'gx' if ex else 'g'}:{d.M}:{d.N}:{d.K}:{d.batch}"
+
+
+def _plan(kind: str, d, mx=None) -> list:
+    """Host-only plan query: [tile config, split-K factor, BM, BN, workgroups, column tiles]; raises where the library refuses."""
+    out, lib = (C.c_int32 * 6)(), _l.load()
+    if kind == "mx8":
+        rc = lib.pbe_gemm_mx8out_plan(C.byref(d), C.byref(mx), out)
+    else:
+        rc = (lib.pbe_conv3x3_plan if kind == "conv" else lib.pbe_gemm_plan)(C.byref(d), out, C.byref(C.c_size_t()))
+    _l.check(rc, f"plan ({kind})")
+    return list(out)
+
+
+@functools.lru_cache(maxsize=None)
+def _layout(cls):
+    """Masks over a descriptor type's bits, nested ranges included: (all but bits 4..63 of each pointer, those bits, the bit after each)."""
+    def ptrs(t, base):
+        for f, ft in t._fields_:
+            o = base + getattr(t, f).offset
+            if issubclass(ft, C.Array):
+                yield from (p for i in range(ft._length_) for p in ptrs(ft._type_, o + i * C.sizeof(ft._type_)))
+            elif ft is C.c_void_p:
+                yield o
+    offs = list(ptrs(cls, 0))
+    hi = sum((2 ** 64 - 16) << 8 * o for o in offs)
+    return (1 << 8 * C.sizeof(cls)) - 1 - hi, hi, sum(1 << 8 * o + 64 for o in offs)
+
+
+def _desc_key(d):
+    """A descriptor as a planner can read it: every field, each pointer reduced to its address mod 16 and whether it is null, i.e. below 16
+    (adding bits 4..63 of a pointer to themselves carries out of the pointer exactly where they are not all zero)."""
+    keep, hi, after = _layout(type(d))
+    x = int.from_bytes(d, "little")
+    return x & keep, ((x & hi) + hi) & after
+
+
+def _mx8_tile(d, mx, cfg: int) -> int:
+    """cfg where the MX copy-out of d takes it, else -1: a tile that splits an MX block is refused when requested, -1 plans an aligned one."""
+    t = type(d).from_buffer_copy(d)
+    t.tile_cfg = cfg
+    try:
+        _plan("mx8", t, mx)
+        return cfg
+    except _l.PbeError:
+        return -1
+
+
+def _pinned(kind: str, d, mx=None, stats: bool = False) -> int:
+    """tile_cfg under pinned_batch_scale: the tile and split-K factor planned for the launch at _PIN_SCALE times the batch - M of a 2-D GEMM
+    (statistics planes as long as its rows), the batch count of a strided batch, B of a conv, M and every range's B of an MX copy-out (MX
+    rule applied).  A launch that cannot take that pair (other fp32 summation order, still correct) is recorded in _PIN_MISSES and warned."""
+    s, big = _PIN_SCALE, type(d).from_buffer_copy(d)
+    bmx = None if mx is None else type(mx).from_buffer_copy(mx)
+    if kind == "conv":
+        big.B *= s
+    elif kind == "batch":
+        big.batch *= s
+    else:
+        big.M *= s
+        if big.ln_stats:
+            big.ln_stats_ld = max(big.ln_stats_ld, big.M)
+        if big.row_stats_out:
+            big.row_stats_ld = max(big.row_stats_ld, big.M)
+        for i in range(0 if bmx is None else bmx.nranges):
+            bmx.r[i].B *= s
+    key = _key(kind, big, stats)
+    big.tile_cfg = int(_FORCE_CFG) if _FORCE_CFG is not None else int(_TUNED.get(key, -1))
+    if bmx is not None:
+        big.tile_cfg = _mx8_tile(big, bmx, big.tile_cfg)
+    pl = _plan(kind, big, bmx)
+    hit = pl[0] | (max(1, pl[1]) << 8)
+    small = type(d).from_buffer_copy(d)
+    small.tile_cfg = hit
+    got = _plan(kind, small, mx)
+    if got[1] != max(1, pl[1]):
+        import warnings
+        _PIN_MISSES.append((key, pl[0], pl[1], got[0], got[1]))
+        warnings.warn(f"pinned_batch_scale({s}): {key} plans tile {pl[0]} / split-K {pl[1]} at the scaled batch but the "
+                      f"sub-batch launch runs tile {got[0]} / split-K {got[1]} (different fp32 summation order)")
+    return hit
+
+
+def _tile(kind: str, d, key: str, mx=None, stats: bool = False) -> int:
+    """tile_cfg of a launch: `key`'s forced or tuned tile (counted in _RECORD), under the MX rule (_mx8_tile), or pinned (_pinned; not fp8
+    operands, which never split K).  Decisions that take plan queries are cached per shape key, descriptor, forced tile and scale."""
+    cfg = _tile_cfg(key)
+    pin = _PIN_SCALE != 1 and (kind == "conv" or not d.operand_dtype)
+    if not pin and (kind != "mx8" or cfg < 0):
+        return cfg
+    ck = (key, cfg, _FORCE_CFG, _PIN_SCALE if pin else 1, _desc_key(d), None if mx is None else _desc_key(mx))
+    hit = _PIN_CACHE.get(ck)
+    if hit is None:
+        hit = _PIN_CACHE[ck] = _pinned(kind, d, mx, stats) if pin else _mx8_tile(d, mx, cfg)
+    return hit
+
+
+def _mx8_tile_cfg(d, mx, key: str, D: int) -> int:
+    """_tile of an MX copy-out outside pinned_batch_scale (D, the head dim, is that of mx's ranges)."""
+    with pinned_batch_scale(1):
+        return _tile("mx8", d, key, mx)
+
+
+def _launch(kind: str, d, mx=None, row_stats=None):
+    """Launch a filled descriptor (but for tile_cfg: _tile, chosen before row_stats_out is set).  row_stats (GEMM): called with the
+    planned column-tile count once the tile is settled, returns the RowStats the epilogue fills; _launch returns it."""
+    key = _key(kind, d, row_stats is not None)
+    d.tile_cfg = _tile(kind, d, key, mx, row_stats is not None)
+    stats = None
+    if row_stats is not None:                   # one partial per column tile of the plan this launch will take
+        d.row_stats_out = 8                     # (any non-null value: the plan only needs to know the form)
+        stats = row_stats(_plan(kind, d)[5])
+        d.row_stats_out, d.row_stats_ld = stats.ptr(), stats.ld
+    if _PLANS is not None:
+        _PLANS.append((key, *_plan(kind, d, mx)[:5]))
+    if _TIMES is not None:                      # the _TIMES key: shape key + epilogue form
+        key += "" if kind == "conv" else "|mx8" if kind == "mx8" else \
+            f"|a{d.act}{'r' * bool(d.resid)}{'v' * bool(d.rowvec)}{'L' * bool(d.ln_stats)}{'S' * (stats is not None)}{'T' * bool(d.VT)}"
+    with _timed(key):
+        if kind == "mx8":
+            _l.check(_l.load().pbe_gemm_mx8out_f16(C.byref(d), C.byref(mx), _stream()), "pbe_gemm_mx8out_f16")
+        elif kind == "conv":
+            _l.check(_l.load().pbe_conv3x3_f16(C.byref(d), _stream()), "pbe_conv3x3_f16")
+        else:
+            _l.check(_l.load().pbe_gemm_f16(C.byref(d), _stream()), "pbe_gemm_f16")
+    return stats
 
 
 def _splitk_ws(device):
@@ -254,13 +343,10 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         ldv = rowvec.stride(0) if rowvec.dim() == 2 else 0
         if group_rows <= 0:
             raise _l.PbeError("gemm: rowvec needs group_rows")
-    ex = bool(alpha_cols or ln is not None or row_stats is not False or vt is not None)
-    kp = "gx" if ex else "g"                   # the extended-epilogue tiles are tuned under their own keys
     d = _l.GemmDesc(_p(a), _p(a2), _p(w), _p(_h(out, "gemm out")), _p(bias), _p(rowvec), _p(resid), M, N, K, K1, lda, lda2, ldw, ldc, ldr,
                     ldv, group_rows, sA, sW, sC, sR, batch, float(alpha), act, 1 if bias_per_row else 0,
-                    _splitk_ws(a.device).data_ptr(), SPLITK_WS_BYTES, _tile_cfg(f"{kp}:{M}:{N}:{K}:{batch}"))
-    stats = None
-    if ex:
+                    _splitk_ws(a.device).data_ptr(), SPLITK_WS_BYTES, -1)
+    if alpha_cols or ln is not None or row_stats is not False or vt is not None:
         if a.dim() != 2:
             raise _l.PbeError("gemm: the extended epilogue takes 2-D operands")
         d.alpha_cols = int(alpha_cols)
@@ -275,25 +361,14 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
             if vt.dim() != 3 or vt.stride(2) != 1 or vt.shape[1] != N - vt_col0 or vt.shape[0] * vt_tokens != M:
                 raise _l.PbeError(f"gemm: vt must be [M / vt_tokens, N - vt_col0, >= vt_tokens], got {tuple(vt.shape)}")
             d.VT, d.vt_col0, d.vt_tokens, d.vt_bs, d.vt_rs = _p(vt), int(vt_col0), int(vt_tokens), vt.stride(0), vt.stride(1)
-    if _PIN_SCALE != 1:
-        if a.dim() == 3:                        # per-sample strided batch (V^T projection): the batch count scales, not M
-            d.tile_cfg = _pinned_cfg(d, lambda sc: f"g:{M}:{N}:{K}:{batch * sc}", False, "batch")
-        else:
-            d.tile_cfg = _pinned_cfg(d, lambda sc: f"{kp}:{M * sc}:{N}:{K}:1", False)
-    if row_stats is not False:                  # one partial per column tile of the plan this launch will take
-        d.row_stats_out = 8                     # (any non-null value: the plan only needs to know the form)
-        parts = _plan_of(d, False)[0][5]
-        if isinstance(row_stats, RowStats):
-            stats = row_stats
-            if stats.parts < parts:
-                raise _l.PbeError(f"gemm: row_stats buffer holds {stats.parts} partials, the plan writes {parts}")
-            stats = RowStats(stats.buf, parts, stats.ld, stats.row0)
-        else:
-            stats = RowStats(torch.empty((parts, M, 2), dtype=torch.float32, device=a.device), parts, M)
-        d.row_stats_out, d.row_stats_ld = stats.ptr(), stats.ld
-    _launch_note(d, f"{kp}:{M}:{N}:{K}:{batch}", False)
-    with _timed(f"{kp}:{M}:{N}:{K}:{batch}|a{act}{'r' if resid is not None else ''}{'v' if rowvec is not None else ''}{'L' if ln is not None else ''}{'S' if stats is not None else ''}{'T' if vt is not None else ''}"):
-        _l.check(_l.load().pbe_gemm_f16(C.byref(d), _stream()), "pbe_gemm_f16")
+
+    def fill(parts):                            # the RowStats of the output rows, `parts` partials
+        if not isinstance(row_stats, RowStats):
+            return RowStats(torch.empty((parts, M, 2), dtype=torch.float32, device=a.device), parts, M)
+        if row_stats.parts < parts:
+            raise _l.PbeError(f"gemm: row_stats buffer holds {row_stats.parts} partials, the plan writes {parts}")
+        return RowStats(row_stats.buf, parts, row_stats.ld, row_stats.row0)
+    stats = _launch("batch" if a.dim() == 3 else "gemm", d, row_stats=None if row_stats is False else fill)
     return (out, stats) if row_stats is not False else out
 
 
@@ -314,36 +389,25 @@ def conv3x3(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], *, 
     if x.dim() != 4 or not x.is_contiguous():
         raise _l.PbeError("conv3x3: x must be a contiguous [B,H,W,C] tensor")
     B, H, W, C1 = x.shape
-    C2 = 0
-    if wp.dim() == 3:                            # pack_conv3x3_up_phases: the upsampling conv as four 2x2 convs on the source grid (4 / 9 of the MACs)
+    C2 = ldv = 0
+    phase = wp.dim() == 3                        # pack_conv3x3_up_phases: the upsampling conv as four 2x2 convs on the source grid (4 / 9 of the MACs)
+    if phase:
         if not upsample or x2 is not None or resid is not None or rowvec is not None or stride != 1 or pad != 1:
             raise _l.PbeError("conv3x3: phase-packed weights are for the plain nearest-2x upsampling conv")
         if wp.shape[0] != 4 or not wp.is_contiguous() or wp.shape[2] != 4 * C1:
             raise _l.PbeError(f"conv3x3: phase-packed weight must be [4, Cout, {4 * C1}], got {tuple(wp.shape)}")
         Cout = wp.shape[1]
-        y = torch.empty((B, 2 * H, 2 * W, Cout), dtype=torch.float16, device=x.device)
-        if bias is not None:
-            _f(bias, "conv3x3 bias")
-        key = f"c:{B}:{H}:{W}:{C1}:0:{Cout}:1:1:2"
-        d = _l.Conv3x3Desc(_p(x), None, _p(wp), _p(y), _p(bias), None, None, B, H, W, C1, 0, Cout, 1, 1, 2, 0, act, _splitk_ws(x.device).data_ptr(),
-                           SPLITK_WS_BYTES, _tile_cfg(key), conv_kblock(C1, 0))
-        if _PIN_SCALE != 1:
-            d.tile_cfg = _pinned_cfg(d, lambda sc: f"c:{B * sc}:{H}:{W}:{C1}:0:{Cout}:1:1:2", True)
-        _launch_note(d, key, True)
-        with _timed(key):
-            _l.check(_l.load().pbe_conv3x3_f16(C.byref(d), _stream()), "pbe_conv3x3_f16 (upsample, phase form)")
-        return y
-    if x2 is not None:
-        _h(x2, "conv3x3 x2")
-        if x2.dim() != 4 or not x2.is_contiguous() or x2.shape[:3] != x.shape[:3]:
-            raise _l.PbeError("conv3x3: x2 must match x in [B,H,W]")
-        C2 = x2.shape[3]
-    Cout = wp.shape[0]
-    if wp.dim() != 2 or not wp.is_contiguous() or wp.shape[1] != 9 * (C1 + C2):
-        raise _l.PbeError(f"conv3x3: packed weight must be [Cout, {9 * (C1 + C2)}], got {tuple(wp.shape)}")
+    else:
+        if x2 is not None:
+            _h(x2, "conv3x3 x2")
+            if x2.dim() != 4 or not x2.is_contiguous() or x2.shape[:3] != x.shape[:3]:
+                raise _l.PbeError("conv3x3: x2 must match x in [B,H,W]")
+            C2 = x2.shape[3]
+        Cout = wp.shape[0]
+        if wp.dim() != 2 or not wp.is_contiguous() or wp.shape[1] != 9 * (C1 + C2):
+            raise _l.PbeError(f"conv3x3: packed weight must be [Cout, {9 * (C1 + C2)}], got {tuple(wp.shape)}")
     Ho, Wo = conv_out_hw(H, W, stride, pad, upsample)
     y = torch.empty((B, Ho, Wo, Cout), dtype=torch.float16, device=x.device)
-    ldv = 0
     if rowvec is not None:
         _h(rowvec, "conv3x3 rowvec")
         if rowvec.dim() != 2 or rowvec.shape[0] != B or rowvec.stride(1) != 1:
@@ -356,18 +420,13 @@ def conv3x3(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], *, 
     if bias is not None:
         _f(bias, "conv3x3 bias")
     d = _l.Conv3x3Desc(_p(x), _p(x2), _p(wp), _p(y), _p(bias), _p(rowvec), _p(resid), B, H, W, C1, C2, Cout, stride, pad,
-                       1 if upsample else 0, ldv, act, _splitk_ws(x.device).data_ptr(), SPLITK_WS_BYTES,
-                       _tile_cfg(f"c:{B}:{H}:{W}:{C1}:{C2}:{Cout}:{stride}:{pad}:{int(bool(upsample))}"), conv_kblock(C1, C2), None, 0, None)
+                       2 if phase else int(bool(upsample)), ldv, act, _splitk_ws(x.device).data_ptr(), SPLITK_WS_BYTES, -1, conv_kblock(C1, C2))
     gs_buf = gs_blocks = None
-    if group_stats > 0 and USE_CONV_GROUP_STATS and Cout % group_stats == 0 and Ho * Wo >= 64:
+    if group_stats > 0 and USE_CONV_GROUP_STATS and not phase and Cout % group_stats == 0 and Ho * Wo >= 64:
         gs_buf = torch.empty((B, (Ho * Wo) // 64, group_stats, 2), dtype=torch.float32, device=x.device)       # room for the smallest row block (64)
         gs_blocks = C.c_int32(0)
         d.group_stats_out, d.group_stats_groups, d.group_stats_blocks = gs_buf.data_ptr(), group_stats, C.cast(C.pointer(gs_blocks), C.c_void_p)
-    if _PIN_SCALE != 1:
-        d.tile_cfg = _pinned_cfg(d, lambda sc: f"c:{B * sc}:{H}:{W}:{C1}:{C2}:{Cout}:{stride}:{pad}:{int(bool(upsample))}", True)
-    _launch_note(d, f"c:{B}:{H}:{W}:{C1}:{C2}:{Cout}:{stride}:{pad}:{int(bool(upsample))}", True)
-    with _timed(f"c:{B}:{H}:{W}:{C1}:{C2}:{Cout}:{stride}:{pad}:{int(bool(upsample))}"):
-        _l.check(_l.load().pbe_conv3x3_f16(C.byref(d), _stream()), "pbe_conv3x3_f16")
+    _launch("conv", d)
     if gs_blocks is not None and gs_blocks.value > 0:
         y._pbe_gstats = GroupStats(gs_buf, B, int(gs_blocks.value), group_stats, y._version)
     return y
@@ -495,11 +554,8 @@ def gemm_f8(a8: torch.Tensor, a_scale: torch.Tensor, w8: torch.Tensor, w_scale: 
     if bias is not None:
         _f(bias, "gemm_f8 bias")
     d = _l.GemmDesc(_p(a8), None, _p(w8), _p(_h(out, "gemm_f8 out")), _p(bias), None, _p(resid), M, N, K, K, lda, 0, ldw, ldc, ldr,
-                    0, 0, sA, sW, sC, 0, batch, float(alpha), act, 0, None, 0, _tile_cfg(f"g8:{M}:{N}:{K}:{batch}"),
-                    _p(a_scale), _p(w_scale), ssa, ssw, 1)
-    _launch_note(d, f"g8:{M}:{N}:{K}:{batch}", False)
-    with _timed(f"g8:{M}:{N}:{K}:{batch}|a{act}{'r' if resid is not None else ''}"):
-        _l.check(_l.load().pbe_gemm_f16(C.byref(d), _stream()), "pbe_gemm_f16 (fp8 operands)")
+                    0, 0, sA, sW, sC, 0, batch, float(alpha), act, 0, None, 0, -1, _p(a_scale), _p(w_scale), ssa, ssw, 1)
+    _launch("batch" if a8.dim() == 3 else "gemm", d)
     return out
 
 
@@ -618,42 +674,6 @@ def _mx8_desc(ranges, channel_rows: bool):
     return mx
 
 
-def _mx8_plan(d, mx):
-    """Host-only plan query of pbe_gemm_mx8out_f16: [tile config, split-K (1), BM, BN, workgroups, column tiles]; raises where refused."""
-    out = (C.c_int32 * 6)()
-    _l.check(_l.load().pbe_gemm_mx8out_plan(C.byref(d), C.byref(mx), out), "pbe_gemm_mx8out_plan")
-    return list(out)
-
-
-_MX8_TUNED = {}
-
-
-def _mx8_tile_cfg(d, mx, key: str, D: int) -> int:
-    """The tuned tile of `key` where it keeps every MX block whole, else -1: the planner then chooses among the aligned tiles
-    (pbe_gemm_mx8out_f16 refuses an explicitly requested tile that splits a block).  Cached per shape."""
-    want = _tile_cfg(key)
-    ck = (key, D, mx.channel_rows, want)
-    hit = _MX8_TUNED.get(ck)
-    if hit is None:
-        hit = want
-        if want >= 0:
-            t = _l.GemmDesc.from_buffer_copy(d)
-            t.tile_cfg = want
-            out = (C.c_int32 * 6)()
-            if _l.load().pbe_gemm_mx8out_plan(C.byref(t), C.byref(mx), out) != 0:
-                hit = -1
-        _MX8_TUNED[ck] = hit
-    return hit
-
-
-def _gemm_mx8out(d, mx, key: str, what: str):
-    """Launch pbe_gemm_mx8out_f16 (d.tile_cfg from the tuned table; under pinned_batch_scale the MX tile of the scaled layer)."""
-    if _PLANS is not None:
-        _PLANS.append((key, *_mx8_plan(d, mx)[:5]))
-    with _timed(f"{key}|mx8"):
-        _l.check(_l.load().pbe_gemm_mx8out_f16(C.byref(d), C.byref(mx), _stream()), what)
-
-
 def qkv_mx8(x2d: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, ln, B: int, H: int, N: int, D: int,
             alpha: float = 1.0, alpha_cols: int = 0, out=None):
     """The LayerNorm-folded q | k | v projection of gemm(x2d, w, bias, ln=ln, alpha=alpha, alpha_cols=alpha_cols, vt=..., vt_col0=2*H*D,
@@ -672,28 +692,12 @@ def qkv_mx8(x2d: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *,
     if colsum.numel() != Nw or st.ld - st.row0 < M:
         raise _l.PbeError("qkv_mx8: LayerNorm fold needs colsum [3*H*D] and row statistics for every row of x")
     q, k, v = (_mx8_target(m, B, H, N, D, x2d.device, o) for m, o in zip((MX8_TOKENS, MX8_TOKENS, MX8_VT), out or (None,) * 3))
-    key = f"gx:{M}:{Nw}:{K}:1"
     d = _l.GemmDesc(_p(x2d), None, _p(w), None, _p(bias), None, None, M, Nw, K, K, lda, 0, ldw, 0, 0, 0, 1, 0, 0, 0, 0, 1, float(alpha), ACT_NONE, 0,
                     None, 0, -1)
     d.alpha_cols = int(alpha_cols)
     d.ln_stats, d.ln_parts, d.ln_stats_ld, d.ln_colsum, d.ln_eps = st.ptr(), st.parts, st.ld, _p(colsum), float(eps)
     d.vt_col0, d.vt_tokens = 2 * inner, N
-    mx = _mx8_desc([(q, 0, 1.0), (k, inner, 1.0), (v, 2 * inner, 1.0)], False)
-    d.tile_cfg = _mx8_tile_cfg(d, mx, key, D)
-    if _PIN_SCALE != 1:                         # run_paired: the MX tile of the batch-2B layer (no split-K: the bits do not depend on it)
-        sc = _PIN_SCALE
-        ck = ("mx8", f"gx:{M * sc}:{Nw}:{K}:1", D, _FORCE_CFG)
-        hit = _PIN_CACHE.get(ck)
-        if hit is None:
-            big = _l.GemmDesc.from_buffer_copy(d)
-            big.M, big.ln_stats_ld = M * sc, max(st.ld, M * sc)
-            bmx = _l.Mx8OutDesc.from_buffer_copy(mx)
-            for i in range(3):
-                bmx.r[i].B = B * sc
-            big.tile_cfg = _mx8_tile_cfg(big, bmx, ck[1], D)
-            hit = _PIN_CACHE[ck] = _mx8_plan(big, bmx)[0]
-        d.tile_cfg = hit
-    _gemm_mx8out(d, mx, key, "pbe_gemm_mx8out_f16 (q|k|v^T)")
+    _launch("mx8", d, _mx8_desc([(q, 0, 1.0), (k, inner, 1.0), (v, 2 * inner, 1.0)], False))
     return q, k, v
 
 
@@ -713,18 +717,13 @@ def qkv_mx8_f8(x8: torch.Tensor, sx: torch.Tensor, wqk8: torch.Tensor, sqk: torc
     if Kw != K or Kv != K or Nqk != 2 * inner or Nv != inner or M != B * N or sx.numel() < M or sqk.numel() < Nqk or sv.numel() < Nv:
         raise _l.PbeError("qkv_mx8_f8: need x8 [B*N, K], wqk8 [2*H*D, K], wv8 [H*D, K], sx [B*N], sqk [2*H*D], sv [H*D]")
     q, k, v = (_mx8_target(m, B, H, N, D, x8.device, o) for m, o in zip((MX8_TOKENS, MX8_TOKENS, MX8_VT), out or (None,) * 3))
-    key = f"g8:{M}:{Nqk}:{K}:1"
     d = _l.GemmDesc(_p(x8), None, _p(wqk8), None, None, None, None, M, Nqk, K, K, lda, 0, ldw, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1.0, ACT_NONE, 0,
                     None, 0, -1, _p(sx), _p(sqk), 0, 0, 1)
-    mx = _mx8_desc([(q, 0, q_alpha), (k, inner, 1.0)], False)
-    d.tile_cfg = _mx8_tile_cfg(d, mx, key, D)
-    _gemm_mx8out(d, mx, key, "pbe_gemm_mx8out_f16 (fp8 q|k)")
-    key = f"g8:{inner}:{N}:{K}:{B}"               # swapped operands: rows = channels, columns = tokens, one sample per batch entry
+    _launch("mx8", d, _mx8_desc([(q, 0, q_alpha), (k, inner, 1.0)], False))
+    # swapped operands: rows = channels, columns = tokens, one sample per batch entry
     d = _l.GemmDesc(_p(wv8), None, _p(x8), None, None, None, None, inner, N, K, K, ldv, 0, lda, 0, 0, 0, 0, 0, N * lda, 0, 0, B, 1.0, ACT_NONE, 0,
                     None, 0, -1, _p(sv), _p(sx), 0, N, 1)
-    mx = _mx8_desc([(v, 0, 1.0)], True)
-    d.tile_cfg = _mx8_tile_cfg(d, mx, key, D)
-    _gemm_mx8out(d, mx, key, "pbe_gemm_mx8out_f16 (fp8 V^T)")
+    _launch("mx8", d, _mx8_desc([(v, 0, 1.0)], True))
     return q, k, v
 
 
