@@ -61,6 +61,7 @@ size_t pbe_sizeof_conv3x3_desc(void);
 size_t pbe_sizeof_attn_desc(void);
 size_t pbe_sizeof_attn_mx8_desc(void);
 size_t pbe_sizeof_mx8_out_desc(void);
+size_t pbe_sizeof_ctx_attn_desc(void);
 
 /* ---------------------------------------------------------------------------------------------
  * pbe_gemm_f16 — C[m,n] = act(alpha * sum_k A[m,k] * W[n,k] + bias + rowvec[m / group_rows, n]) + R[m,n]
@@ -295,6 +296,42 @@ typedef struct pbe_mx8_out_desc {
 } pbe_mx8_out_desc;
 int pbe_gemm_mx8out_f16(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, pbe_stream_t stream);
 int pbe_gemm_mx8out_plan(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, int32_t* out6);
+
+/* ---------------------------------------------------------------------------------------------
+ * pbe_ctx_attention_f16 — x + attn2(LayerNorm(x), context) of a transformer block (attention.py:207-230, 268-272) for a SHORT context
+ * of Nk = 1..16 tokens, as one launch over the residual stream.  Everything that depends on the context alone is folded by the caller
+ * (once per context, pbe_gemm_f16 launches): with k = to_k(context), v = to_v(context), per sample b, head h, context token j
+ *   Kq[b, h*Nk + j, c] = scale * log2(e) * gamma[c] * sum_d k[b,j,h,d] * Wq[h*D + d, c]      fp16 [B, HJ, C], HJ = H * Nk
+ *   colsum[b, hj]      = sum_c of the fp16 values Kq[b, hj, c];  kbias[b, hj] = scale * log2(e) * sum_d k[b,j,h,d] * (Wq beta)[h*D + d]
+ *   Vo[b, c, h*Nk + j] = sum_d Wo[c, h*D + d] * v[b,j,h,d]                                    fp16 [B, C, HJ]
+ * and the kernel computes, for row m of sample b = m / tokens,
+ *   Y[m,:] = X[m,:] + bias + sum_{h, j<Nk} softmax_j( rstd[m] * (X[m,:] . Kq[b,hj,:] - mean[m] * colsum[b,hj]) + kbias[b,hj] ) * Vo[b,:,hj]
+ * The head dimension D is folded away.  Both products run on the matrix cores with fp32 accumulation; the softmax (exp2: the scores
+ * are in the log2 domain) runs in fp32 over each head's Nk columns with the group maximum subtracted, its weights are rounded to fp16
+ * once.  mean / rstd come from the row statistics of X under the contract of pbe_gemm_desc.ln_stats (float2 (sum, sumsq) partials:
+ * the producer's row_stats_out, or pbe_row_stats_f16).  row_stats_out (or NULL): float2 [M] (sum, sumsq) of the stored fp16 rows of
+ * Y, ONE partial (the layout of pbe_row_stats_f16), for the LayerNorm-folded GEMM that reads Y.  Row tiles never straddle two
+ * samples; Kq rows and Vo columns past HJ are never read as values (operands may be padded or not).  Bit-reproducible run to run.
+ * Accepted: C % 64 == 0, 64 <= C <= 1280, 1 <= Nk <= 16, H * Nk <= 128, M a multiple of tokens >= 1; leading dimensions and batch
+ * strides multiples of 8 elements, vo_rs >= HJ rounded up to 8, X / Y / Kq / Vo 16-byte aligned.  Anything else: PBE_EINVAL.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct pbe_ctx_attn_desc {
+    const void* X;          /* fp16 [M, C], leading dim ldx: the residual stream (raw, not normalised)  */
+    void* Y;                /* fp16 [M, C], leading dim ldy                                              */
+    const void* Kq;         /* fp16: element (b, hj, c) at Kq[b*kq_bs + hj*kq_rs + c]                    */
+    const float* colsum;    /* fp32: element (b, hj) at colsum[b*cs_bs + hj]                             */
+    const float* kbias;     /* fp32: element (b, hj) at kbias[b*cs_bs + hj]                              */
+    const void* Vo;         /* fp16: element (b, c, hj) at Vo[b*vo_bs + c*vo_rs + hj]                    */
+    const float* bias;      /* fp32 [C]: to_out's bias                                                   */
+    const float* ln_stats;  /* float2 [ln_parts][ln_stats_ld] partial (sum, sumsq) of X's rows           */
+    float* row_stats_out;   /* float2 [M] (sum, sumsq) of Y's stored rows, or NULL                       */
+    int32_t M, C, tokens, H, Nk;
+    int64_t ldx, ldy, kq_bs, kq_rs, vo_bs, vo_rs, cs_bs;
+    int32_t ln_parts;
+    int64_t ln_stats_ld;
+    float ln_eps;
+} pbe_ctx_attn_desc;
+int pbe_ctx_attention_f16(const pbe_ctx_attn_desc* d, pbe_stream_t stream);
 
 /* pbe_softmax_rows_f16 — Y[r,:] = softmax(scale * X[r,:]) over rows of `cols` fp16 (VAE mid attention,
  * model.py:193-195: one head, d = 512, N = 4096, scores kept in HBM once per image). */

@@ -10,7 +10,7 @@ import torch
 
 from pbe_amd import ops
 from pbe_amd.lib import PbeError
-from ldm.models.diffusion.plms import PLMSSampler, inpaint_kwargs
+from ldm.models.diffusion.plms import PLMSSampler, guidance_context, inpaint_kwargs
 
 
 class DDIMSampler(PLMSSampler):
@@ -55,10 +55,7 @@ class DDIMSampler(PLMSSampler):
         msk = msk.to(device=device, dtype=torch.float32).contiguous()
         guided = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
         if guided:
-            uc = unconditional_conditioning.to(device)
-            if uc.shape[0] != b:
-                uc = uc.expand(b, *uc.shape[1:])
-            ctx = torch.cat((uc.to(torch.float16), cond.to(device=device, dtype=torch.float16))).contiguous()
+            ctx = guidance_context(cond, unconditional_conditioning, b, device)      # a one-token uc is repeated to cond's K tokens (exact: plms.py)
         else:
             ctx = cond.to(device=device, dtype=torch.float16).contiguous()
         dup = 2 if guided else 1

@@ -43,6 +43,25 @@ def inpaint_kwargs(kwargs):
     return z, m
 
 
+def guidance_context(cond, uc, b, device):
+    """The [uc | c] context of a guidance pair (plms.py:185-187) as fp16 [2b, K, D].  cond [b, K, D] may hold K >= 1 tokens per sample
+    (several exemplars); a ONE-token uc is repeated to K tokens.  That is exact, not an approximation: K copies of one key give K equal
+    scores, the softmax weights are 1/K each, and the weighted sum of K equal values is that value - attn2 of the repeated context is
+    attn2 of the single token.  Any other difference in length is refused (per-sample exemplar counts would need a mask)."""
+    uc = uc.to(device)
+    cond = cond.to(device)
+    if uc.shape[0] != b:                           # scripts/inference.py:325 hands [1,1,768]; the test bench repeats it
+        uc = uc.expand(b, *uc.shape[1:])
+    if uc.dim() != 3 or cond.dim() != 3:
+        raise PbeError(f"sampler: conditioning must be [B, K, D], got {tuple(cond.shape)} / {tuple(uc.shape)}")
+    if uc.shape[1] != cond.shape[1]:
+        if uc.shape[1] != 1:
+            raise PbeError(f"sampler: unconditional_conditioning has {uc.shape[1]} tokens, conditioning {cond.shape[1]}: "
+                           "only a one-token unconditional context can be repeated (per-sample context lengths are not supported)")
+        uc = uc.expand(-1, cond.shape[1], -1)
+    return torch.cat((uc.to(torch.float16), cond.to(torch.float16))).contiguous()
+
+
 class PLMSSampler(object):
     def __init__(self, model, schedule="linear", **kwargs):
         self.model = model
@@ -137,10 +156,7 @@ class PLMSSampler(object):
         cond = cond.to(device)
         guided = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
         if guided:
-            uc = unconditional_conditioning.to(device)
-            if uc.shape[0] != b:                       # scripts/inference.py:325 hands [1,1,768]; the test bench repeats it
-                uc = uc.expand(b, *uc.shape[1:])
-            ctx = torch.cat((uc.to(torch.float16), cond.to(torch.float16))).contiguous()
+            ctx = guidance_context(cond, unconditional_conditioning, b, device)      # a one-token uc is repeated to cond's K tokens (exact)
         else:
             ctx = cond.to(torch.float16).contiguous()
         dup = 2 if guided else 1

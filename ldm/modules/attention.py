@@ -11,6 +11,10 @@ ldm/modules/attention.py in zhanwenchen/pbe (GEGLU :38-45, FeedForward :48-65, C
     SURVEY.md K6): it is computed once per context as a [B, C] vector and added inside the
     epilogue of attn1's output projection.  norm2 / attn2.to_q / attn2.to_k keep their
     parameters (checkpoint compatibility) but are dead arithmetic on this path,
+  * a context of SEVERAL tokens (several exemplars) keeps that structure: everything that depends
+    on the context alone is folded once per context into two skinny operands, and
+    ``x + attn2(norm2(x), ctx)`` is ONE launch over the residual stream (pbe_ctx_attention_f16,
+    DESIGN.md section 4.11); contexts longer than that kernel takes run q / attention / to_out,
   * bias, residual and the row-broadcast adds are GEMM epilogues.
 """
 from types import SimpleNamespace
@@ -223,6 +227,18 @@ class CrossAttention(HipModule):
         return ops.gemm(o.view(B * N, inner), p.wo, p.bo).view(B, N, -1)
 
 
+class ContextKV:
+    """What the existing-kernel route of a multi-token attn2 keeps per context: k = to_k(context) [B*Nk, inner] and
+    vt = to_v(context)^T [B, inner, npad] (npad = Nk rounded up to 8, zeros past Nk)."""
+    __slots__ = ("k", "vt", "B", "Nk")
+
+    def __init__(self, k, vt, B, Nk):
+        self.k, self.vt, self.B, self.Nk = k, vt, B, Nk
+
+    def rows(self, b0, b1):
+        return ContextKV(self.k[b0 * self.Nk:b1 * self.Nk], self.vt[b0:b1], b1 - b0, self.Nk)
+
+
 class BasicTransformerBlock(HipModule):
     def __init__(self, dim, n_heads, d_head, dropout=0., context_dim=None, gated_ff=True, checkpoint=True):
         super().__init__()
@@ -248,7 +264,32 @@ class BasicTransformerBlock(HipModule):
         F = w.shape[0] // 2
         wi, bi = torch.stack([w[:F], w[F:]], 1).reshape(2 * F, -1), torch.stack([b[:F], b[F:]], 1).reshape(2 * F)   # (value, gate) rows interleaved
         ns.wg, ns.c2g, ns.c1g = ops.pack_linear_ln(wi, bi, n3.weight, n3.bias)
+        ns.m2 = None                                     # the multi-token attn2 pack, built on first use (_pack_multi)
         return ns
+
+    def _pack_multi(self):
+        """The pack of attn2 with a multi-token context (kept on pk(), built on first use: the one-token path never pays for it)."""
+        ns = self.pk()
+        if ns.m2 is not None:
+            return ns.m2
+        m = SimpleNamespace()
+        with torch.no_grad():
+            # attn2 with a multi-token context (context_operands): norm2 folded into to_q - for the existing-kernel route as a LayerNorm-
+            # folded q projection, for pbe_ctx_attention_f16 as per-head [C + 8, D] blocks whose rows are (Wq gamma2)[hD + d, c] for c < C
+            # and (Wq beta2)[hD + d] at c = C, so ONE batched GEMM with to_k(context) gives Kq and the Kq . beta term; Wo per head likewise
+            a2, n2 = self.attn2, self.norm2
+            H, D, Cq = a2.heads, a2.dim_head, a2.to_q.weight.shape[1]
+            m.g2, m.b2, m.eps2 = f32(n2.weight), f32(n2.bias), n2.eps
+            m.qscale2 = a2.scale * 1.4426950408889634
+            m.wq2, m.c2q2, m.c1q2 = ops.pack_linear_ln(a2.to_q.weight, None, n2.weight, n2.bias)
+            wq32 = a2.to_q.weight.detach().float()
+            ext = torch.zeros((H, Cq + 8, D), dtype=torch.float32, device=wq32.device)
+            ext[:, :Cq] = (wq32 * n2.weight.detach().float()[None, :]).view(H, D, Cq).permute(0, 2, 1)
+            ext[:, Cq] = (wq32.double() @ n2.bias.detach().double()).float().view(H, D)
+            m.wq2h = ext.to(torch.float16).contiguous()
+            m.wo2h = a2.to_out[0].weight.detach().float().view(-1, H, D).permute(1, 0, 2).to(torch.float16).contiguous()      # [H, C, D]
+        ns.m2 = m
+        return m
 
     linear_fp8 = False          # pbe_amd.precision.set_linear_precision(model, "fp8") turns the LayerNorm-fed projections to e4m3 operands
     fold_layernorm = True       # False: the separate LayerNorm launches of rounds 1-2 (A/B runs, tools/)
@@ -256,9 +297,137 @@ class BasicTransformerBlock(HipModule):
     def _folded(self, p, N):
         return self.fold_layernorm and not self.linear_fp8 and p.wqkv is not None and N % 8 == 0
 
+    # The dispatch bound of pbe_ctx_attention_f16, from profiles/ctx_attention_timing.txt: at C = 320 and 640 the fused kernel takes 0.41 ..
+    # 0.95 of the faster composition for 2 .. 16 tokens; at C = 1280 (M = 2048 / 512 rows at the headline batch: 32 / 8 workgroups, each
+    # walking 20 k-tiles and 20 column tiles behind exposed load latency) it takes 1.10 .. 1.70, so those levels run the existing kernels.
+    ctx_fused_max_tokens = ops.CTX_MAX_TOKENS
+    ctx_fused_max_width = 640
+
+    def _ctx_fused(self, K):
+        """A K-token context runs in the fused kernel: within the measured dispatch bound and the kernel's shape limits."""
+        a2, Cq = self.attn2, self.attn2.to_q.weight.shape[1]
+        return K <= min(self.ctx_fused_max_tokens, ops.CTX_MAX_TOKENS) and a2.heads * K <= ops.CTX_MAX_HJ and Cq % 64 == 0 and \
+            64 <= Cq <= min(self.ctx_fused_max_width, ops.CTX_MAX_C)
+
+    def context_operands(self, context):
+        """What run() needs of a context, computed once per context.  [B, 1, Dc]: attn2's constant to_out(to_v(context)) as [B, C]
+        (single_token_context: the softmax over one key is 1).  [B, K > 1, Dc]: the operands of pbe_ctx_attention_f16 (ops.CtxOperands:
+        with k = to_k(context), v = to_v(context), per head Kq = scale log2(e) k_h (Wq gamma2)_h, kbias = scale log2(e) k_h (Wq beta2)_h,
+        Vo = Wo_h v_h, colsum = row sums of the fp16 Kq) - or, beyond that kernel's dispatch bound (K > 16, heads * K > 128, C > 640), a ContextKV
+        for the q projection / pbe_attention_f16 / to_out route.  All products are pbe_gemm_f16 launches."""
+        c = _tokens(context)
+        if c.dim() != 3:
+            raise PbeError(f"BasicTransformerBlock: context must be [B, K, Dc], got {tuple(c.shape)}")
+        B, K, _ = c.shape
+        if K == 1:
+            return self.attn2.single_token_context(c)
+        if self.linear_fp8:
+            raise PbeError("BasicTransformerBlock: a multi-token context is not available with linear_fp8 (the fp8 path folds attn2's "
+                           "constant into the out-projection epilogue; the multi-token kernels take fp16 operands only)")
+        a2, p2 = self.attn2, self.attn2.pk()
+        inner = a2.heads * a2.dim_head
+        k = ops.gemm(c.view(B * K, -1), p2.wk)                                    # [B*K, inner]
+        if not self._ctx_fused(K):
+            npad = (K + 7) // 8 * 8
+            vt = torch.zeros((B, inner, npad), dtype=torch.float16, device=c.device)
+            ops.gemm(p2.wv.unsqueeze(0).expand(B, -1, -1), c, out=vt[:, :, :K] if npad != K else vt)
+            return ContextKV(k, vt, B, K)
+        return self._fused_operands(c, k)
+
+    def _fused_operands(self, c, k=None):
+        """ops.CtxOperands of context c [B, K, Dc] fp16 (K >= 1 within the kernel's limits; k = to_k(c) when the caller has it)."""
+        a2, p2, bp = self.attn2, self.attn2.pk(), self._pack_multi()
+        H, D = a2.heads, a2.dim_head
+        B, K, _ = c.shape
+        Cq = a2.to_q.weight.shape[1]
+        c2d = c.view(B * K, -1)
+        if k is None:
+            k = ops.gemm(c2d, p2.wk)
+        v = ops.gemm(c2d, p2.wv)
+        heads = lambda t: t.view(B * K, H, D).permute(1, 0, 2)                    # [H, B*K, D] view: batch = head
+        kq_h = ops.gemm(heads(k), bp.wq2h, alpha=bp.qscale2)                      # [H, B*K, C + 8]: Kq | Kq . beta
+        vo_h = ops.gemm(heads(v), bp.wo2h)                                        # [H, B*K, C]
+        HJ = H * K
+        kq = kq_h[:, :, :Cq].reshape(H, B, K, Cq).permute(1, 0, 2, 3).reshape(B, HJ, Cq).contiguous()
+        kbias = kq_h[:, :, Cq].reshape(H, B, K).permute(1, 0, 2).reshape(B, HJ).float().contiguous()
+        colsum = ops.row_stats(kq.view(B * HJ, Cq)).buf[0, :, 0].reshape(B, HJ).contiguous()
+        vo = torch.zeros((B, Cq, (HJ + 7) // 8 * 8), dtype=torch.float16, device=c.device)
+        vo[:, :, :HJ] = vo_h.view(H, B, K, Cq).permute(1, 3, 0, 2).reshape(B, Cq, HJ)
+        return ops.CtxOperands(kq, colsum, kbias, vo, p2.bo, H, K)
+
+    def _attn2(self, x1, st2, ctx, B, N, folded, out=None, stats_out=None):
+        """x2 = x1 + attn2(norm2(x1), ctx) for a multi-token context -> (x2, RowStats of x2 or None when not folded).  st2: RowStats of
+        x1 (None: computed here).  out / stats_out: targets inside shared buffers (run_paired)."""
+        p, a2, p2 = self._pack_multi(), self.attn2, self.attn2.pk()
+        want = False if not folded else (stats_out if stats_out is not None else True)
+        if isinstance(ctx, ops.CtxOperands):
+            return ops.ctx_attention(x1, ctx, st2 if st2 is not None else ops.row_stats(x1), p.eps2, tokens=N, out=out, row_stats=want)
+        inner = a2.heads * a2.dim_head
+        if folded:
+            q = ops.gemm(x1, p.wq2, p.c2q2, ln=(st2 if st2 is not None else ops.row_stats(x1), p.c1q2, p.eps2))
+        else:
+            q = ops.gemm(ops.layernorm(x1, p.g2, p.b2, p.eps2), p2.wq)
+        npad = ctx.vt.shape[2]
+        o = ops.attention(q, ctx.k, ctx.vt, B, a2.heads, N, ctx.Nk, a2.dim_head, a2.scale, q_strides=(N * inner, inner),
+                          k_strides=(ctx.Nk * inner, inner), vt_strides=(inner * npad, npad))
+        r = ops.gemm(o.view(B * N, inner), p2.wo, p2.bo, resid=x1, out=out, row_stats=want)
+        return r if folded else (r, None)
+
+    def _ff(self, x2, st3, folded):
+        p = self.pk()
+        if folded:
+            h = ops.gemm(x2, p.wg, p.c2g, act=ops.ACT_GEGLU, ln=(st3, p.c1g, p.eps3))
+            fp = self.ff.pk()
+            return ops.gemm(h, fp.w2, fp.b2, resid=x2)
+        return self.ff.run(ops.layernorm(x2, p.g3, p.b3, p.eps3), resid=x2)
+
+    def _attn1(self, x2d, B, N, stats, folded):
+        """x1 = x + attn1(norm1(x)) with no attn2 term -> (x1, RowStats of x1 or None when not folded)."""
+        p, a1 = self.pk(), self.attn1.pk()
+        if folded:
+            a = self.attn1.self_attention_fused(x2d, stats if stats is not None else ops.row_stats(x2d), p, B, N)
+            return ops.gemm(a, a1.wo, a1.bo, resid=x2d, row_stats=True)
+        a = self.attn1.self_attention(ops.layernorm(x2d, p.g1, p.b1, p.eps1), B, N)
+        return ops.gemm(a, a1.wo, a1.bo, resid=x2d), None
+
+    def _run_multi(self, x2d, B, N, ctx, stats):
+        """run() for a multi-token context: attn1, x1 = to_out(a) + x (+ row statistics), x2 = x1 + attn2 (pbe_ctx_attention_f16, or
+        q / attention / to_out beyond its limits), GEGLU with norm3 folded on x2's statistics, ff out + x2: six launches folded."""
+        if self.linear_fp8:
+            raise PbeError("BasicTransformerBlock: a multi-token context is not available with linear_fp8 (fp16 operands only)")
+        folded = self._folded(self.pk(), N)
+        x1, st2 = self._attn1(x2d, B, N, stats, folded)
+        x2, st3 = self._attn2(x1, st2, ctx, B, N, folded)
+        return self._ff(x2, st3, folded)
+
+    def _run_paired_multi(self, x2d, B, N, ctx, stats):
+        """run_paired() for a multi-token context (ctx for 2B samples): x1 does not depend on the context, so attn1 AND its output
+        projection run once at batch B; the halves part at attn2, each writing its half of the 2B buffer and of the statistics."""
+        if self.linear_fp8:
+            raise PbeError("BasicTransformerBlock: a multi-token context is not available with linear_fp8 (fp16 operands only)")
+        folded = self._folded(self.pk(), N)
+        M = B * N
+        x2 = torch.empty((2 * M, x2d.shape[1]), dtype=torch.float16, device=x2d.device)
+        fused = isinstance(ctx, ops.CtxOperands)
+        maxp = 1 if fused else (x2d.shape[1] + 63) // 64
+        buf = torch.empty((maxp, 2 * M, 2), dtype=torch.float32, device=x2d.device) if folded else None
+        parts = 1
+        with ops.pinned_batch_scale(2):              # batch-B launches take the tile of the batch-2B layer: same bits
+            x1, st2 = self._attn1(x2d, B, N, stats, folded)
+            if st2 is None and fused:
+                st2 = ops.row_stats(x1)
+            for half in (0, 1):
+                tgt = ops.RowStats(buf, maxp, 2 * M, half * M) if folded else None
+                _, got = self._attn2(x1, st2, ctx.rows(half * B, (half + 1) * B), B, N, folded, out=x2[half * M:(half + 1) * M], stats_out=tgt)
+                parts = got.parts if got is not None else 1
+        return self._ff(x2, ops.RowStats(buf, parts, 2 * M) if folded else None, folded)
+
     def run(self, x2d, B, N, ctx_vec, stats=None):
-        """x2d [B*N, C] fp16 residual stream; ctx_vec [B, C] = attn2's constant (single_token_context); stats = ops.RowStats of x2d's
-        rows when its producer emitted them (SpatialTransformer's proj_in does), else they are computed here."""
+        """x2d [B*N, C] fp16 residual stream; ctx_vec = context_operands(context): [B, C] = attn2's constant for a one-token context
+        (single_token_context), or the multi-token operands (ops.CtxOperands / ContextKV); stats = ops.RowStats of x2d's rows when its
+        producer emitted them (SpatialTransformer's proj_in does), else they are computed here."""
+        if not isinstance(ctx_vec, torch.Tensor):
+            return self._run_multi(x2d, B, N, ctx_vec, stats)
         p = self.pk()
         a1 = self.attn1.pk()
         if self.linear_fp8:                      # BASELINE configs[4]: LayerNorm emits e4m3 + a scale per token; q|k, V^T and the GEGLU projection read it
@@ -278,7 +447,10 @@ class BasicTransformerBlock(HipModule):
     def run_paired(self, x2d, B, N, ctx_vec, stats=None):
         """Guidance pair with a SHARED input (x2d [B*N, C] serves both halves, ctx_vec [2B, C] differs): LayerNorm, q/k/v
         and the attention core do not depend on the context, so they run once at batch B; the two halves part where
-        attn2's constant is added (the out-projection epilogue).  Returns [2B*N, C]."""
+        attn2's constant is added (the out-projection epilogue).  Returns [2B*N, C].  With multi-token operands (for 2B samples) the
+        shared part also covers the out-projection: the halves part at attn2 itself (_run_paired_multi)."""
+        if not isinstance(ctx_vec, torch.Tensor):
+            return self._run_paired_multi(x2d, B, N, ctx_vec, stats)
         p = self.pk()
         x1 = torch.empty((2 * B * N, x2d.shape[1]), dtype=torch.float16, device=x2d.device)
         if self._folded(p, N):
@@ -306,11 +478,12 @@ class BasicTransformerBlock(HipModule):
         return self.ff.run(ops.layernorm(x1, p.g3, p.b3, p.eps3), resid=x1)
 
     def forward(self, x, context=None):
+        """x [B, N, C], context [B, K, Dc] with K >= 1 tokens per sample -> [B, N, C]."""
         x = _tokens(x)
         B, N, Cc = x.shape
-        if context is None or context.shape[1] != 1:
-            raise PbeError("BasicTransformerBlock: the HIP path expects a one-token context [B, 1, D]")
-        return self.run(x.view(B * N, Cc), B, N, self.attn2.single_token_context(context)).view(B, N, Cc)
+        if context is None or context.dim() != 3 or context.shape[0] != B:
+            raise PbeError("BasicTransformerBlock: the HIP path expects a context [B, K, D] with one row of K >= 1 tokens per sample")
+        return self.run(x.view(B * N, Cc), B, N, self.context_operands(context)).view(B, N, Cc)
 
 
 class SpatialTransformer(HipModule):
@@ -332,10 +505,12 @@ class SpatialTransformer(HipModule):
                                wo=ops.pack_linear(self.proj_out.weight), bo=f32(self.proj_out.bias))
 
     def context_vectors(self, context):
-        return [blk.attn2.single_token_context(context) for blk in self.transformer_blocks]
+        """Per block, what its run() needs of context [B, K, Dc]: the [B, C] constant for K = 1, the multi-token operands for K > 1
+        (BasicTransformerBlock.context_operands)."""
+        return [blk.context_operands(context) for blk in self.transformer_blocks]
 
     def run(self, x, ctx_vecs):
-        """x [B, H, W, C] fp16 NHWC -> same shape."""
+        """x [B, H, W, C] fp16 NHWC -> same shape; ctx_vecs = context_vectors(context)."""
         p = self.pk()
         B, H, W, Cc = x.shape
         N = H * W
@@ -345,7 +520,8 @@ class SpatialTransformer(HipModule):
         return ops.gemm(h, p.wo, p.bo, resid=x.view(B * N, Cc)).view(B, H, W, Cc)
 
     def run_paired(self, x, ctx_vecs):
-        """x [B, H, W, C] shared by the two halves of a guidance pair, ctx_vecs for 2B samples -> [2B, H, W, C]."""
+        """x [B, H, W, C] shared by the two halves of a guidance pair, ctx_vecs = context_vectors of the 2B contexts (one- or multi-token)
+        -> [2B, H, W, C]."""
         p = self.pk()
         B, H, W, Cc = x.shape
         N = H * W
@@ -362,7 +538,7 @@ class SpatialTransformer(HipModule):
         return y.view(2 * B, H, W, Cc)
 
     def forward(self, x, context=None):
-        """Reference layout: x [B, C, H, W] -> [B, C, H, W]."""
+        """Reference layout: x [B, C, H, W], context [B, K, Dc] (K >= 1 tokens) -> [B, C, H, W]."""
         require_gpu(x, "SpatialTransformer")
         if context is None:
             raise PbeError("SpatialTransformer: context is required on the Paint-by-Example path")

@@ -14,7 +14,8 @@ resblock up/down); the arithmetic is HIP kernels over NHWC fp16 activations:
     pair in place,
   * the 22 ``emb_layers`` Linear(SiLU(emb)) are ONE GEMM per forward,
   * the 16 cross-attention layers collapse to 16 per-sample bias vectors computed once per
-    context and cached across the 51 PLMS calls.
+    context and cached across the 51 PLMS calls; a context of several tokens per
+    sample keeps per-context operands instead and adds one launch per block (attention.py).
 """
 from types import SimpleNamespace
 
@@ -237,8 +238,9 @@ class UNetModel(HipModule):
         self.__dict__["_emb_cache"] = {}
 
     def context_vectors(self, context):
-        """The 16 per-sample cross-attention constants for this context (cached while the same
-        context tensor is presented, i.e. across the 51 calls of one PLMS run)."""
+        """What the 16 transformer blocks need of this context [N, K, context_dim] (cached while the same context tensor is presented,
+        i.e. across the 51 calls of one PLMS run): for K = 1 the per-sample cross-attention constants, for K > 1 tokens per sample the
+        operands of the multi-token cross-attention (BasicTransformerBlock.context_operands)."""
         key = (context.data_ptr(), context._version, tuple(context.shape), context.dtype)
         c = self.__dict__.get("_ctx_cache")
         if c is None or c[0] != key:
@@ -277,7 +279,7 @@ class UNetModel(HipModule):
         return row
 
     def forward_nhwc(self, x16, timesteps, context, paired=False, step=None):
-        """x16 [B,H,W,cin_pad] fp16 (channels >= in_channels zero) -> eps [B,H,W,out_channels] fp16.
+        """x16 [B,H,W,cin_pad] fp16 (channels >= in_channels zero), context [B, K, context_dim] (K >= 1) -> eps [B,H,W,out_channels] fp16.
 
         paired=True is the classifier-free-guidance call of the samplers (plms.py:182-189): the reference feeds
         cat([x]*2), cat([t]*2), cat([uc, c]) - both halves share x and t and differ ONLY in the context.  Then x16 holds the
@@ -324,7 +326,7 @@ class UNetModel(HipModule):
         return ops.conv3x3(h, p.w_out, p.b_out)
 
     def forward(self, x, timesteps=None, context=None, y=None, **kwargs):
-        """x [N, in_channels, H, W] (fp32 or fp16), timesteps [N] int, context [N, 1, context_dim] ->
+        """x [N, in_channels, H, W] (fp32 or fp16), timesteps [N] int, context [N, K, context_dim] (K >= 1 tokens per sample) ->
         eps [N, out_channels, H, W] in fp16 (what the reference returns under torch.autocast)."""
         if y is not None:
             raise PbeError("UNetModel: class labels are not supported (num_classes is None)")

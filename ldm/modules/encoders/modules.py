@@ -162,7 +162,12 @@ class FrozenCLIPImageEmbedder(AbstractEncoder):
             param.requires_grad = False
 
     def forward(self, image):
+        """image [B, 3, S, S] -> [B, 1, hidden]; several exemplars per sample, image [B, K, 3, S, S] -> [B, K, hidden] (each exemplar
+        is encoded on its own - the mapper is a one-token transformer - and becomes one context token of its sample)."""
         require_gpu(image, "FrozenCLIPImageEmbedder")
+        if image.dim() == 5:
+            B, K = image.shape[:2]
+            return self.forward(image.reshape(B * K, *image.shape[2:])).view(B, K, -1)
         z = self.transformer(pixel_values=image).pooler_output                 # [B, hidden] fp16
         z = self.mapper.run(z)
         z = ops.layernorm(z, self.final_ln.weight.float(), self.final_ln.bias.float(), self.final_ln.eps)

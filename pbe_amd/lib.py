@@ -54,6 +54,13 @@ class Mx8OutDesc(C.Structure):
     _fields_ = [("nranges", c_i32), ("channel_rows", c_i32), ("r", Mx8OutRange * 3)]
 
 
+class CtxAttnDesc(C.Structure):
+    _fields_ = [("X", c_vp), ("Y", c_vp), ("Kq", c_vp), ("colsum", c_vp), ("kbias", c_vp), ("Vo", c_vp), ("bias", c_vp), ("ln_stats", c_vp),
+                ("row_stats_out", c_vp), ("M", c_i32), ("C", c_i32), ("tokens", c_i32), ("H", c_i32), ("Nk", c_i32),
+                ("ldx", c_i64), ("ldy", c_i64), ("kq_bs", c_i64), ("kq_rs", c_i64), ("vo_bs", c_i64), ("vo_rs", c_i64), ("cs_bs", c_i64),
+                ("ln_parts", c_i32), ("ln_stats_ld", c_i64), ("ln_eps", c_f32)]
+
+
 # name -> (restype, argtypes): every symbol include/pbe_hip.h declares
 SYMBOLS = {
     "pbe_abi_version": (c_i32, []),
@@ -64,6 +71,8 @@ SYMBOLS = {
     "pbe_sizeof_attn_desc": (c_sz, []),
     "pbe_sizeof_attn_mx8_desc": (c_sz, []),
     "pbe_sizeof_mx8_out_desc": (c_sz, []),
+    "pbe_sizeof_ctx_attn_desc": (c_sz, []),
+    "pbe_ctx_attention_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp]),
     "pbe_gemm_f16": (c_i32, [C.POINTER(GemmDesc), c_vp]),
     "pbe_conv3x3_f16": (c_i32, [C.POINTER(Conv3x3Desc), c_vp]),
     "pbe_gemm_plan": (c_i32, [C.POINTER(GemmDesc), C.POINTER(c_i32), C.POINTER(c_sz)]),
@@ -108,7 +117,7 @@ SYMBOLS = {
 _lib = None
 _lock = threading.Lock()
 
-SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_astat.hip", "attention.hip", "attention_mx8.hip", "norm.hip",
+SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_astat.hip", "attention.hip", "attention_mx8.hip", "ctx_attention.hip", "norm.hip",
            "elementwise.hip"]
 HASHED = [os.path.join("csrc", f) for f in SOURCES] + [os.path.join("csrc", "common.h"), os.path.join("csrc", "igemm_kernel.h"), os.path.join("..", "include", "pbe_hip.h"), "build.py"]
 
@@ -154,7 +163,7 @@ def load() -> C.CDLL:
         if v != ABI_VERSION:
             raise PbeError(f"libpbe_hip.so ABI version {v} != expected {ABI_VERSION}")
         for cls, fn in ((GemmDesc, lib.pbe_sizeof_gemm_desc), (Conv3x3Desc, lib.pbe_sizeof_conv3x3_desc), (AttnDesc, lib.pbe_sizeof_attn_desc),
-                        (AttnMx8Desc, lib.pbe_sizeof_attn_mx8_desc), (Mx8OutDesc, lib.pbe_sizeof_mx8_out_desc)):
+                        (AttnMx8Desc, lib.pbe_sizeof_attn_mx8_desc), (Mx8OutDesc, lib.pbe_sizeof_mx8_out_desc), (CtxAttnDesc, lib.pbe_sizeof_ctx_attn_desc)):
             if C.sizeof(cls) != fn():
                 raise PbeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, libpbe_hip.so was compiled with {fn()}")
         built, want = lib.pbe_source_hash().decode(), source_hash()

@@ -584,6 +584,77 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, B: int, H: int
     return out
 
 
+CTX_MAX_TOKENS, CTX_MAX_HJ, CTX_MAX_C = 16, 128, 1280        # what pbe_ctx_attention_f16 takes (include/pbe_hip.h)
+
+
+class CtxOperands:
+    """The per-context operands of pbe_ctx_attention_f16 (include/pbe_hip.h): kq fp16 [B, HJ, C], colsum / kbias fp32 [B, HJ], vo fp16
+    [B, C, HJP] (rows padded to a multiple of 8 columns, zeros), bias fp32 [C]; HJ = H * Nk.  Computed once per context
+    (BasicTransformerBlock.context_operands); a slice of the batch (`rows`) serves one half of a guidance pair."""
+    __slots__ = ("kq", "colsum", "kbias", "vo", "bias", "B", "H", "Nk", "C")
+
+    def __init__(self, kq, colsum, kbias, vo, bias, H, Nk):
+        self.kq, self.colsum, self.kbias, self.vo, self.bias, self.H, self.Nk = kq, colsum, kbias, vo, bias, int(H), int(Nk)
+        self.B, self.C = kq.shape[0], kq.shape[2]
+
+    def rows(self, b0: int, b1: int) -> "CtxOperands":
+        return CtxOperands(self.kq[b0:b1], self.colsum[b0:b1], self.kbias[b0:b1], self.vo[b0:b1], self.bias, self.H, self.Nk)
+
+
+def ctx_attention_check(C_: int, H: int, Nk: int, tokens: int, M: int) -> None:
+    """Host validation of a pbe_ctx_attention_f16 launch (no GPU needed): raises PbeError naming the limit that was broken."""
+    if C_ % 64 or not 64 <= C_ <= CTX_MAX_C:
+        raise _l.PbeError(f"ctx_attention: C = {C_} must be a multiple of 64 in 64..{CTX_MAX_C}")
+    if not 1 <= Nk <= CTX_MAX_TOKENS:
+        raise _l.PbeError(f"ctx_attention: {Nk} context tokens, the fused kernel takes 1..{CTX_MAX_TOKENS}")
+    if H < 1 or H * Nk > CTX_MAX_HJ:
+        raise _l.PbeError(f"ctx_attention: heads * context tokens = {H * Nk}, the fused kernel takes <= {CTX_MAX_HJ}")
+    if tokens < 1 or M < 1 or M % tokens:
+        raise _l.PbeError(f"ctx_attention: {M} rows are not whole samples of {tokens} tokens")
+
+
+def ctx_attention(x: torch.Tensor, ops_ctx: CtxOperands, stats: "RowStats", eps: float, *, tokens: int, out: Optional[torch.Tensor] = None,
+                  row_stats=True):
+    """y = x + attn2(LayerNorm(x), context) for a context of 1..16 tokens in one launch (pbe_ctx_attention_f16): x [M, C] fp16 is the RAW
+    residual stream, `stats` the RowStats of its rows, ops_ctx the context's CtxOperands (sample b serves rows b * tokens ..).
+    Returns (y, RowStats of y's rows - one partial; row_stats may be a RowStats to fill, or False: (y, None))."""
+    if not isinstance(ops_ctx, CtxOperands):
+        raise _l.PbeError("ctx_attention: ops_ctx must be a CtxOperands")
+    o = ops_ctx
+    M, Cc, ldx = _rows(x, "ctx_attention x") if isinstance(x, torch.Tensor) and x.dim() == 2 else (0, 0, 0)
+    if not M:
+        raise _l.PbeError("ctx_attention: x must be a 2-D [M, C] tensor")
+    ctx_attention_check(Cc, o.H, o.Nk, int(tokens), M)
+    HJ = o.H * o.Nk
+    if M // tokens != o.B or o.C != Cc:
+        raise _l.PbeError(f"ctx_attention: operands are for {o.B} samples of width {o.C}, x holds {M // tokens} samples of width {Cc}")
+    _h(x, "ctx_attention x"); _h(o.kq, "ctx_attention kq"); _h(o.vo, "ctx_attention vo")
+    _f(o.colsum, "ctx_attention colsum"); _f(o.kbias, "ctx_attention kbias"); _f(o.bias, "ctx_attention bias")
+    if tuple(o.kq.shape[1:]) != (HJ, Cc) or o.kq.stride(2) != 1 or tuple(o.vo.shape[:2]) != (o.B, Cc) or o.vo.shape[2] < HJ or o.vo.stride(2) != 1:
+        raise _l.PbeError(f"ctx_attention: need kq [B, {HJ}, {Cc}] and vo [B, {Cc}, >= {HJ}], got {tuple(o.kq.shape)} / {tuple(o.vo.shape)}")
+    if tuple(o.colsum.shape) != (o.B, HJ) or tuple(o.kbias.shape) != (o.B, HJ) or o.colsum.stride(1) != 1 or o.kbias.stride(1) != 1 \
+            or o.colsum.stride(0) != o.kbias.stride(0) or o.bias.numel() != Cc or not o.bias.is_contiguous():
+        raise _l.PbeError(f"ctx_attention: need colsum / kbias [B, {HJ}] with equal strides and bias [{Cc}]")
+    if stats.ld - stats.row0 < M:
+        raise _l.PbeError("ctx_attention: row statistics for every row of x are required")
+    if out is None:
+        out = torch.empty((M, Cc), dtype=torch.float16, device=x.device)
+    if _rows(_h(out, "ctx_attention out"), "ctx_attention out")[:2] != (M, Cc):
+        raise _l.PbeError(f"ctx_attention: out must be [{M}, {Cc}]")
+    rs = None
+    if row_stats is not False:
+        rs = row_stats if isinstance(row_stats, RowStats) else RowStats(torch.empty((1, M, 2), dtype=torch.float32, device=x.device), 1, M)
+        if rs.ld - rs.row0 < M:
+            raise _l.PbeError("ctx_attention: row_stats buffer too short")
+        rs = RowStats(rs.buf, 1, rs.ld, rs.row0)
+    d = _l.CtxAttnDesc(_p(x), _p(out), _p(o.kq), _p(o.colsum), _p(o.kbias), _p(o.vo), _p(o.bias), stats.ptr(), None if rs is None else rs.ptr(),
+                       M, Cc, int(tokens), o.H, o.Nk, ldx, out.stride(0), o.kq.stride(0), o.kq.stride(1), o.vo.stride(0), o.vo.stride(1),
+                       o.colsum.stride(0), stats.parts, stats.ld, float(eps))
+    with _timed(f"xa:{M}:{Cc}:{o.H}:{o.Nk}"):
+        _l.check(_l.load().pbe_ctx_attention_f16(C.byref(d), _stream()), "pbe_ctx_attention_f16")
+    return out, rs
+
+
 MX8_TOKENS, MX8_VT = 0, 1          # include/pbe_hip.h PBE_MX8_*: q / k rows (contraction = channel) and V^T rows (contraction = token)
 
 

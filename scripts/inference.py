@@ -7,6 +7,8 @@ sampler -> decode -> clamp) and the same output tree, running on the MI355X HIP 
         --image_path examples/image/example_1.png --mask_path examples/mask/example_1.png \
         --reference_path examples/reference/example_1.jpg --seed 321 --scale 5
 
+`--reference_path` may name several images (not in the reference): each becomes one context token of the sample.
+
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
 `--random_weights` runs with name-seeded random weights (no checkpoint exists offline);
@@ -46,7 +48,8 @@ def parse(argv=None):
     p.add_argument("--precision", type=str, choices=["full", "autocast"], default="autocast")
     p.add_argument("--image_path", type=str, default="")
     p.add_argument("--mask_path", type=str, default="")
-    p.add_argument("--reference_path", type=str, default="")
+    p.add_argument("--reference_path", type=str, nargs="+", default=[""], help="one exemplar image as in the reference, or several: they "
+                   "become the context tokens of the sample")
     p.add_argument("--random_weights", action="store_true", help="name-seeded random weights instead of --ckpt")
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
@@ -90,10 +93,14 @@ def main(argv=None):
         start_code = torch.randn([opt.n_samples, opt.C, opt.H // opt.f, opt.W // opt.f], device=device)
 
     with torch.no_grad(), model.ema_scope():
-        t = preprocess.load_triple_device(opt.image_path, opt.mask_path, opt.reference_path, device)      # uint8 up, arithmetic on the GPU
+        refs = list(opt.reference_path) if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
+        t = preprocess.load_triple_device(opt.image_path, opt.mask_path, refs[0], device)      # uint8 up, arithmetic on the GPU
         filename = os.path.basename(opt.image_path)
         test_model_kwargs = {"inpaint_mask": t["mask"], "inpaint_image": t["inpaint"]}
         ref = t["ref"]
+        if len(refs) > 1:                                                              # several exemplars: [1, K, 3, 224, 224] -> K context tokens
+            more = [preprocess.load_triple_device(opt.image_path, opt.mask_path, r, device)["ref"] for r in refs[1:]]
+            ref = torch.stack([ref] + more, 1)
         uc = model.learnable_vector if opt.scale != 1.0 else None
         c = model.proj_out(model.get_learned_conditioning(ref))                      # scripts/inference.py:326-327
         post = model.encode_first_stage(test_model_kwargs["inpaint_image"])
