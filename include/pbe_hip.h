@@ -232,6 +232,17 @@ typedef struct pbe_attn_desc {
 } pbe_attn_desc;
 int pbe_attention_f16(const pbe_attn_desc* d, pbe_stream_t stream);
 
+/* pbe_attention_kbias_f16 — the product of pbe_attention_f16 with a per-(sample, key) logit bias: cross-attention
+ * (attention.py:207-230) over a context whose tokens carry non-negative weights w[b, key], softmax weight proportional to
+ * w[b, key] * exp(scale * q.k).  key_bias: fp32, element (b, key) at key_bias[b*kb_bs + key], = log2 w[b, key]: the LOG2 domain the
+ * kernel's exp2 works in (added after scale * log2(e), or directly to a q_prescaled product), shared by the H heads of sample b;
+ * -inf removes the key (weight 0: a padded ragged batch), +inf and NaN are not allowed, and every sample needs at least one finite
+ * entry (otherwise its rows are 0 / 0).  Nothing past key Nk - 1 is read.  Same operands, D range, strides and alignment as
+ * pbe_attention_f16 (the descriptor is unchanged); Nk <= 8192 (the sample's bias row is kept in LDS).  A bias of all zeros gives
+ * pbe_attention_f16's result within its rounding, not its bits at D = 40: this form never keeps the softmax reference in the head-dim
+ * padding, because a reference taken from a tile whose keys are all absent would be -inf. */
+int pbe_attention_kbias_f16(const pbe_attn_desc* d, const float* key_bias, int64_t kb_bs, pbe_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * MX-fp8 attention core (opt-in, pbe_amd.precision.set_attention_precision): OCP e4m3 operands with one E8M0 (power-of-two) scale
  * per 32 consecutive contraction elements, both products on v_mfma_scale_f32_32x32x64_f8f6f4.
@@ -332,6 +343,13 @@ typedef struct pbe_ctx_attn_desc {
     float ln_eps;
 } pbe_ctx_attn_desc;
 int pbe_ctx_attention_f16(const pbe_ctx_attn_desc* d, pbe_stream_t stream);
+
+/* pbe_ctx_attention_w_f16 — pbe_ctx_attention_f16 with exemplar weights (attention.py:207-230 with context token j of sample b
+ * counted w[b, j] >= 0 times): log2w fp32, element (b, j) at log2w[b*w_bs + j], = log2 w[b, j] (-inf for weight 0), is added to
+ * kbias[b, h*Nk + j] in fp32 when the kernel stages it, for every head h.  The folded operands (Kq, colsum, kbias, Vo) do not depend
+ * on the weights: they can change without re-folding.  Every sample needs one token of positive weight.  log2w of all zeros gives the
+ * bits of pbe_ctx_attention_f16. */
+int pbe_ctx_attention_w_f16(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, pbe_stream_t stream);
 
 /* pbe_softmax_rows_f16 — Y[r,:] = softmax(scale * X[r,:]) over rows of `cols` fp16 (VAE mid attention,
  * model.py:193-195: one head, d = 512, N = 4096, scores kept in HBM once per image). */

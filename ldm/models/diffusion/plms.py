@@ -47,7 +47,8 @@ def guidance_context(cond, uc, b, device):
     """The [uc | c] context of a guidance pair (plms.py:185-187) as fp16 [2b, K, D].  cond [b, K, D] may hold K >= 1 tokens per sample
     (several exemplars); a ONE-token uc is repeated to K tokens.  That is exact, not an approximation: K copies of one key give K equal
     scores, the softmax weights are 1/K each, and the weighted sum of K equal values is that value - attn2 of the repeated context is
-    attn2 of the single token.  Any other difference in length is refused (per-sample exemplar counts would need a mask)."""
+    attn2 of the single token.  Any other difference in length is refused: samples with different exemplar counts are padded to one K
+    and given per-sample weights (guidance_weights; pbe_amd.pipeline.pad_conditionings builds both)."""
     uc = uc.to(device)
     cond = cond.to(device)
     if uc.shape[0] != b:                           # scripts/inference.py:325 hands [1,1,768]; the test bench repeats it
@@ -57,9 +58,23 @@ def guidance_context(cond, uc, b, device):
     if uc.shape[1] != cond.shape[1]:
         if uc.shape[1] != 1:
             raise PbeError(f"sampler: unconditional_conditioning has {uc.shape[1]} tokens, conditioning {cond.shape[1]}: "
-                           "only a one-token unconditional context can be repeated (per-sample context lengths are not supported)")
+                           "only a one-token unconditional context can be repeated (per-sample exemplar counts go through "
+                           "conditioning_weights, with weight 0 on the padding tokens)")
         uc = uc.expand(-1, cond.shape[1], -1)
     return torch.cat((uc.to(torch.float16), cond.to(torch.float16))).contiguous()
+
+
+def guidance_weights(weights, cond, b, guided):
+    """Exemplar weights of the context guidance_context builds: conditioning_weights [b, K] (>= 0, positive sum per sample, 0 = token
+    absent) -> fp64 host tensor [2b, K] for a guidance pair (the unconditional half gets ones: on K copies of one token any weights
+    with a positive sum give that token, for the reason above) or [b, K] unguided; None for None.  One tensor per run, so the U-Net's
+    per-context cache sees one identity across the steps; validated where the operands are built (attention.prepare_context_weights)."""
+    if weights is None:
+        return None
+    w = torch.as_tensor(weights).detach().to("cpu", torch.float64)
+    if tuple(w.shape) != (b, cond.shape[1]):
+        raise PbeError(f"sampler: conditioning_weights must be [{b}, {cond.shape[1]}] (one per conditioning token), got {tuple(w.shape)}")
+    return torch.cat((torch.ones_like(w), w)).contiguous() if guided else w.contiguous()
 
 
 class PLMSSampler(object):
@@ -95,7 +110,9 @@ class PLMSSampler(object):
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
                eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
-               x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, **kwargs):
+               x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, conditioning_weights=None, **kwargs):
+        """conditioning_weights: per-sample exemplar weights [batch_size, K] over conditioning's K tokens (>= 0, positive sum per sample;
+        0 = token absent, so a ragged batch is padded to one K), or None: every token counts once."""
         if conditioning is None:
             raise PbeError("PLMSSampler.sample: conditioning is required")
         if conditioning.shape[0] != batch_size:
@@ -108,10 +125,11 @@ class PLMSSampler(object):
         C, H, W = shape
         return self.plms_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0, **kwargs)
+                                  unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
+                                  conditioning_weights=conditioning_weights, **kwargs)
 
     # ---- one U-Net evaluation with guidance (plms.py:181-195) -----------------------------------
-    def _eps(self, x, step, ctx, z_inp, msk, dup):
+    def _eps(self, x, step, ctx, z_inp, msk, dup, ctx_w=None):
         b = x.shape[0]
         t = torch.full((dup * b,), int(step), device=x.device, dtype=torch.int64)
         unet = self.model.model.diffusion_model
@@ -121,7 +139,9 @@ class PLMSSampler(object):
         if (graphs_enabled(dup * b) if self.use_graph is None else self.use_graph) and x.is_cuda:      # launch-bound regime: one HIP graph per call
             if self._graphed is None or self._graphed.unet is not unet:
                 self._graphed = GraphedUNet(unet)
-            return self._graphed(x9, t, ctx, paired)
+            return self._graphed(x9, t, ctx, paired) if ctx_w is None else self._graphed(x9, t, ctx, paired, ctx_w)
+        if ctx_w is not None:                                                     # (without weights: exactly the call made before they existed)
+            return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step), context_weights=ctx_w)
         return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step))      # every row of t is `step`: the embedding rows come from the per-value cache
 
     def _coef(self, index, weights):
@@ -144,7 +164,7 @@ class PLMSSampler(object):
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, callback=None, timesteps=None, img_callback=None, log_every_t=100,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, mask=None, x0=None, **kwargs):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, mask=None, x0=None, conditioning_weights=None, **kwargs):
         device = self.model.betas.device
         if self.require_gpu and device.type != "cuda":
             raise PbeError("PLMSSampler: the model must live on an MI355X (model.to('cuda')); there is no CPU path")
@@ -160,6 +180,7 @@ class PLMSSampler(object):
         else:
             ctx = cond.to(torch.float16).contiguous()
         dup = 2 if guided else 1
+        ctx_w = guidance_weights(conditioning_weights, cond, b, guided)
         scale = float(unconditional_guidance_scale)
 
         time_range = np.flip(self._schedule_subset(timesteps))
@@ -173,11 +194,11 @@ class PLMSSampler(object):
             step_next = time_range[min(i + 1, total - 1)]
             if mask is not None:
                 img = self._blend_known(img, x0, mask, step)
-            eps = self._eps(img, step, ctx, z_inp, msk, dup)
+            eps = self._eps(img, step, ctx, z_inp, msk, dup, ctx_w)
             if len(old) == 0:
                 # pseudo improved Euler (plms.py:230-235): probe x_prev with e_t, re-evaluate at t_next, average
                 x_probe, _, e_t = ops.plms_update(eps, dup, scale, img, [], self._coef(index, _AB[0]), want_pred=False)
-                eps2 = self._eps(x_probe, step_next, ctx, z_inp, msk, dup)
+                eps2 = self._eps(x_probe, step_next, ctx, z_inp, msk, dup, ctx_w)
                 # e' = (e_t + e_next)/2 : c0 weights the fresh eps (= e_next), history slot 1 = e_t
                 img, pred_x0, _ = ops.plms_update(eps2, dup, scale, img, [e_t], self._coef(index, (0.5, 0.5)), want_e_t=False)
             else:

@@ -229,14 +229,46 @@ class CrossAttention(HipModule):
 
 class ContextKV:
     """What the existing-kernel route of a multi-token attn2 keeps per context: k = to_k(context) [B*Nk, inner] and
-    vt = to_v(context)^T [B, inner, npad] (npad = Nk rounded up to 8, zeros past Nk)."""
-    __slots__ = ("k", "vt", "B", "Nk")
+    vt = to_v(context)^T [B, inner, npad] (npad = Nk rounded up to 8, zeros past Nk); log2w [B, Nk] fp32 = log2 of the exemplar
+    weights (the key bias of pbe_attention_kbias_f16) or None."""
+    __slots__ = ("k", "vt", "B", "Nk", "log2w")
 
-    def __init__(self, k, vt, B, Nk):
-        self.k, self.vt, self.B, self.Nk = k, vt, B, Nk
+    def __init__(self, k, vt, B, Nk, log2w=None):
+        self.k, self.vt, self.B, self.Nk, self.log2w = k, vt, B, Nk, log2w
 
     def rows(self, b0, b1):
-        return ContextKV(self.k[b0 * self.Nk:b1 * self.Nk], self.vt[b0:b1], b1 - b0, self.Nk)
+        return ContextKV(self.k[b0 * self.Nk:b1 * self.Nk], self.vt[b0:b1], b1 - b0, self.Nk, None if self.log2w is None else self.log2w[b0:b1])
+
+
+class ContextWeights:
+    """Validated exemplar weights of one context, as the kernels take them: log2w fp32 [B, K] on the context's device, log2 of the
+    weight of token j of sample b, -inf for weight 0.  Built ONCE per context by prepare_context_weights() (set-up, like the schedule tables)."""
+    __slots__ = ("log2w",)
+
+    def __init__(self, log2w):
+        self.log2w = log2w
+
+
+def prepare_context_weights(context, weights):
+    """Exemplar weights [B, K] (tensor or nested sequence, any device) for context [B, K, Dc] -> ContextWeights, or None for None.
+    Token j of sample b takes the softmax weight w[b, j] exp(s_j) / sum_i w[b, i] exp(s_i) (attention.py:207-230 with the token counted
+    w times): weight 0 removes it (a padded ragged batch), integer weights equal repeating it, uniform weights change nothing.  Raises
+    PbeError unless the weights are [B, K], finite, >= 0 and every sample's sum is > 0.  log2 is taken in fp64 on the host."""
+    if weights is None or isinstance(weights, ContextWeights):
+        return weights
+    if context.dim() != 3:
+        raise PbeError(f"context weights: context must be [B, K, Dc], got {tuple(context.shape)}")
+    B, K = context.shape[0], context.shape[1]
+    w = torch.as_tensor(weights).detach().to("cpu", torch.float64)
+    if tuple(w.shape) != (B, K):
+        raise PbeError(f"context weights: weights must be [{B}, {K}] (one per context token), got {tuple(w.shape)}")
+    if not bool(torch.isfinite(w).all()):
+        raise PbeError("context weights: weights must be finite")
+    if bool((w < 0).any()):
+        raise PbeError("context weights: weights must be >= 0")
+    if not bool((w.sum(1) > 0).all()):
+        raise PbeError("context weights: every sample needs a positive weight sum (at least one exemplar token present)")
+    return ContextWeights(torch.log2(w).to(torch.float32).to(context.device).contiguous())
 
 
 class BasicTransformerBlock(HipModule):
@@ -309,8 +341,10 @@ class BasicTransformerBlock(HipModule):
         return K <= min(self.ctx_fused_max_tokens, ops.CTX_MAX_TOKENS) and a2.heads * K <= ops.CTX_MAX_HJ and Cq % 64 == 0 and \
             64 <= Cq <= min(self.ctx_fused_max_width, ops.CTX_MAX_C)
 
-    def context_operands(self, context):
-        """What run() needs of a context, computed once per context.  [B, 1, Dc]: attn2's constant to_out(to_v(context)) as [B, C]
+    def context_operands(self, context, weights=None):
+        """What run() needs of a context, computed once per context.  weights: exemplar weights [B, K] or a ContextWeights
+        (prepare_context_weights: validated there), None = every token counts once; their log2 rides beside the operands (CtxOperands.log2w /
+        ContextKV.log2w), which do not depend on it.  [B, 1, Dc]: attn2's constant to_out(to_v(context)) as [B, C]
         (single_token_context: the softmax over one key is 1).  [B, K > 1, Dc]: the operands of pbe_ctx_attention_f16 (ops.CtxOperands:
         with k = to_k(context), v = to_v(context), per head Kq = scale log2(e) k_h (Wq gamma2)_h, kbias = scale log2(e) k_h (Wq beta2)_h,
         Vo = Wo_h v_h, colsum = row sums of the fp16 Kq) - or, beyond that kernel's dispatch bound (K > 16, heads * K > 128, C > 640), a ContextKV
@@ -319,7 +353,8 @@ class BasicTransformerBlock(HipModule):
         if c.dim() != 3:
             raise PbeError(f"BasicTransformerBlock: context must be [B, K, Dc], got {tuple(c.shape)}")
         B, K, _ = c.shape
-        if K == 1:
+        cw = prepare_context_weights(c, weights)
+        if K == 1:                                # (any positive weight on a single token is exact: the softmax over one key is 1)
             return self.attn2.single_token_context(c)
         if self.linear_fp8:
             raise PbeError("BasicTransformerBlock: a multi-token context is not available with linear_fp8 (the fp8 path folds attn2's "
@@ -331,8 +366,10 @@ class BasicTransformerBlock(HipModule):
             npad = (K + 7) // 8 * 8
             vt = torch.zeros((B, inner, npad), dtype=torch.float16, device=c.device)
             ops.gemm(p2.wv.unsqueeze(0).expand(B, -1, -1), c, out=vt[:, :, :K] if npad != K else vt)
-            return ContextKV(k, vt, B, K)
-        return self._fused_operands(c, k)
+            return ContextKV(k, vt, B, K, None if cw is None else cw.log2w)
+        o = self._fused_operands(c, k)
+        o.log2w = None if cw is None else cw.log2w
+        return o
 
     def _fused_operands(self, c, k=None):
         """ops.CtxOperands of context c [B, K, Dc] fp16 (K >= 1 within the kernel's limits; k = to_k(c) when the caller has it)."""
@@ -369,7 +406,7 @@ class BasicTransformerBlock(HipModule):
             q = ops.gemm(ops.layernorm(x1, p.g2, p.b2, p.eps2), p2.wq)
         npad = ctx.vt.shape[2]
         o = ops.attention(q, ctx.k, ctx.vt, B, a2.heads, N, ctx.Nk, a2.dim_head, a2.scale, q_strides=(N * inner, inner),
-                          k_strides=(ctx.Nk * inner, inner), vt_strides=(inner * npad, npad))
+                          k_strides=(ctx.Nk * inner, inner), vt_strides=(inner * npad, npad), key_bias=ctx.log2w)
         r = ops.gemm(o.view(B * N, inner), p2.wo, p2.bo, resid=x1, out=out, row_stats=want)
         return r if folded else (r, None)
 
@@ -477,13 +514,13 @@ class BasicTransformerBlock(HipModule):
             return self.ff.run_f8(*ops.layernorm_f8(x1, p.g3, p.b3, p.eps3), resid=x1)
         return self.ff.run(ops.layernorm(x1, p.g3, p.b3, p.eps3), resid=x1)
 
-    def forward(self, x, context=None):
-        """x [B, N, C], context [B, K, Dc] with K >= 1 tokens per sample -> [B, N, C]."""
+    def forward(self, x, context=None, context_weights=None):
+        """x [B, N, C], context [B, K, Dc] with K >= 1 tokens per sample (context_weights [B, K] or None) -> [B, N, C]."""
         x = _tokens(x)
         B, N, Cc = x.shape
         if context is None or context.dim() != 3 or context.shape[0] != B:
             raise PbeError("BasicTransformerBlock: the HIP path expects a context [B, K, D] with one row of K >= 1 tokens per sample")
-        return self.run(x.view(B * N, Cc), B, N, self.context_operands(context)).view(B, N, Cc)
+        return self.run(x.view(B * N, Cc), B, N, self.context_operands(context, context_weights)).view(B, N, Cc)
 
 
 class SpatialTransformer(HipModule):
@@ -504,10 +541,11 @@ class SpatialTransformer(HipModule):
                                wi=ops.pack_linear(self.proj_in.weight), bi=f32(self.proj_in.bias),
                                wo=ops.pack_linear(self.proj_out.weight), bo=f32(self.proj_out.bias))
 
-    def context_vectors(self, context):
+    def context_vectors(self, context, context_weights=None):
         """Per block, what its run() needs of context [B, K, Dc]: the [B, C] constant for K = 1, the multi-token operands for K > 1
-        (BasicTransformerBlock.context_operands)."""
-        return [blk.context_operands(context) for blk in self.transformer_blocks]
+        (BasicTransformerBlock.context_operands).  context_weights: exemplar weights [B, K] (or a ContextWeights), validated once here."""
+        cw = prepare_context_weights(context, context_weights)
+        return [blk.context_operands(context, cw) for blk in self.transformer_blocks]
 
     def run(self, x, ctx_vecs):
         """x [B, H, W, C] fp16 NHWC -> same shape; ctx_vecs = context_vectors(context)."""
@@ -537,10 +575,10 @@ class SpatialTransformer(HipModule):
                 ops.gemm(h[half * B * N:(half + 1) * B * N], p.wo, p.bo, resid=x2d, out=y[half * B * N:(half + 1) * B * N])
         return y.view(2 * B, H, W, Cc)
 
-    def forward(self, x, context=None):
-        """Reference layout: x [B, C, H, W], context [B, K, Dc] (K >= 1 tokens) -> [B, C, H, W]."""
+    def forward(self, x, context=None, context_weights=None):
+        """Reference layout: x [B, C, H, W], context [B, K, Dc] (K >= 1 tokens), context_weights [B, K] or None -> [B, C, H, W]."""
         require_gpu(x, "SpatialTransformer")
         if context is None:
             raise PbeError("SpatialTransformer: context is required on the Paint-by-Example path")
-        y = self.run(ops.nchw_to_nhwc(x.float()), self.context_vectors(context))
+        y = self.run(ops.nchw_to_nhwc(x.float()), self.context_vectors(context, context_weights))
         return ops.nhwc_to_nchw(y).to(x.dtype)

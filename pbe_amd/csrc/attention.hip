@@ -28,6 +28,8 @@ struct AttnP {
     float scale_log2e;
     int q_pre;          // Q already multiplied by scale log2e (then scale_log2e == 1)
     int nqb;            // query blocks per (batch, head): the grid is 1-D, nqb * B * H workgroups
+    const float* kbias; // KB form only: per-(sample, key) logit bias, log2 domain, element (b, key) at kbias[b * kb_bs + key]
+    long kb_bs;
 #ifdef PBE_ATTN_STAMPS
     unsigned long long* stamps;     // diagnostic build only (tools/attn_stamps.py): 4 words per workgroup, written by lane 0 of wave 0, read by nothing
 #endif
@@ -64,8 +66,14 @@ __device__ __forceinline__ int attn_key_of_row(int r) { return (r & ~12) | ((r &
 #define PBE_ATTN_PRIO 0      // 1: s_setprio 1 around the MFMA phases (A/B build, tools/attn_ab.py with PBE_LIB_PATH)
 #endif
 
-template <int DP, int QW, int KH, bool MPAD = false>
+template <int DP, int QW, int KH, bool MPAD = false, bool KB = false>
 __global__ void __launch_bounds__(256, (QW == 2 && DP <= 48) ? 2 : 1) attn_kernel(const AttnP p) {
+    // KB (pbe_attention_kbias_f16): kbias[b, key] is added to every score of key `key` (log2 domain, after scale log2e) before the
+    // maximum, the exp2 and the denominator; -inf removes the key.  The whole bias row of the sample sits in LDS behind the tile images
+    // (nt * 64 floats, -inf past Nk: the ragged tail needs no mask of its own), written once at workgroup entry; a lane reads its 32
+    // values per unit as 8 ds_read_b128 issued under the QK^T MFMAs.  Never combined with MPAD: there the reference is taken from the
+    // first tile's maximum, which is -inf when the bias removes the whole tile.
+    static_assert(!(MPAD && KB), "the key-bias form does not keep the reference in the head-dim padding");
     // MPAD (D == DP - 8: the U-Net's d = 40 heads): the reference maximum rides in the padding of the head dimension.  Column D
     // of every K row is the constant 64, column D of the (pre-scaled) Q row holds -m / 64 as fp16, so the QK^T MFMA itself returns
     // s = scale log2e q.k - m and the softmax is max -> exp2 -> cvt with no multiply-add per score (32 of ~130 VALU issues per
@@ -116,6 +124,13 @@ __global__ void __launch_bounds__(256, (QW == 2 && DP <= 48) ? 2 : 1) attn_kerne
     __syncthreads();
     if (ONES && tid < 8 * NSLOT)
         *reinterpret_cast<h16x8*>(smem + (tid >> 3) * BUF + K_BYTES + (DV - 1) * VSTR + (tid & 7) * 16) = one8;
+    const int nt = (p.Nk + KT - 1) / KT;
+    const int rem = p.Nk - (nt - 1) * KT;                 // keys in the last tile (1..64)
+    const float* kbt = reinterpret_cast<const float*>(smem + NSLOT * BUF);    // KB: the sample's bias row
+    if constexpr (KB) {                                   // the row belongs to the SAMPLE b (not to bh); nothing is read past key Nk - 1
+        float* w = reinterpret_cast<float*>(smem + NSLOT * BUF);
+        for (int i = tid; i < nt * KT; i += 256) w[i] = i < p.Nk ? p.kbias[(long)b * p.kb_bs + i] : -INFINITY;
+    }
     if constexpr (MPAD) {                                 // K[:, D] = 64 in every tile image (chunk DC - 1 of a row is never a DMA target)
         const h16x8 kpad = {(h16)64.f, 0, 0, 0, 0, 0, 0, 0};
         for (int i = tid; i < NSLOT * KT; i += 256)
@@ -137,8 +152,6 @@ __global__ void __launch_bounds__(256, (QW == 2 && DP <= 48) ? 2 : 1) attn_kerne
             if (c < KT / 8 && row < D) { src[j] = Vb + (long)row * p.vt_rs + c * 8; inc[j] = KT; }
         }
     }
-    const int nt = (p.Nk + KT - 1) / KT;
-    const int rem = p.Nk - (nt - 1) * KT;                 // keys in the last tile (1..64)
     auto issue_tile = [&](int t, int buf) {
         unsigned char* dst = smem + buf * BUF + wave * 1024;
         if (t + 1 < nt || rem == KT) {                    // full tile: constant-stride pointers
@@ -282,7 +295,21 @@ __global__ void __launch_bounds__(256, (QW == 2 && DP <= 48) ? 2 : 1) attn_kerne
     auto softmax = [&](int i, int kv0, bool first) {
         f32x16& s0 = sc[0];
         f32x16& s1 = sc[1];
-        if (kv0 + KT > p.Nk) {                          // ragged last tile only (wave-uniform branch)
+        if constexpr (KB) {
+            // s <- scale log2e s + kbias[key], then max / exp2 on the biased scores.  register r of half-wave h: key 16 (r >> 3) + 8 h + (r & 7)
+            const f32x4* bt = reinterpret_cast<const f32x4*>(kbt + kv0 + 8 * h5);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x4 b0 = bt[4 * j], b1 = bt[4 * j + 1];          // keys 16 j + 8 h + 0..3, + 4..7
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    f32x16& s = j < 2 ? s0 : s1;
+                    const int r = 8 * (j & 1) + e;
+                    s[r] = __builtin_fmaf(s[r], p.scale_log2e, b0[e]);
+                    s[r + 4] = __builtin_fmaf(s[r + 4], p.scale_log2e, b1[e]);
+                }
+            }
+        } else if (kv0 + KT > p.Nk) {                   // ragged last tile only (wave-uniform branch)
             int left = p.Nk - kv0 - 8 * h5;             // keys left from this half-wave's first key
             asm volatile("" : "+v"(left));              // pins the 32 compares inside the branch (else they are hoisted into every tile)
 #pragma unroll
@@ -322,6 +349,26 @@ __global__ void __launch_bounds__(256, (QW == 2 && DP <= 48) ? 2 : 1) attn_kerne
             for (int r = 0; r < 16; ++r) {
                 s0[r] = __builtin_amdgcn_exp2f(s0[r]);
                 s1[r] = __builtin_amdgcn_exp2f(s1[r]);
+            }
+        } else if constexpr (KB) {
+            // mx = -inf (every key of the tile absent for this query's sample): -inf - m_run is -inf or NaN, neither raises.  While no
+            // live key has been seen m_run is still -inf and the reference used is 0: P = exp2(-inf - 0) = 0, never exp2(-inf + inf).
+            // The first live tile then raises from -inf (mx - -inf = +inf > ATTN_THR) with alpha = exp2(-inf) = 0 on O = l = 0.
+            if (__builtin_amdgcn_ballot_w64(mx - m_run[i] > ATTN_THR) != 0) {
+                const float m_new = fmaxf(m_run[i], mx);
+                const float alpha = __builtin_amdgcn_exp2f(m_run[i] - m_new);
+                m_run[i] = m_new;
+                l_run[i] *= alpha;
+#pragma unroll
+                for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[i][dt][r] *= alpha;
+            }
+            const float mref = m_run[i] == -INFINITY ? 0.f : m_run[i];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                s0[r] = __builtin_amdgcn_exp2f(s0[r] - mref);
+                s1[r] = __builtin_amdgcn_exp2f(s1[r] - mref);
             }
         } else {
             const float ms = mx * p.scale_log2e;
@@ -460,26 +507,29 @@ extern "C" int pbe_debug_set_attn_stamps(void* buf) { g_pbe_attn_stamps = (unsig
 #endif
 int g_pbe_attn_pad_lds = 0;  // pbe_tune(8, bytes): extra dynamic LDS per workgroup (fewer resident workgroups per CU: occupancy experiments only)
 
-template <int DP, int QW, int KH = 1, bool MPAD = false>
+#define ATTN_KB_MAX_NK 8192  // key-bias form: the sample's bias row lives in LDS (32 KB at most, beside <= 88 KB of tile images)
+
+template <int DP, int QW, int KH = 1, bool MPAD = false, bool KB = false>
 static void launch_attn(const AttnP& p, hipStream_t s) {
     constexpr size_t lds0 = 2 * KH * AttnTile<DP>::BUF;
-    static_assert(lds0 <= 160 * 1024, "attention tile exceeds the LDS");
-    const size_t lds = lds0 + (g_pbe_attn_pad_lds > 0 && lds0 + g_pbe_attn_pad_lds <= 160 * 1024 ? g_pbe_attn_pad_lds : 0);      // (occupancy experiments)
+    static_assert(lds0 + (KB ? ATTN_KB_MAX_NK * 4 : 0) <= 160 * 1024, "attention tile exceeds the LDS");
+    const size_t lds = KB ? lds0 + (size_t)cdiv(p.Nk, 64) * 256                                                                    // + the bias row
+                          : lds0 + (g_pbe_attn_pad_lds > 0 && lds0 + g_pbe_attn_pad_lds <= 160 * 1024 ? g_pbe_attn_pad_lds : 0);  // (occupancy experiments)
     static std::atomic<uint64_t> attr_done{0};
-    pbe_raise_dynamic_lds(attr_done, reinterpret_cast<const void*>(&attn_kernel<DP, QW, KH, MPAD>), 160 * 1024);
+    pbe_raise_dynamic_lds(attr_done, reinterpret_cast<const void*>(&attn_kernel<DP, QW, KH, MPAD, KB>), 160 * 1024);
     AttnP q = p;
     q.nqb = cdiv(p.Nq, 128 * QW);
 #ifdef PBE_ATTN_STAMPS
     q.stamps = g_pbe_attn_stamps;
 #endif
     dim3 grid((unsigned)(q.nqb * p.B * p.H));
-    hipLaunchKernelGGL((attn_kernel<DP, QW, KH, MPAD>), grid, dim3(256), lds, s, q);
+    hipLaunchKernelGGL((attn_kernel<DP, QW, KH, MPAD, KB>), grid, dim3(256), lds, s, q);
 }
 
 int g_pbe_attn_qw = 0;       // pbe_tune(3, v): 0 = heuristic, 1 / 2 = force queries-per-wave factor
 int g_pbe_attn_mpad = 1;     // pbe_tune(6, 0/1): reference maximum in the head-dim padding (d = 40)
 
-extern "C" int pbe_attention_f16(const pbe_attn_desc* d, pbe_stream_t stream) {
+static int attn_fill(const pbe_attn_desc* d, AttnP& p) {
     PBE_REQUIRE(d && d->Q && d->K && d->VT && d->O, "pbe_attention_f16: null operand");
     PBE_REQUIRE(d->B > 0 && d->H > 0 && d->Nq > 0 && d->Nk > 0, "pbe_attention_f16: bad dims");
     PBE_REQUIRE(d->D % 8 == 0 && d->D >= 8 && d->D <= 160, "pbe_attention_f16: head dim %d unsupported (multiple of 8, <= 160)", d->D);
@@ -490,13 +540,19 @@ extern "C" int pbe_attention_f16(const pbe_attn_desc* d, pbe_stream_t stream) {
     PBE_REQUIRE(((uintptr_t)d->Q & 15) == 0 && ((uintptr_t)d->K & 15) == 0 && ((uintptr_t)d->VT & 15) == 0 && ((uintptr_t)d->O & 15) == 0,
                 "pbe_attention_f16: 16-byte alignment");
     PBE_REQUIRE((long)d->B * d->H * ((d->Nq + 127) / 128) < (1L << 31), "pbe_attention_f16: too many workgroups");
-    AttnP p;
     p.Q = (const h16*)d->Q; p.K = (const h16*)d->K; p.VT = (const h16*)d->VT; p.O = (h16*)d->O;
     p.B = d->B; p.H = d->H; p.Nq = d->Nq; p.Nk = d->Nk; p.D = d->D;
     p.q_bs = d->q_bs; p.q_rs = d->q_rs; p.k_bs = d->k_bs; p.k_rs = d->k_rs;
     p.vt_bs = d->vt_bs; p.vt_rs = d->vt_rs; p.o_bs = d->o_bs; p.o_rs = d->o_rs;
     p.q_pre = d->q_prescaled ? 1 : 0;
     p.scale_log2e = p.q_pre ? 1.0f : d->scale * 1.4426950408889634f;
+    p.kbias = nullptr; p.kb_bs = 0;
+    return PBE_OK;
+}
+
+extern "C" int pbe_attention_f16(const pbe_attn_desc* d, pbe_stream_t stream) {
+    AttnP p;
+    if (const int rc = attn_fill(d, p)) return rc;
     hipStream_t s = (hipStream_t)stream;
     pbe_prof_begin(PBE_K_ATTN, s);
     const int D = d->D;
@@ -520,5 +576,33 @@ extern "C" int pbe_attention_f16(const pbe_attn_desc* d, pbe_stream_t stream) {
     pbe_prof_end(PBE_K_ATTN, s, 4.0 * d->B * d->H * (double)d->Nq * d->Nk * d->D,
                  2.0 * d->B * d->H * (double)d->D * (2.0 * d->Nq + 2.0 * d->Nk));                 // q, o, k, v^T once each
     PBE_LAUNCH_CHECK("pbe_attention_f16");
+    return PBE_OK;
+}
+
+// The same product with key_bias[b, key] (fp32, log2 domain, shared by the heads of sample b; -inf = key absent) added to every score
+// before the softmax: cross-attention over a weighted / ragged multi-token context.  Only the forms this dispatch reaches are
+// instantiated; the d = 40 heads take the multiply-add form (see attn_kernel).
+extern "C" int pbe_attention_kbias_f16(const pbe_attn_desc* d, const float* key_bias, int64_t kb_bs, pbe_stream_t stream) {
+    AttnP p;
+    if (const int rc = attn_fill(d, p)) return rc;
+    PBE_REQUIRE(key_bias && ((uintptr_t)key_bias & 3) == 0, "pbe_attention_kbias_f16: key_bias must be a 4-byte aligned pointer");
+    PBE_REQUIRE(kb_bs >= 0, "pbe_attention_kbias_f16: negative key_bias batch stride");
+    PBE_REQUIRE(d->Nk <= ATTN_KB_MAX_NK, "pbe_attention_kbias_f16: Nk = %d unsupported (<= %d: the bias row is kept in LDS)", d->Nk, ATTN_KB_MAX_NK);
+    p.kbias = key_bias; p.kb_bs = kb_bs;
+    hipStream_t s = (hipStream_t)stream;
+    pbe_prof_begin(PBE_K_ATTN, s);
+    const int D = d->D;
+    const long blocks2 = (long)cdiv(d->Nq, 256) * d->B * d->H;
+    const bool two = g_pbe_attn_qw ? g_pbe_attn_qw == 2 : (blocks2 >= 512 && D <= 80);
+    if (D <= 16) launch_attn<16, 1, 1, false, true>(p, s);
+    else if (D <= 32) launch_attn<32, 1, 1, false, true>(p, s);
+    else if (D <= 48) { if (two) launch_attn<48, 2, 2, false, true>(p, s); else launch_attn<48, 1, 1, false, true>(p, s); }
+    else if (D <= 64) { if (two) launch_attn<64, 2, 1, false, true>(p, s); else launch_attn<64, 1, 1, false, true>(p, s); }
+    else if (D <= 80) { if (two) launch_attn<80, 2, 1, false, true>(p, s); else launch_attn<80, 1, 1, false, true>(p, s); }
+    else if (D <= 128) launch_attn<128, 1, 1, false, true>(p, s);
+    else launch_attn<160, 1, 1, false, true>(p, s);
+    pbe_prof_end(PBE_K_ATTN, s, 4.0 * d->B * d->H * (double)d->Nq * d->Nk * d->D,
+                 2.0 * d->B * d->H * (double)d->D * (2.0 * d->Nq + 2.0 * d->Nk));
+    PBE_LAUNCH_CHECK("pbe_attention_kbias_f16");
     return PBE_OK;
 }

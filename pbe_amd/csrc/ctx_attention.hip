@@ -27,6 +27,7 @@ struct CtxP {
     int C, tokens, H, Nk, HJ, NJ, tps;      // NJ = 32-column blocks of S; tps = row tiles per sample
     long ldx, ldy, kq_bs, kq_rs, vo_bs, vo_rs, cs_bs, ln_ld;
     int ln_parts; float ln_eps; double inv_c;
+    const float* log2w; long w_bs;          // pbe_ctx_attention_w_f16: per-(sample, token) log2 weight added to kbias, or null
 };
 
 #define CTX_TM 64          // rows per workgroup
@@ -68,7 +69,11 @@ __global__ void __launch_bounds__(256) ctx_attn_kernel(const CtxP p) {
     } else if (tid < CTX_TM + 128) {
         const int c = tid - CTX_TM;
         s_cs[c] = c < HJ ? p.colsum[(long)b * p.cs_bs + c] : 0.f;
-        s_kb[c] = c < HJ ? p.kbias[(long)b * p.cs_bs + c] : 0.f;
+        float kb = c < HJ ? p.kbias[(long)b * p.cs_bs + c] : 0.f;
+        // exemplar weights: softmax weight ~ w exp(s), i.e. + log2 w in this log2 domain (-inf: token absent), added in fp32 AFTER kbias's
+        // own fp16 rounding; column c = (head, token c % Nk).  Done once per workgroup, outside the per-score path.
+        if (p.log2w && c < HJ) kb += p.log2w[(long)b * p.w_bs + c % p.Nk];
+        s_kb[c] = kb;
     }
 
     // ---- phase 1: S = X Kq^T ----
@@ -233,7 +238,7 @@ __global__ void __launch_bounds__(256) ctx_attn_kernel(const CtxP p) {
 
 extern "C" size_t pbe_sizeof_ctx_attn_desc(void) { return sizeof(pbe_ctx_attn_desc); }
 
-extern "C" int pbe_ctx_attention_f16(const pbe_ctx_attn_desc* d, pbe_stream_t stream) {
+static int ctx_attention_launch(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, pbe_stream_t stream) {
     PBE_REQUIRE(d && d->X && d->Y && d->Kq && d->colsum && d->kbias && d->Vo && d->bias && d->ln_stats, "pbe_ctx_attention_f16: null operand");
     PBE_REQUIRE(d->C % 64 == 0 && d->C >= 64 && d->C <= 1280, "pbe_ctx_attention_f16: C = %d unsupported (multiple of 64, 64..1280)", d->C);
     PBE_REQUIRE(d->Nk >= 1 && d->Nk <= 16, "pbe_ctx_attention_f16: Nk = %d unsupported (1..16 context tokens)", d->Nk);
@@ -256,6 +261,7 @@ extern "C" int pbe_ctx_attention_f16(const pbe_ctx_attn_desc* d, pbe_stream_t st
     p.C = d->C; p.tokens = d->tokens; p.H = d->H; p.Nk = d->Nk; p.HJ = HJ; p.NJ = (HJ + 31) / 32; p.tps = tps;
     p.ldx = d->ldx; p.ldy = d->ldy; p.kq_bs = d->kq_bs; p.kq_rs = d->kq_rs; p.vo_bs = d->vo_bs; p.vo_rs = d->vo_rs; p.cs_bs = d->cs_bs;
     p.ln_ld = d->ln_stats_ld; p.ln_parts = d->ln_parts; p.ln_eps = d->ln_eps; p.inv_c = 1.0 / (double)d->C;
+    p.log2w = log2w; p.w_bs = w_bs;
     hipStream_t s = (hipStream_t)stream;
     pbe_prof_begin(PBE_K_CTXATTN, s);
     hipLaunchKernelGGL(ctx_attn_kernel, dim3((unsigned)(B * tps)), dim3(256), 0, s, p);
@@ -264,4 +270,13 @@ extern "C" int pbe_ctx_attention_f16(const pbe_ctx_attn_desc* d, pbe_stream_t st
     pbe_prof_end(PBE_K_CTXATTN, s, 2.0 * (3.0 * (double)d->M * d->C + 2.0 * (double)B * HJ * d->C));
     PBE_LAUNCH_CHECK("pbe_ctx_attention_f16");
     return PBE_OK;
+}
+
+extern "C" int pbe_ctx_attention_f16(const pbe_ctx_attn_desc* d, pbe_stream_t stream) { return ctx_attention_launch(d, nullptr, 0, stream); }
+
+// The same launch with exemplar weights: log2w [B, Nk] fp32 (element (b, j) at log2w[b * w_bs + j]) holds log2 of token j's
+// non-negative weight, -inf for weight 0.  At least one token per sample must be present (the caller validates the weights).
+extern "C" int pbe_ctx_attention_w_f16(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, pbe_stream_t stream) {
+    PBE_REQUIRE(log2w && ((uintptr_t)log2w & 3) == 0 && w_bs >= 0, "pbe_ctx_attention_w_f16: log2w must be a 4-byte aligned pointer, w_bs >= 0");
+    return ctx_attention_launch(d, log2w, w_bs, stream);
 }

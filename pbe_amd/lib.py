@@ -73,6 +73,7 @@ SYMBOLS = {
     "pbe_sizeof_mx8_out_desc": (c_sz, []),
     "pbe_sizeof_ctx_attn_desc": (c_sz, []),
     "pbe_ctx_attention_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp]),
+    "pbe_ctx_attention_w_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp, c_i64, c_vp]),
     "pbe_gemm_f16": (c_i32, [C.POINTER(GemmDesc), c_vp]),
     "pbe_conv3x3_f16": (c_i32, [C.POINTER(Conv3x3Desc), c_vp]),
     "pbe_gemm_plan": (c_i32, [C.POINTER(GemmDesc), C.POINTER(c_i32), C.POINTER(c_sz)]),
@@ -85,6 +86,7 @@ SYMBOLS = {
     "pbe_row_stats_f16": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_vp]),
     "pbe_layernorm_f8": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_f32, c_vp]),
     "pbe_attention_f16": (c_i32, [C.POINTER(AttnDesc), c_vp]),
+    "pbe_attention_kbias_f16": (c_i32, [C.POINTER(AttnDesc), c_vp, c_i64, c_vp]),
     "pbe_quant_mx8_f16": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_f32, c_vp]),
     "pbe_attention_mx8": (c_i32, [C.POINTER(AttnMx8Desc), c_vp]),
     "pbe_gemm_mx8out_f16": (c_i32, [C.POINTER(GemmDesc), C.POINTER(Mx8OutDesc), c_vp]),

@@ -571,14 +571,23 @@ def pack_linear_f8(w: torch.Tensor):
 
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, B: int, H: int, Nq: int, Nk: int, D: int, scale: float, *,
               q_strides: Tuple[int, int], k_strides: Tuple[int, int], vt_strides: Tuple[int, int],
-              out: Optional[torch.Tensor] = None, q_prescaled: bool = False) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, q_prescaled: bool = False, key_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(q k^T scale) v -> [B, Nq, H*D].  q/k: element (b,n,h,d) at b*bs + n*rs + h*D + d of the given
-    (possibly sliced) tensors; vt: element (b,h,d,n) at b*bs + (h*D+d)*rs + n.  strides = (bs, rs) in elements."""
+    (possibly sliced) tensors; vt: element (b,h,d,n) at b*bs + (h*D+d)*rs + n.  strides = (bs, rs) in elements.
+    key_bias: fp32 [B, Nk] added to the logits of key n of sample b in the LOG2 domain (log2 of a token weight, -inf = absent), for
+    every head (pbe_attention_kbias_f16, launch key `ab:`); None: pbe_attention_f16, launch key `a:`."""
     _h(q, "attention q"); _h(k, "attention k"); _h(vt, "attention vt")
     if out is None:
         out = torch.empty((B, Nq, H * D), dtype=torch.float16, device=q.device)
     d = _l.AttnDesc(_p(q), _p(k), _p(vt), _p(out), B, H, Nq, Nk, D, q_strides[0], q_strides[1], k_strides[0], k_strides[1],
                     vt_strides[0], vt_strides[1], out.stride(0), out.stride(1), float(scale), 1 if q_prescaled else 0)
+    if key_bias is not None:
+        _f(key_bias, "attention key_bias")
+        if tuple(key_bias.shape) != (B, Nk) or key_bias.stride(1) != 1:
+            raise _l.PbeError(f"attention: key_bias must be [{B}, {Nk}] with unit stride over the keys, got {tuple(key_bias.shape)}")
+        with _timed(f"ab:{B}:{H}:{Nq}:{Nk}:{D}"):
+            _l.check(_l.load().pbe_attention_kbias_f16(C.byref(d), _p(key_bias), key_bias.stride(0), _stream()), "pbe_attention_kbias_f16")
+        return out
     with _timed(f"a:{B}:{H}:{Nq}:{Nk}:{D}"):
         _l.check(_l.load().pbe_attention_f16(C.byref(d), _stream()), "pbe_attention_f16")
     return out
@@ -590,15 +599,18 @@ CTX_MAX_TOKENS, CTX_MAX_HJ, CTX_MAX_C = 16, 128, 1280        # what pbe_ctx_atte
 class CtxOperands:
     """The per-context operands of pbe_ctx_attention_f16 (include/pbe_hip.h): kq fp16 [B, HJ, C], colsum / kbias fp32 [B, HJ], vo fp16
     [B, C, HJP] (rows padded to a multiple of 8 columns, zeros), bias fp32 [C]; HJ = H * Nk.  Computed once per context
-    (BasicTransformerBlock.context_operands); a slice of the batch (`rows`) serves one half of a guidance pair."""
-    __slots__ = ("kq", "colsum", "kbias", "vo", "bias", "B", "H", "Nk", "C")
+    (BasicTransformerBlock.context_operands); a slice of the batch (`rows`) serves one half of a guidance pair.  log2w: fp32 [B, Nk]
+    log2 of the exemplar weights (-inf: token absent) or None; it rides beside the folded operands, which do not depend on it."""
+    __slots__ = ("kq", "colsum", "kbias", "vo", "bias", "B", "H", "Nk", "C", "log2w")
 
-    def __init__(self, kq, colsum, kbias, vo, bias, H, Nk):
+    def __init__(self, kq, colsum, kbias, vo, bias, H, Nk, log2w=None):
         self.kq, self.colsum, self.kbias, self.vo, self.bias, self.H, self.Nk = kq, colsum, kbias, vo, bias, int(H), int(Nk)
         self.B, self.C = kq.shape[0], kq.shape[2]
+        self.log2w = log2w
 
     def rows(self, b0: int, b1: int) -> "CtxOperands":
-        return CtxOperands(self.kq[b0:b1], self.colsum[b0:b1], self.kbias[b0:b1], self.vo[b0:b1], self.bias, self.H, self.Nk)
+        return CtxOperands(self.kq[b0:b1], self.colsum[b0:b1], self.kbias[b0:b1], self.vo[b0:b1], self.bias, self.H, self.Nk,
+                           None if self.log2w is None else self.log2w[b0:b1])
 
 
 def ctx_attention_check(C_: int, H: int, Nk: int, tokens: int, M: int) -> None:
@@ -650,6 +662,13 @@ def ctx_attention(x: torch.Tensor, ops_ctx: CtxOperands, stats: "RowStats", eps:
     d = _l.CtxAttnDesc(_p(x), _p(out), _p(o.kq), _p(o.colsum), _p(o.kbias), _p(o.vo), _p(o.bias), stats.ptr(), None if rs is None else rs.ptr(),
                        M, Cc, int(tokens), o.H, o.Nk, ldx, out.stride(0), o.kq.stride(0), o.kq.stride(1), o.vo.stride(0), o.vo.stride(1),
                        o.colsum.stride(0), stats.parts, stats.ld, float(eps))
+    if o.log2w is not None:
+        _f(o.log2w, "ctx_attention log2w")
+        if tuple(o.log2w.shape) != (o.B, o.Nk) or o.log2w.stride(1) != 1:
+            raise _l.PbeError(f"ctx_attention: log2w must be [{o.B}, {o.Nk}] with unit stride over the tokens, got {tuple(o.log2w.shape)}")
+        with _timed(f"xaw:{M}:{Cc}:{o.H}:{o.Nk}"):
+            _l.check(_l.load().pbe_ctx_attention_w_f16(C.byref(d), _p(o.log2w), o.log2w.stride(0), _stream()), "pbe_ctx_attention_w_f16")
+        return out, rs
     with _timed(f"xa:{M}:{Cc}:{o.H}:{o.Nk}"):
         _l.check(_l.load().pbe_ctx_attention_f16(C.byref(d), _stream()), "pbe_ctx_attention_f16")
     return out, rs

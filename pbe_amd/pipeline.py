@@ -5,11 +5,40 @@ VAE decode -> clamp((x+1)/2, 0, 1).  Inputs are already pre-processed tensors
 (pbe_amd.preprocess), outputs fp32 NCHW in [0,1]."""
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
+from .lib import PbeError
+
+
+def pad_conditionings(conds: Sequence[torch.Tensor], weights: Optional[Sequence] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A ragged batch of conditionings -> one padded context and its exemplar weights.  conds: per sample a tensor [k_i, D] (k_i >= 1
+    exemplar tokens, one D and device for all); weights: per sample k_i non-negative weights, default ones.  Returns (context
+    [B, K_max, D] in the dtype / on the device of conds[0], weights fp64 [B, K_max] on the host): the padding rows are COPIES of the
+    sample's first token (finite, never uninitialised memory) and carry weight 0, which removes them from the softmax - pass the pair
+    as conditioning / conditioning_weights to the samplers, or as context / context_weights to the U-Net."""
+    if len(conds) == 0:
+        raise PbeError("pad_conditionings: no conditionings")
+    if any((not isinstance(c, torch.Tensor)) or c.dim() != 2 or c.shape[0] < 1 or c.shape[1] != conds[0].shape[1] for c in conds):
+        raise PbeError("pad_conditionings: every conditioning must be a [k_i >= 1, D] tensor with one D")
+    if weights is not None and len(weights) != len(conds):
+        raise PbeError(f"pad_conditionings: {len(weights)} weight rows for {len(conds)} conditionings")
+    B, K = len(conds), max(int(c.shape[0]) for c in conds)
+    ctx = torch.empty((B, K, conds[0].shape[1]), dtype=conds[0].dtype, device=conds[0].device)
+    w = torch.zeros((B, K), dtype=torch.float64)
+    for i, c in enumerate(conds):
+        k = int(c.shape[0])
+        ctx[i, :k] = c
+        ctx[i, k:] = c[0]
+        wi = torch.ones(k, dtype=torch.float64) if weights is None else torch.as_tensor(weights[i]).detach().to("cpu", torch.float64).reshape(-1)
+        if wi.numel() != k:
+            raise PbeError(f"pad_conditionings: sample {i} has {k} tokens and {wi.numel()} weights")
+        if not bool(torch.isfinite(wi).all()) or bool((wi < 0).any()) or not float(wi.sum()) > 0.0:
+            raise PbeError(f"pad_conditionings: the weights of sample {i} must be finite, >= 0 and have a positive sum")
+        w[i, :k] = wi
+    return ctx, w
 
 
 def resize_mask(mask: torch.Tensor, size, antialias: bool = True) -> torch.Tensor:
@@ -22,9 +51,9 @@ def resize_mask(mask: torch.Tensor, size, antialias: bool = True) -> torch.Tenso
 @torch.no_grad()
 def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *, steps: int = 50, scale: float = 5.0,
             x_T: Optional[torch.Tensor] = None, post_eps: Optional[torch.Tensor] = None, sampler: str = "plms",
-            antialias: bool = True, timings: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
-    """image [B,3,H,W] in [-1,1], mask [B,1,H,W] in {0,1} (1 = keep), ref [B,3,224,224] CLIP-normalised;
-    everything on the model's GPU.  Returns {'image' [B,3,H,W] in [0,1], 'latent', 'c', 'z_inpaint', 'mask_lat'}."""
+            antialias: bool = True, timings: Optional[Dict[str, float]] = None, ref_weights=None) -> Dict[str, torch.Tensor]:
+    """image [B,3,H,W] in [-1,1], mask [B,1,H,W] in {0,1} (1 = keep), ref [B,3,224,224] CLIP-normalised (or [B,K,3,224,224]: K
+    exemplars per sample, with ref_weights [B, K] their non-negative weights or None); everything on the model's GPU.  Returns {'image' [B,3,H,W] in [0,1], 'latent', 'c', 'z_inpaint', 'mask_lat'}."""
     from ldm.models.diffusion.ddim import DDIMSampler
     from ldm.models.diffusion.plms import PLMSSampler
     dev = model.device
@@ -46,7 +75,7 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     smp = (PLMSSampler if sampler == "plms" else DDIMSampler)(model)
     z0, _ = smp.sample(S=steps, batch_size=B, shape=list(z_inp.shape[1:]), conditioning=c, verbose=False,
                        unconditional_guidance_scale=scale, unconditional_conditioning=uc, eta=0.0, x_T=x_T,
-                       test_model_kwargs={"inpaint_image": z_inp, "inpaint_mask": m_lat})
+                       test_model_kwargs={"inpaint_image": z_inp, "inpaint_mask": m_lat}, conditioning_weights=ref_weights)
     if ev:
         ev[3].record()
     img = ops.image_post(model.decode_first_stage_nhwc(z0))                              # inference.py:346-347

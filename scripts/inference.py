@@ -8,6 +8,8 @@ sampler -> decode -> clamp) and the same output tree, running on the MI355X HIP 
         --reference_path examples/reference/example_1.jpg --seed 321 --scale 5
 
 `--reference_path` may name several images (not in the reference): each becomes one context token of the sample.
+`--reference_weight w1 w2 ...` gives each of them a non-negative weight (default: all 1): its share of the cross-attention is
+proportional to w exp(score), so `2 1` equals naming the first image twice and `1 0` equals naming the first image alone.
 
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
@@ -50,10 +52,19 @@ def parse(argv=None):
     p.add_argument("--mask_path", type=str, default="")
     p.add_argument("--reference_path", type=str, nargs="+", default=[""], help="one exemplar image as in the reference, or several: they "
                    "become the context tokens of the sample")
+    p.add_argument("--reference_weight", type=float, nargs="+", default=None, help="(not in the reference) one non-negative weight per "
+                   "--reference_path, default all 1; at least one must be positive")
     p.add_argument("--random_weights", action="store_true", help="name-seeded random weights instead of --ckpt")
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
-    return p.parse_args(argv)
+    opt = p.parse_args(argv)
+    if opt.reference_weight is not None:
+        w, refs = opt.reference_weight, opt.reference_path if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
+        if len(w) != len(refs):
+            p.error(f"--reference_weight: {len(w)} weights for {len(refs)} --reference_path images")
+        if any(not (x >= 0.0) or x == float("inf") for x in w) or not sum(w) > 0.0:
+            p.error("--reference_weight: weights must be finite and >= 0 with a positive sum")
+    return opt
 
 
 def seed_everything(seed):
@@ -103,6 +114,9 @@ def main(argv=None):
             ref = torch.stack([ref] + more, 1)
         uc = model.learnable_vector if opt.scale != 1.0 else None
         c = model.proj_out(model.get_learned_conditioning(ref))                      # scripts/inference.py:326-327
+        cw = None
+        if opt.reference_weight is not None:                                           # one weight per exemplar token, the same for every sample
+            cw = torch.tensor([opt.reference_weight], dtype=torch.float64).expand(c.shape[0], -1).contiguous()
         post = model.encode_first_stage(test_model_kwargs["inpaint_image"])
         pb, ph, pw, _ = post.parameters.shape
         post_eps = torch.randn((pb, post.z, ph, pw)) if opt.dump_tensors else None   # the CPU draw DiagonalGaussianDistribution.sample() makes itself
@@ -112,7 +126,7 @@ def main(argv=None):
         shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
         samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=opt.n_samples, shape=shape, verbose=False,
                                     unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc, eta=opt.ddim_eta,
-                                    x_T=start_code, test_model_kwargs=test_model_kwargs)
+                                    x_T=start_code, test_model_kwargs=test_model_kwargs, conditioning_weights=cw)
         xd = ops.image_post(model.decode_first_stage_nhwc(samples))                  # clamp((x+1)/2, 0, 1), still on the GPU
         if not opt.skip_save:
             for i in range(xd.shape[0]):
@@ -122,7 +136,8 @@ def main(argv=None):
             import numpy as np
             np.savez(opt.dump_tensors, x_T=(start_code if start_code is not None else torch.zeros(0)).float().cpu().numpy(),
                      post_eps=post_eps.numpy(), c=c.float().cpu().numpy(), z_inpaint=z_inpaint.float().cpu().numpy(),
-                     mask64=test_model_kwargs["inpaint_mask"].float().cpu().numpy(), latent=samples.float().cpu().numpy(), image=x.numpy())
+                     mask64=test_model_kwargs["inpaint_mask"].float().cpu().numpy(), latent=samples.float().cpu().numpy(), image=x.numpy(),
+                     reference_weight=(cw if cw is not None else torch.ones(c.shape[:2])).double().numpy())
     print(f"Your samples are ready and waiting for you here: \n{opt.outdir} \n \nEnjoy.")
     return x
 

@@ -10,7 +10,14 @@ Per (M, C) in (8*4096, 320), (8*1024, 640), (8*256, 1280), (8*64, 1280) and Nk i
 is timed with device events around `inner` back-to-back launches; the three variants alternate inside every repetition, the input rotates
 over enough buffers that no launch re-reads what the previous one left in the caches (>= 512 MB in rotation, at most 16 buffers), and the
 table gives the median and the 10 % / 90 % quantiles over the repetitions, per launch, in microseconds.  "spread" is (p90 - p10) / median
-of the composition.  The variants' results are compared first (rel-L2 of fused against composition on the same operands)."""
+of the composition.  The variants' results are compared first (rel-L2 of fused against composition on the same operands).
+
+    python tools/bench_ctx_attention.py --weights [--out profiles/ctx_weights_timing.txt]
+
+times the exemplar-weight forms against their unweighted ones instead, arms alternating the same way: pbe_ctx_attention_w_f16 against
+pbe_ctx_attention_f16 at the shapes above, and pbe_attention_kbias_f16 against pbe_attention_f16 at the cross-attention shapes the
+existing-kernel route launches (a:8:8:256:4:160, a:8:8:64:4:160, a:8:8:4096:20:40).  Weights: exp2(randn), the last token of every
+second sample absent.  "spread" is (p90 - p10) / median of the unweighted arm."""
 import argparse
 import os
 import sys
@@ -60,9 +67,80 @@ def composition(x, st, c, folded):
     return ops.gemm(o.view(B * N, C), c["wo"], c["bo"], resid=x, row_stats=True)
 
 
+CROSS = [(256, 4, 160), (64, 4, 160), (4096, 20, 40)]          # (Nq, Nk, D) at B = 8, H = 8
+
+
+def _time(variants, a, nbuf):
+    """{name: [p10, median, p90]} microseconds per launch; the variants alternate inside every repetition."""
+    for fn in variants.values():
+        for w in range(a.warmup):
+            fn(w % nbuf)
+    torch.cuda.synchronize()
+    times = {k: [] for k in variants}
+    it = 0
+    for _ in range(a.reps):
+        for name, fn in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                fn(it % nbuf)
+                it += 1
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) / a.inner * 1e3)
+    return {k: torch.tensor(v).quantile(torch.tensor([0.1, 0.5, 0.9])).tolist() for k, v in times.items()}
+
+
+def _log2w(Nk, dev, g):
+    w = torch.exp2(torch.randn(B, Nk, generator=g))
+    w[1::2, Nk - 1] = 0.0
+    return torch.log2(w).float().to(dev)
+
+
+def weights_table(a, dev):
+    cell = lambda q: f"{q[1]:8.1f} [{q[0]:7.1f} .. {q[2]:7.1f}]"      # noqa: E731
+    lines = [f"# exemplar-weight forms vs their unweighted forms; device: {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}); "
+             f"B = {B} samples, {H} heads",
+             f"# per launch, microseconds: median [p10 .. p90] over {a.reps} repetitions of {a.inner} back-to-back launches, arms alternating",
+             f"# pbe_ctx_attention_w_f16 vs pbe_ctx_attention_f16\n# {'M':>6} {'C':>5} {'Nk':>3} | {'unweighted':>28} | {'weighted':>28} | w/plain  spread"]
+    g = torch.Generator().manual_seed(0)
+    for M, C in SHAPES:
+        nbuf = max(2, min(16, -(-(512 << 20) // (2 * M * C))))
+        xs = [(torch.randn(M, C, generator=g) * 0.8 + 0.1).half().to(dev) for _ in range(nbuf)]
+        sts = [ops.row_stats(x) for x in xs]
+        for Nk in TOKENS:
+            oc, _ = build(M, C, Nk, dev, g)
+            ow = ops.CtxOperands(oc.kq, oc.colsum, oc.kbias, oc.vo, oc.bias, oc.H, oc.Nk, _log2w(Nk, dev, g))
+            q = _time({"plain": lambda i: ops.ctx_attention(xs[i], oc, sts[i], 1e-5, tokens=M // B),
+                       "w": lambda i: ops.ctx_attention(xs[i], ow, sts[i], 1e-5, tokens=M // B)}, a, nbuf)
+            lines.append(f"  {M:6d} {C:5d} {Nk:3d} | {cell(q['plain']):>28} | {cell(q['w']):>28} | {q['w'][1] / q['plain'][1]:7.3f}  "
+                         f"{(q['plain'][2] - q['plain'][0]) / q['plain'][1]:6.2f}")
+            print(lines[-1], flush=True)
+        del xs, sts
+    lines.append(f"# pbe_attention_kbias_f16 vs pbe_attention_f16\n# {'launch':>20} | {'unbiased':>28} | {'key bias':>28} | kb/plain  spread")
+    for Nq, Nk, D in CROSS:
+        C = H * D
+        npad = (Nk + 7) // 8 * 8
+        nbuf = max(2, min(16, -(-(512 << 20) // (2 * B * Nq * C))))
+        qs = [torch.randn(B * Nq, C, generator=g).half().to(dev) for _ in range(nbuf)]
+        k = torch.randn(B * Nk, C, generator=g).half().to(dev)
+        vt = torch.zeros(B, C, npad, dtype=torch.float16)
+        vt[:, :, :Nk] = torch.randn(B, C, Nk, generator=g).half()
+        vt, kb = vt.to(dev), _log2w(Nk, dev, g)
+        outs = [torch.empty(B, Nq, C, dtype=torch.float16, device=dev) for _ in range(nbuf)]
+        att = lambda i, bias: ops.attention(qs[i], k, vt, B, H, Nq, Nk, D, D ** -0.5, q_strides=(Nq * C, C), k_strides=(Nk * C, C),      # noqa: E731
+                                            vt_strides=(C * npad, npad), out=outs[i], key_bias=bias)
+        q = _time({"plain": lambda i: att(i, None), "kb": lambda i: att(i, kb)}, a, nbuf)
+        lines.append(f"  {f'a:{B}:{H}:{Nq}:{Nk}:{D}':>20} | {cell(q['plain']):>28} | {cell(q['kb']):>28} | {q['kb'][1] / q['plain'][1]:8.3f}  "
+                     f"{(q['plain'][2] - q['plain'][0]) / q['plain'][1]:6.2f}")
+        print(lines[-1], flush=True)
+    return "\n".join(lines) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--weights", action="store_true", help="time the exemplar-weight forms against the unweighted ones instead")
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -70,6 +148,14 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_ctx_attention.py needs an MI355X: a timing taken anywhere else says nothing")
     dev = torch.device("cuda:0")
+    if a.weights:
+        text = weights_table(a, dev)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     lines = [f"# pbe_ctx_attention_f16 vs the kernels it replaces; device: {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}, {torch.cuda.get_device_properties(0).multi_processor_count} CUs); B = {B} samples, {H} heads",
              f"# per launch, microseconds: median [p10 .. p90] over {a.reps} repetitions of {a.inner} back-to-back launches, variants alternating; "
              "inputs rotate over >= 512 MB",
