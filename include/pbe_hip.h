@@ -351,6 +351,16 @@ int pbe_ctx_attention_f16(const pbe_ctx_attn_desc* d, pbe_stream_t stream);
  * bits of pbe_ctx_attention_f16. */
 int pbe_ctx_attention_w_f16(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, pbe_stream_t stream);
 
+/* pbe_ctx_attention_rw_f16 — pbe_ctx_attention_f16 with a weight per (sample, query row, context token): regional exemplars, token j
+ * counts e[b, t, j] >= 0 times at row t of sample b.  log2rw fp32, element (b, t, j) at log2rw[b*rw_bs + t*rw_rs + j] for t < tokens,
+ * j < Nk, = log2 e[b, t, j] (-inf for 0; the caller has multiplied the exemplar weights in), is added to kbias[b, h*Nk + j] in fp32
+ * BEFORE the LayerNorm fold's multiply-adds, for every head h.  Every row needs one token of positive weight; a +inf or NaN entry
+ * corrupts its own row only.  Rows past a sample's last token clamp their table row as they clamp X: nothing past row tokens - 1 of a
+ * sample's table, or past column Nk - 1 of a row, is read.  A table of zeros gives the bits of pbe_ctx_attention_f16, a table equal
+ * to log2 w[b, j] on every row those of pbe_ctx_attention_w_f16 (Y and row_stats_out).  The folded operands do not depend on it.
+ * Required: log2rw non-null and 4-byte aligned, rw_rs >= Nk, rw_bs >= 0; additive to the ABI (same descriptor). */
+int pbe_ctx_attention_rw_f16(const pbe_ctx_attn_desc* d, const float* log2rw, int64_t rw_bs, int64_t rw_rs, pbe_stream_t stream);
+
 /* pbe_softmax_rows_f16 — Y[r,:] = softmax(scale * X[r,:]) over rows of `cols` fp16 (VAE mid attention,
  * model.py:193-195: one head, d = 512, N = 4096, scores kept in HBM once per image). */
 int pbe_softmax_rows_f16(const void* X, void* Y, int64_t rows, int32_t cols, int64_t ldx, int64_t ldy,

@@ -77,6 +77,19 @@ def guidance_weights(weights, cond, b, guided):
     return torch.cat((torch.ones_like(w), w)).contiguous() if guided else w.contiguous()
 
 
+def guidance_regions(regions, cond, b, guided):
+    """Region maps of the context guidance_context builds: conditioning_regions [b, K, Hr, Wr] (>= 0; 1 = token j counts fully at that
+    position) -> fp64 host tensor [2b, K, Hr, Wr] for a guidance pair (the unconditional half gets ones: uc is one token repeated K
+    times, and any weights with a positive sum give that token) or [b, K, Hr, Wr] unguided; None for None.  One tensor per run, like
+    guidance_weights; validated where the tables are built (attention.prepare_context_regions)."""
+    if regions is None:
+        return None
+    r = torch.as_tensor(regions).detach().to("cpu", torch.float64)
+    if r.dim() != 4 or tuple(r.shape[:2]) != (b, cond.shape[1]):
+        raise PbeError(f"sampler: conditioning_regions must be [{b}, {cond.shape[1]}, Hr, Wr] (one map per conditioning token), got {tuple(r.shape)}")
+    return torch.cat((torch.ones_like(r), r)).contiguous() if guided else r.contiguous()
+
+
 class PLMSSampler(object):
     def __init__(self, model, schedule="linear", **kwargs):
         self.model = model
@@ -110,9 +123,12 @@ class PLMSSampler(object):
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
                eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
-               x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, conditioning_weights=None, **kwargs):
+               x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, conditioning_weights=None,
+               conditioning_regions=None, **kwargs):
         """conditioning_weights: per-sample exemplar weights [batch_size, K] over conditioning's K tokens (>= 0, positive sum per sample;
-        0 = token absent, so a ragged batch is padded to one K), or None: every token counts once."""
+        0 = token absent, so a ragged batch is padded to one K), or None: every token counts once.
+        conditioning_regions: per-sample, per-token region maps [batch_size, K, Hr, Wr] >= 0 (regional exemplars: where each token
+        applies; every transformer level's grid must divide Hr x Wr), or None: every token applies everywhere."""
         if conditioning is None:
             raise PbeError("PLMSSampler.sample: conditioning is required")
         if conditioning.shape[0] != batch_size:
@@ -126,10 +142,10 @@ class PLMSSampler(object):
         return self.plms_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
-                                  conditioning_weights=conditioning_weights, **kwargs)
+                                  conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions, **kwargs)
 
     # ---- one U-Net evaluation with guidance (plms.py:181-195) -----------------------------------
-    def _eps(self, x, step, ctx, z_inp, msk, dup, ctx_w=None):
+    def _eps(self, x, step, ctx, z_inp, msk, dup, ctx_w=None, ctx_r=None):
         b = x.shape[0]
         t = torch.full((dup * b,), int(step), device=x.device, dtype=torch.int64)
         unet = self.model.model.diffusion_model
@@ -139,7 +155,11 @@ class PLMSSampler(object):
         if (graphs_enabled(dup * b) if self.use_graph is None else self.use_graph) and x.is_cuda:      # launch-bound regime: one HIP graph per call
             if self._graphed is None or self._graphed.unet is not unet:
                 self._graphed = GraphedUNet(unet)
+            if ctx_r is not None:
+                return self._graphed(x9, t, ctx, paired, ctx_w, ctx_r)
             return self._graphed(x9, t, ctx, paired) if ctx_w is None else self._graphed(x9, t, ctx, paired, ctx_w)
+        if ctx_r is not None:
+            return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step), context_weights=ctx_w, context_regions=ctx_r)
         if ctx_w is not None:                                                     # (without weights: exactly the call made before they existed)
             return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step), context_weights=ctx_w)
         return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step))      # every row of t is `step`: the embedding rows come from the per-value cache
@@ -164,7 +184,8 @@ class PLMSSampler(object):
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, callback=None, timesteps=None, img_callback=None, log_every_t=100,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, mask=None, x0=None, conditioning_weights=None, **kwargs):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, mask=None, x0=None, conditioning_weights=None,
+                      conditioning_regions=None, **kwargs):
         device = self.model.betas.device
         if self.require_gpu and device.type != "cuda":
             raise PbeError("PLMSSampler: the model must live on an MI355X (model.to('cuda')); there is no CPU path")
@@ -181,6 +202,7 @@ class PLMSSampler(object):
             ctx = cond.to(torch.float16).contiguous()
         dup = 2 if guided else 1
         ctx_w = guidance_weights(conditioning_weights, cond, b, guided)
+        ctx_r = guidance_regions(conditioning_regions, cond, b, guided)
         scale = float(unconditional_guidance_scale)
 
         time_range = np.flip(self._schedule_subset(timesteps))
@@ -194,11 +216,11 @@ class PLMSSampler(object):
             step_next = time_range[min(i + 1, total - 1)]
             if mask is not None:
                 img = self._blend_known(img, x0, mask, step)
-            eps = self._eps(img, step, ctx, z_inp, msk, dup, ctx_w)
+            eps = self._eps(img, step, ctx, z_inp, msk, dup, ctx_w, ctx_r)
             if len(old) == 0:
                 # pseudo improved Euler (plms.py:230-235): probe x_prev with e_t, re-evaluate at t_next, average
                 x_probe, _, e_t = ops.plms_update(eps, dup, scale, img, [], self._coef(index, _AB[0]), want_pred=False)
-                eps2 = self._eps(x_probe, step_next, ctx, z_inp, msk, dup, ctx_w)
+                eps2 = self._eps(x_probe, step_next, ctx, z_inp, msk, dup, ctx_w, ctx_r)
                 # e' = (e_t + e_next)/2 : c0 weights the fresh eps (= e_next), history slot 1 = e_t
                 img, pred_x0, _ = ops.plms_update(eps2, dup, scale, img, [e_t], self._coef(index, (0.5, 0.5)), want_e_t=False)
             else:

@@ -15,6 +15,8 @@ ldm/modules/attention.py in zhanwenchen/pbe (GEGLU :38-45, FeedForward :48-65, C
     on the context alone is folded once per context into two skinny operands, and
     ``x + attn2(norm2(x), ctx)`` is ONE launch over the residual stream (pbe_ctx_attention_f16,
     DESIGN.md section 4.11); contexts longer than that kernel takes run q / attention / to_out,
+  * exemplar tokens may carry a weight per sample (``context_weights``) and a map of where each applies (``context_regions``:
+    regional exemplars, a weight per query row - pbe_ctx_attention_rw_f16 on the same folded operands),
   * bias, residual and the row-broadcast adds are GEMM epilogues.
 """
 from types import SimpleNamespace
@@ -243,10 +245,10 @@ class ContextKV:
 class ContextWeights:
     """Validated exemplar weights of one context, as the kernels take them: log2w fp32 [B, K] on the context's device, log2 of the
     weight of token j of sample b, -inf for weight 0.  Built ONCE per context by prepare_context_weights() (set-up, like the schedule tables)."""
-    __slots__ = ("log2w",)
+    __slots__ = ("log2w", "w")
 
-    def __init__(self, log2w):
-        self.log2w = log2w
+    def __init__(self, log2w, w=None):
+        self.log2w, self.w = log2w, w           # w: the validated fp64 host copy (prepare_context_regions multiplies the maps by it)
 
 
 def prepare_context_weights(context, weights):
@@ -268,7 +270,86 @@ def prepare_context_weights(context, weights):
         raise PbeError("context weights: weights must be >= 0")
     if not bool((w.sum(1) > 0).all()):
         raise PbeError("context weights: every sample needs a positive weight sum (at least one exemplar token present)")
-    return ContextWeights(torch.log2(w).to(torch.float32).to(context.device).contiguous())
+    return ContextWeights(torch.log2(w).to(torch.float32).to(context.device).contiguous(), w)
+
+
+class ContextRegions:
+    """Validated regional exemplar maps of one context: maps fp64 [B, K, Hr, Wr] and weights fp64 [B, K] on the host.  level(h, w) is
+    the table pbe_ctx_attention_rw_f16 takes at a transformer level with an h x w grid: fp32 [B, h*w, K] on the context's device,
+    log2 of the effective weight e[b, t, j] = w[b, j] * (area average of maps[b, j] over grid cell t = y*w + x, the NHWC row order);
+    a row that no token of positive weight covers takes e[b, t, :] = w[b, :] (outside every region the exemplars blend as they do
+    without regions), so every row keeps a token of positive weight.  Built once per (context, level), uploaded once, cached here."""
+    __slots__ = ("maps", "weights", "device", "_levels")
+
+    def __init__(self, maps, weights, device):
+        self.maps, self.weights, self.device, self._levels = maps, weights, device, {}
+
+    def level_weights(self, h, w):
+        """fp64 host [B, h*w, K]: the effective weights e of the h x w level (fallback rows included)."""
+        B, K, Hr, Wr = self.maps.shape
+        h, w = int(h), int(w)
+        if h < 1 or w < 1 or Hr % h or Wr % w:
+            raise PbeError(f"context regions: the {Hr} x {Wr} region maps do not divide into the {h} x {w} grid of this transformer level "
+                           f"(both sides must be whole multiples)")
+        r = self.maps.view(B, K, h, Hr // h, w, Wr // w).mean((3, 5))                 # area average, fp64
+        e = (r.reshape(B, K, h * w) * self.weights[:, :, None]).permute(0, 2, 1)
+        bare = e.sum(-1, keepdim=True) <= 0
+        return torch.where(bare, self.weights[:, None, :].expand_as(e), e).contiguous()
+
+    def level(self, h, w):
+        t = self._levels.get((int(h), int(w)))
+        if t is None:
+            t = torch.log2(self.level_weights(h, w)).to(torch.float32).to(self.device).contiguous()
+            self._levels[(int(h), int(w))] = t
+        return t
+
+
+def prepare_context_regions(context, regions, weights=None):
+    """Region maps [B, K, Hr, Wr] (>= 0; 1 = token j counts fully at that position, 0 = absent there; any resolution that every
+    transformer level's grid divides) for context [B, K, Dc] -> ContextRegions, or None for None.  weights: the exemplar weights
+    [B, K] (or a ContextWeights) that multiply the maps, None = ones; they are checked by prepare_context_weights.  Raises PbeError
+    unless the maps are [B, K, Hr, Wr], finite and >= 0."""
+    if regions is None or isinstance(regions, ContextRegions):
+        return regions
+    if context.dim() != 3:
+        raise PbeError(f"context regions: context must be [B, K, Dc], got {tuple(context.shape)}")
+    B, K = context.shape[0], context.shape[1]
+    r = torch.as_tensor(regions).detach().to("cpu", torch.float64)
+    if r.dim() != 4 or tuple(r.shape[:2]) != (B, K) or r.shape[2] < 1 or r.shape[3] < 1:
+        raise PbeError(f"context regions: regions must be [{B}, {K}, Hr, Wr] (one map per context token), got {tuple(r.shape)}")
+    if not bool(torch.isfinite(r).all()):
+        raise PbeError("context regions: regions must be finite")
+    if bool((r < 0).any()):
+        raise PbeError("context regions: regions must be >= 0")
+    cw = prepare_context_weights(context, weights)
+    if cw is None:
+        w = torch.ones((B, K), dtype=torch.float64)
+    else:
+        w = cw.w if cw.w is not None else torch.exp2(cw.log2w.detach().to("cpu", torch.float64))
+    return ContextRegions(r.contiguous(), w, context.device)
+
+
+def prepare_row_weights(x_shape, context, row_weights):
+    """Already-levelled effective weights e [B, N, K] (>= 0, finite, a positive sum on every row) -> the kernel's table fp32
+    [B, N, K] = log2 e on the context's device (log2 in fp64 on the host)."""
+    B, N, K = x_shape[0], x_shape[1], context.shape[1]
+    e = torch.as_tensor(row_weights).detach().to("cpu", torch.float64)
+    if tuple(e.shape) != (B, N, K):
+        raise PbeError(f"context row weights: must be [{B}, {N}, {K}] (sample, query token, context token), got {tuple(e.shape)}")
+    if not bool(torch.isfinite(e).all()) or bool((e < 0).any()):
+        raise PbeError("context row weights: must be finite and >= 0")
+    if not bool((e.sum(-1) > 0).all()):
+        raise PbeError("context row weights: every row needs a positive weight sum")
+    return torch.log2(e).to(torch.float32).to(context.device).contiguous()
+
+
+class RegionalVectors:
+    """What SpatialTransformer.context_vectors returns for a context WITH regions: the per-block list and the context's
+    ContextRegions.  The level is known only where the grid is: run / run_paired resolve it there (SpatialTransformer._levelled)."""
+    __slots__ = ("vecs", "regions")
+
+    def __init__(self, vecs, regions):
+        self.vecs, self.regions = vecs, regions
 
 
 class BasicTransformerBlock(HipModule):
@@ -332,6 +413,8 @@ class BasicTransformerBlock(HipModule):
     # The dispatch bound of pbe_ctx_attention_f16, from profiles/ctx_attention_timing.txt: at C = 320 and 640 the fused kernel takes 0.41 ..
     # 0.95 of the faster composition for 2 .. 16 tokens; at C = 1280 (M = 2048 / 512 rows at the headline batch: 32 / 8 workgroups, each
     # walking 20 k-tiles and 20 column tiles behind exposed load latency) it takes 1.10 .. 1.70, so those levels run the existing kernels.
+    # ctx_fused_max_width is a SPEED bound, measured against a composition (q projection / pbe_attention_kbias_f16 / to_out) that has no
+    # per-row form: it does not apply to regional exemplars, which take the fused kernel at every width it accepts (_ctx_regional).
     ctx_fused_max_tokens = ops.CTX_MAX_TOKENS
     ctx_fused_max_width = 640
 
@@ -341,14 +424,26 @@ class BasicTransformerBlock(HipModule):
         return K <= min(self.ctx_fused_max_tokens, ops.CTX_MAX_TOKENS) and a2.heads * K <= ops.CTX_MAX_HJ and Cq % 64 == 0 and \
             64 <= Cq <= min(self.ctx_fused_max_width, ops.CTX_MAX_C)
 
-    def context_operands(self, context, weights=None):
+    def _ctx_regional(self, K):
+        """Regions need the fused kernel (the only per-row form): raise PbeError naming the limit a K-token context breaks."""
+        a2, Cq = self.attn2, self.attn2.to_q.weight.shape[1]
+        if K > ops.CTX_MAX_TOKENS:
+            raise PbeError(f"BasicTransformerBlock: regional exemplars take at most {ops.CTX_MAX_TOKENS} context tokens, got {K}")
+        if a2.heads * K > ops.CTX_MAX_HJ:
+            raise PbeError(f"BasicTransformerBlock: regional exemplars need heads * tokens <= {ops.CTX_MAX_HJ}, got {a2.heads} * {K}")
+        if Cq % 64 or not 64 <= Cq <= ops.CTX_MAX_C:
+            raise PbeError(f"BasicTransformerBlock: regional exemplars need a width that is a multiple of 64 in 64..{ops.CTX_MAX_C}, got {Cq}")
+
+    def context_operands(self, context, weights=None, regional=False):
         """What run() needs of a context, computed once per context.  weights: exemplar weights [B, K] or a ContextWeights
         (prepare_context_weights: validated there), None = every token counts once; their log2 rides beside the operands (CtxOperands.log2w /
         ContextKV.log2w), which do not depend on it.  [B, 1, Dc]: attn2's constant to_out(to_v(context)) as [B, C]
         (single_token_context: the softmax over one key is 1).  [B, K > 1, Dc]: the operands of pbe_ctx_attention_f16 (ops.CtxOperands:
         with k = to_k(context), v = to_v(context), per head Kq = scale log2(e) k_h (Wq gamma2)_h, kbias = scale log2(e) k_h (Wq beta2)_h,
         Vo = Wo_h v_h, colsum = row sums of the fp16 Kq) - or, beyond that kernel's dispatch bound (K > 16, heads * K > 128, C > 640), a ContextKV
-        for the q projection / pbe_attention_f16 / to_out route.  All products are pbe_gemm_f16 launches."""
+        for the q projection / pbe_attention_f16 / to_out route.  All products are pbe_gemm_f16 launches.  regional: the caller will hand
+        the operands a per-row table (CtxOperands.with_row_weights), so K > 1 always takes the fused kernel, at every width it accepts,
+        and a context beyond its limits is refused."""
         c = _tokens(context)
         if c.dim() != 3:
             raise PbeError(f"BasicTransformerBlock: context must be [B, K, Dc], got {tuple(c.shape)}")
@@ -361,8 +456,10 @@ class BasicTransformerBlock(HipModule):
                            "constant into the out-projection epilogue; the multi-token kernels take fp16 operands only)")
         a2, p2 = self.attn2, self.attn2.pk()
         inner = a2.heads * a2.dim_head
+        if regional:
+            self._ctx_regional(K)
         k = ops.gemm(c.view(B * K, -1), p2.wk)                                    # [B*K, inner]
-        if not self._ctx_fused(K):
+        if not regional and not self._ctx_fused(K):
             npad = (K + 7) // 8 * 8
             vt = torch.zeros((B, inner, npad), dtype=torch.float16, device=c.device)
             ops.gemm(p2.wv.unsqueeze(0).expand(B, -1, -1), c, out=vt[:, :, :K] if npad != K else vt)
@@ -514,12 +611,22 @@ class BasicTransformerBlock(HipModule):
             return self.ff.run_f8(*ops.layernorm_f8(x1, p.g3, p.b3, p.eps3), resid=x1)
         return self.ff.run(ops.layernorm(x1, p.g3, p.b3, p.eps3), resid=x1)
 
-    def forward(self, x, context=None, context_weights=None):
-        """x [B, N, C], context [B, K, Dc] with K >= 1 tokens per sample (context_weights [B, K] or None) -> [B, N, C]."""
+    def forward(self, x, context=None, context_weights=None, context_row_weights=None):
+        """x [B, N, C], context [B, K, Dc] with K >= 1 tokens per sample (context_weights [B, K] or None) -> [B, N, C].
+        context_row_weights: the already-levelled regional form, effective weights e [B, N, K] >= 0 of token j at query row t (they
+        hold the exemplar weights already, so context_weights must be None with them)."""
         x = _tokens(x)
         B, N, Cc = x.shape
         if context is None or context.dim() != 3 or context.shape[0] != B:
             raise PbeError("BasicTransformerBlock: the HIP path expects a context [B, K, D] with one row of K >= 1 tokens per sample")
+        if context_row_weights is not None:
+            if context_weights is not None:
+                raise PbeError("BasicTransformerBlock: context_row_weights hold the exemplar weights already: give one of the two")
+            table = prepare_row_weights(x.shape, context, context_row_weights)
+            o = self.context_operands(context, None, regional=True)
+            if isinstance(o, ops.CtxOperands):               # (K = 1: validated, otherwise ignored - the softmax over one key is 1)
+                o = o.with_row_weights(table)
+            return self.run(x.view(B * N, Cc), B, N, o).view(B, N, Cc)
         return self.run(x.view(B * N, Cc), B, N, self.context_operands(context, context_weights)).view(B, N, Cc)
 
 
@@ -541,17 +648,34 @@ class SpatialTransformer(HipModule):
                                wi=ops.pack_linear(self.proj_in.weight), bi=f32(self.proj_in.bias),
                                wo=ops.pack_linear(self.proj_out.weight), bo=f32(self.proj_out.bias))
 
-    def context_vectors(self, context, context_weights=None):
+    def context_vectors(self, context, context_weights=None, context_regions=None):
         """Per block, what its run() needs of context [B, K, Dc]: the [B, C] constant for K = 1, the multi-token operands for K > 1
-        (BasicTransformerBlock.context_operands).  context_weights: exemplar weights [B, K] (or a ContextWeights), validated once here."""
+        (BasicTransformerBlock.context_operands).  context_weights: exemplar weights [B, K] (or a ContextWeights), validated once here.
+        context_regions: region maps [B, K, Hr, Wr] (or a ContextRegions), validated once here; with them the result is a
+        RegionalVectors (the list and the regions), which run() / run_paired() resolve at their grid."""
         cw = prepare_context_weights(context, context_weights)
-        return [blk.context_operands(context, cw) for blk in self.transformer_blocks]
+        cr = prepare_context_regions(context, context_regions, cw)
+        vecs = [blk.context_operands(context, cw, regional=cr is not None) for blk in self.transformer_blocks]
+        return vecs if cr is None else RegionalVectors(vecs, cr)
+
+    @staticmethod
+    def _levelled(ctx_vecs, H, W):
+        """The per-block list of ctx_vecs; a RegionalVectors gets the regions' table of the H x W grid on every multi-token block's
+        operands (one-token constants: unchanged)."""
+        if not isinstance(ctx_vecs, RegionalVectors):
+            return ctx_vecs
+        vecs = ctx_vecs.vecs
+        if not any(isinstance(cv, ops.CtxOperands) for cv in vecs):      # (K = 1: validated, otherwise ignored)
+            return vecs
+        table = ctx_vecs.regions.level(H, W)
+        return [cv.with_row_weights(table) if isinstance(cv, ops.CtxOperands) else cv for cv in vecs]
 
     def run(self, x, ctx_vecs):
         """x [B, H, W, C] fp16 NHWC -> same shape; ctx_vecs = context_vectors(context)."""
         p = self.pk()
         B, H, W, Cc = x.shape
         N = H * W
+        ctx_vecs = self._levelled(ctx_vecs, H, W)
         h, st = ops.gemm(ops.groupnorm(x, p.g, p.b, p.eps, False).view(B * N, Cc), p.wi, p.bi, row_stats=True)   # statistics for the first block's norm1
         for blk, cv in zip(self.transformer_blocks, ctx_vecs):
             h, st = blk.run(h, B, N, cv, stats=st), None
@@ -563,6 +687,7 @@ class SpatialTransformer(HipModule):
         p = self.pk()
         B, H, W, Cc = x.shape
         N = H * W
+        ctx_vecs = self._levelled(ctx_vecs, H, W)
         x2d = x.view(B * N, Cc)
         with ops.pinned_batch_scale(2):
             h, st = ops.gemm(ops.groupnorm(x, p.g, p.b, p.eps, False).view(B * N, Cc), p.wi, p.bi, row_stats=True)
@@ -575,10 +700,11 @@ class SpatialTransformer(HipModule):
                 ops.gemm(h[half * B * N:(half + 1) * B * N], p.wo, p.bo, resid=x2d, out=y[half * B * N:(half + 1) * B * N])
         return y.view(2 * B, H, W, Cc)
 
-    def forward(self, x, context=None, context_weights=None):
-        """Reference layout: x [B, C, H, W], context [B, K, Dc] (K >= 1 tokens), context_weights [B, K] or None -> [B, C, H, W]."""
+    def forward(self, x, context=None, context_weights=None, context_regions=None):
+        """Reference layout: x [B, C, H, W], context [B, K, Dc] (K >= 1 tokens), context_weights [B, K] or None, context_regions
+        [B, K, Hr, Wr] or None (H | Hr and W | Wr) -> [B, C, H, W]."""
         require_gpu(x, "SpatialTransformer")
         if context is None:
             raise PbeError("SpatialTransformer: context is required on the Paint-by-Example path")
-        y = self.run(ops.nchw_to_nhwc(x.float()), self.context_vectors(context, context_weights))
+        y = self.run(ops.nchw_to_nhwc(x.float()), self.context_vectors(context, context_weights, context_regions))
         return ops.nhwc_to_nchw(y).to(x.dtype)

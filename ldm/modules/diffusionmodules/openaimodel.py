@@ -25,7 +25,7 @@ from torch import nn
 from pbe_amd import ops
 from pbe_amd.hipmodule import HipModule, f32, require_gpu
 from pbe_amd.lib import PbeError
-from ldm.modules.attention import SpatialTransformer, prepare_context_weights
+from ldm.modules.attention import SpatialTransformer, prepare_context_regions, prepare_context_weights
 from ldm.modules.diffusionmodules.util import conv_nd, linear, normalization, timestep_embedding, zero_module
 
 
@@ -237,23 +237,28 @@ class UNetModel(HipModule):
         self.__dict__["_ctx_cache"] = None
         self.__dict__["_emb_cache"] = {}
 
-    def context_vectors(self, context, context_weights=None):
+    def context_vectors(self, context, context_weights=None, context_regions=None):
         """What the 16 transformer blocks need of this context [N, K, context_dim] (cached while the same context tensor is presented,
         i.e. across the 51 calls of one PLMS run): for K = 1 the per-sample cross-attention constants, for K > 1 tokens per sample the
         operands of the multi-token cross-attention (BasicTransformerBlock.context_operands).  context_weights: exemplar weights [N, K]
         or None; the cache key holds the weights tensor's identity and version too (the same context with other weights is another
-        entry), and the weights are validated and uploaded once per entry (attention.prepare_context_weights)."""
-        w = context_weights
-        if isinstance(w, torch.Tensor):
-            wkey = (w.data_ptr(), w._version, tuple(w.shape), w.dtype, str(w.device))
-        else:
-            wkey = None if w is None else ("values", repr(w))
-        key = (context.data_ptr(), context._version, tuple(context.shape), context.dtype, wkey)
+        entry), and the weights are validated and uploaded once per entry (attention.prepare_context_weights).  context_regions: region
+        maps [N, K, Hr, Wr] or None (attention.prepare_context_regions), keyed and kept alive exactly as the weights are; the entry's
+        ContextRegions is shared by every transformer, so each level's table is built and uploaded once per entry."""
+        def tkey(w):
+            if isinstance(w, torch.Tensor):
+                return (w.data_ptr(), w._version, tuple(w.shape), w.dtype, str(w.device))
+            return None if w is None else ("values", repr(w))
+        w, r = context_weights, context_regions
+        key = (context.data_ptr(), context._version, tuple(context.shape), context.dtype, tkey(w))
+        if r is not None:                     # (without regions: the key as it was)
+            key += (tkey(r),)
         c = self.__dict__.get("_ctx_cache")
         if c is None or c[0] != key:
             cw = prepare_context_weights(context, w)
-            vecs = {id(st): st.context_vectors(context, cw) for st in self._transformers()}
-            c = (key, vecs, context, w)       # keep `context` (and the weights) alive so a data_ptr cannot be recycled
+            cr = prepare_context_regions(context, r, cw)
+            vecs = {id(st): st.context_vectors(context, cw, cr) for st in self._transformers()}
+            c = (key, vecs, context, w, r)    # keep `context` (and the weights / regions) alive so a data_ptr cannot be recycled
             self.__dict__["_ctx_cache"] = c
         return c[1]
 
@@ -286,9 +291,11 @@ class UNetModel(HipModule):
             row = cache[(int(step), device)] = ops.gemm(e, p.emb_w, p.emb_b)
         return row
 
-    def forward_nhwc(self, x16, timesteps, context, paired=False, step=None, context_weights=None):
+    def forward_nhwc(self, x16, timesteps, context, paired=False, step=None, context_weights=None, context_regions=None):
         """x16 [B,H,W,cin_pad] fp16 (channels >= in_channels zero), context [B, K, context_dim] (K >= 1) -> eps [B,H,W,out_channels] fp16.
         context_weights: per-sample exemplar weights [B, K] (>= 0, positive sum per sample; 0 = token absent) or None.
+        context_regions: per-sample, per-token region maps [B, K, Hr, Wr] >= 0 (every transformer level's grid must divide Hr x Wr:
+        the level's map is the area average, and a position no region covers blends the exemplars by their weights) or None.
 
         paired=True is the classifier-free-guidance call of the samplers (plms.py:182-189): the reference feeds
         cat([x]*2), cat([t]*2), cat([uc, c]) - both halves share x and t and differ ONLY in the context.  Then x16 holds the
@@ -299,7 +306,7 @@ class UNetModel(HipModule):
         fp32 summation order - is pinned to the batch-2B choice, so the duplicated evaluation gives the same bits
         (tools/layer_diff.py shows where un-pinned batch sizes part ways)."""
         p = self.pk()
-        ctx = self.context_vectors(context, context_weights)
+        ctx = self.context_vectors(context, context_weights, context_regions)
         if step is not None:                                           # the caller vouches that every entry of `timesteps` equals `step` (the samplers do)
             emb_all = self.embedding_rows(step, x16.device).expand(timesteps.shape[0], -1)      # one cached row, stride-0 broadcast over the samples
         else:
@@ -334,9 +341,9 @@ class UNetModel(HipModule):
         h = ops.groupnorm(h, p.go, p.bo, p.eps_o, True)
         return ops.conv3x3(h, p.w_out, p.b_out)
 
-    def forward(self, x, timesteps=None, context=None, y=None, context_weights=None, **kwargs):
+    def forward(self, x, timesteps=None, context=None, y=None, context_weights=None, context_regions=None, **kwargs):
         """x [N, in_channels, H, W] (fp32 or fp16), timesteps [N] int, context [N, K, context_dim] (K >= 1 tokens per sample),
-        context_weights [N, K] exemplar weights or None -> eps [N, out_channels, H, W] in fp16 (what the reference returns under
+        context_weights [N, K] exemplar weights or None, context_regions [N, K, Hr, Wr] region maps or None -> eps [N, out_channels, H, W] in fp16 (what the reference returns under
         torch.autocast)."""
         if y is not None:
             raise PbeError("UNetModel: class labels are not supported (num_classes is None)")
@@ -345,5 +352,5 @@ class UNetModel(HipModule):
             raise PbeError("UNetModel.forward needs timesteps and context")
         p = self.pk()
         x16 = ops.nchw_to_nhwc(x.float(), p.cin_pad)
-        out = self.forward_nhwc(x16, timesteps, context, context_weights=context_weights)
+        out = self.forward_nhwc(x16, timesteps, context, context_weights=context_weights, context_regions=context_regions)
         return ops.nhwc_to_nchw(out).to(torch.float16)

@@ -18,6 +18,12 @@
 //
 // Rows past the sample's last token are CLAMPED on every read and masked on every write; rows of Kq past HJ are clamped and their
 // columns get weight 0; chunks of a Vo row past HJ are zeroed in registers, never trusted (0 * NaN).  Fixed summation order everywhere.
+//
+// Row-weight form (template RW, pbe_ctx_attention_rw_f16): the weight of context token j depends on the query row too (regional
+// exemplars), so log2rw[b, t, j] joins kbias per (row, column) in the softmax stage instead of once per workgroup.  The tile's 64 x Nk
+// table entries are fetched into <= 4 registers per thread before phase 1 (their latency hides under it) and parked in an LDS
+// array that only this form has (4352 B; the occupancy of 2 is set by the registers, 57344 B fit twice), so the softmax stage stays
+// one pass.  The RW = false instantiation is the kernel as it was.
 #include "common.h"
 #include "../../include/pbe_hip.h"
 
@@ -28,6 +34,7 @@ struct CtxP {
     long ldx, ldy, kq_bs, kq_rs, vo_bs, vo_rs, cs_bs, ln_ld;
     int ln_parts; float ln_eps; double inv_c;
     const float* log2w; long w_bs;          // pbe_ctx_attention_w_f16: per-(sample, token) log2 weight added to kbias, or null
+    const float* log2rw; long rw_bs, rw_rs; // RW form: per-(sample, row, token) log2 weight, element (b, t, j) at b rw_bs + t rw_rs + j
 };
 
 #define CTX_TM 64          // rows per workgroup
@@ -35,7 +42,9 @@ struct CtxP {
 #define CTX_TS 72          // halfs per staged row (9 16-byte slots, odd: conflict-free ds_read_b128)
 #define CTX_SS 129         // floats per row of S (odd: the (row, head) threads of a wave hit 64 different banks)
 #define CTX_PS 136         // halfs per row of P (17 slots)
+#define CTX_RS 17          // RW form: floats per parked table row (odd: the 64 rows of a wave hit 64 different banks)
 
+template <bool RW>
 __global__ void __launch_bounds__(256) ctx_attn_kernel(const CtxP p) {
     // [0, 33024): phase 1 staging (X tile 64 x 72, Kq tile 128 x 72 halfs = 27648 B), then S fp32 [64][129]
     __shared__ __attribute__((aligned(16))) unsigned char smem[CTX_TM * CTX_SS * 4 + CTX_TM * CTX_PS * 2];
@@ -89,6 +98,15 @@ __global__ void __launch_bounds__(256) ctx_attn_kernel(const CtxP p) {
         const int q = tid + 256 * u, r = q >> 3, c8 = q & 7;
         ksrc[u] = Kqb + (long)min(r, HJ - 1) * p.kq_rs + c8 * 8;
     }
+    // RW form: this tile's table entries (row, token) = (q / Nk, q % Nk), q = tid + 256 u < 64 Nk <= 1024; the row is clamped as X's is
+    float rwv[4];
+    if constexpr (RW) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int q = tid + 256 * u, r = q / p.Nk, j = q - r * p.Nk;
+            rwv[u] = q < CTX_TM * p.Nk ? p.log2rw[(long)b * p.rw_bs + (long)min(row0 + r, p.tokens - 1) * p.rw_rs + j] : 0.f;
+        }
+    }
     h16x8 xr[2], kr[4];
     auto fetch = [&](int k0) {
 #pragma unroll
@@ -139,16 +157,30 @@ __global__ void __launch_bounds__(256) ctx_attn_kernel(const CtxP p) {
             for (int r = 0; r < 16; ++r)
                 S[(rw * 32 + (r & 3) + 8 * (r >> 2) + 4 * h5) * CTX_SS + (cw + 2 * i) * 32 + l31] = acc[i][r];
         }
+    float* T = nullptr;
+    if constexpr (RW) {                                      // park the table in LDS of its own (the discarded branch allocates nothing)
+        __shared__ float s_rw[CTX_TM * CTX_RS];
+        T = s_rw;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int q = tid + 256 * u, r = q / p.Nk, j = q - r * p.Nk;
+            if (q < CTX_TM * p.Nk) T[r * CTX_RS + j] = rwv[u];
+        }
+    }
     __syncthreads();
 
     // ---- LayerNorm fold + grouped softmax (fp32, group maximum subtracted), weights rounded to fp16 once ----
+    // RW form: the row's table entry is added to kbias FIRST (fp32), then the same fma chain: a table of zeros gives the plain form's
+    // bits, a row-constant table the weighted form's.
     for (int q = tid; q < CTX_TM * p.H; q += 256) {
         const int row = q & (CTX_TM - 1), h = q >> 6;
         float* srow = S + row * CTX_SS + h * p.Nk;
         const float rstd = s_rstd[row], nmr = s_nmr[row];
         float mx = -INFINITY;
         for (int j = 0; j < p.Nk; ++j) {
-            const float v = fmaf(rstd, srow[j], fmaf(nmr, s_cs[h * p.Nk + j], s_kb[h * p.Nk + j]));
+            float kb = s_kb[h * p.Nk + j];
+            if constexpr (RW) kb += T[row * CTX_RS + j];
+            const float v = fmaf(rstd, srow[j], fmaf(nmr, s_cs[h * p.Nk + j], kb));
             srow[j] = v;
             mx = fmaxf(mx, v);
         }
@@ -238,7 +270,8 @@ __global__ void __launch_bounds__(256) ctx_attn_kernel(const CtxP p) {
 
 extern "C" size_t pbe_sizeof_ctx_attn_desc(void) { return sizeof(pbe_ctx_attn_desc); }
 
-static int ctx_attention_launch(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, pbe_stream_t stream) {
+static int ctx_attention_launch(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, const float* log2rw, int64_t rw_bs, int64_t rw_rs,
+                                pbe_stream_t stream) {
     PBE_REQUIRE(d && d->X && d->Y && d->Kq && d->colsum && d->kbias && d->Vo && d->bias && d->ln_stats, "pbe_ctx_attention_f16: null operand");
     PBE_REQUIRE(d->C % 64 == 0 && d->C >= 64 && d->C <= 1280, "pbe_ctx_attention_f16: C = %d unsupported (multiple of 64, 64..1280)", d->C);
     PBE_REQUIRE(d->Nk >= 1 && d->Nk <= 16, "pbe_ctx_attention_f16: Nk = %d unsupported (1..16 context tokens)", d->Nk);
@@ -261,10 +294,11 @@ static int ctx_attention_launch(const pbe_ctx_attn_desc* d, const float* log2w, 
     p.C = d->C; p.tokens = d->tokens; p.H = d->H; p.Nk = d->Nk; p.HJ = HJ; p.NJ = (HJ + 31) / 32; p.tps = tps;
     p.ldx = d->ldx; p.ldy = d->ldy; p.kq_bs = d->kq_bs; p.kq_rs = d->kq_rs; p.vo_bs = d->vo_bs; p.vo_rs = d->vo_rs; p.cs_bs = d->cs_bs;
     p.ln_ld = d->ln_stats_ld; p.ln_parts = d->ln_parts; p.ln_eps = d->ln_eps; p.inv_c = 1.0 / (double)d->C;
-    p.log2w = log2w; p.w_bs = w_bs;
+    p.log2w = log2w; p.w_bs = w_bs; p.log2rw = log2rw; p.rw_bs = rw_bs; p.rw_rs = rw_rs;
     hipStream_t s = (hipStream_t)stream;
     pbe_prof_begin(PBE_K_CTXATTN, s);
-    hipLaunchKernelGGL(ctx_attn_kernel, dim3((unsigned)(B * tps)), dim3(256), 0, s, p);
+    if (log2rw) hipLaunchKernelGGL(ctx_attn_kernel<true>, dim3((unsigned)(B * tps)), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(ctx_attn_kernel<false>, dim3((unsigned)(B * tps)), dim3(256), 0, s, p);
     // a class of its own, accounted in bytes like the norms (memory-bound: 4 HJ FLOP per byte of X at most): X twice (the 2nd from L2 at
     // best), Y, Kq, Vo
     pbe_prof_end(PBE_K_CTXATTN, s, 2.0 * (3.0 * (double)d->M * d->C + 2.0 * (double)B * HJ * d->C));
@@ -272,11 +306,22 @@ static int ctx_attention_launch(const pbe_ctx_attn_desc* d, const float* log2w, 
     return PBE_OK;
 }
 
-extern "C" int pbe_ctx_attention_f16(const pbe_ctx_attn_desc* d, pbe_stream_t stream) { return ctx_attention_launch(d, nullptr, 0, stream); }
+extern "C" int pbe_ctx_attention_f16(const pbe_ctx_attn_desc* d, pbe_stream_t stream) { return ctx_attention_launch(d, nullptr, 0, nullptr, 0, 0, stream); }
 
 // The same launch with exemplar weights: log2w [B, Nk] fp32 (element (b, j) at log2w[b * w_bs + j]) holds log2 of token j's
 // non-negative weight, -inf for weight 0.  At least one token per sample must be present (the caller validates the weights).
 extern "C" int pbe_ctx_attention_w_f16(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, pbe_stream_t stream) {
     PBE_REQUIRE(log2w && ((uintptr_t)log2w & 3) == 0 && w_bs >= 0, "pbe_ctx_attention_w_f16: log2w must be a 4-byte aligned pointer, w_bs >= 0");
-    return ctx_attention_launch(d, log2w, w_bs, stream);
+    return ctx_attention_launch(d, log2w, w_bs, nullptr, 0, 0, stream);
+}
+
+// The same launch with a weight per (sample, query row, token): log2rw fp32, element (b, t, j) at log2rw[b * rw_bs + t * rw_rs + j] for
+// t < tokens, j < Nk, holds log2 of the effective weight of token j at row t (-inf: absent there; the exemplar weights are already
+// multiplied in).  Every row must keep one token of positive weight (the caller's fallback rule sees to it).  The entry is added to
+// kbias in fp32 before the LayerNorm fold's fma chain: zeros give the bits of pbe_ctx_attention_f16, log2 w[b, j] on every row those
+// of pbe_ctx_attention_w_f16.  Nothing past row tokens - 1 of a sample's table or past column Nk - 1 is read.
+extern "C" int pbe_ctx_attention_rw_f16(const pbe_ctx_attn_desc* d, const float* log2rw, int64_t rw_bs, int64_t rw_rs, pbe_stream_t stream) {
+    PBE_REQUIRE(log2rw && ((uintptr_t)log2rw & 3) == 0, "pbe_ctx_attention_rw_f16: log2rw must be a 4-byte aligned pointer");
+    PBE_REQUIRE(d && rw_rs >= d->Nk && rw_bs >= 0, "pbe_ctx_attention_rw_f16: rw_rs must cover Nk, rw_bs >= 0");
+    return ctx_attention_launch(d, nullptr, 0, log2rw, rw_bs, rw_rs, stream);
 }

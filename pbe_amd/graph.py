@@ -31,18 +31,22 @@ class GraphedUNet:
         self.graph = None
         self.replays = 0
 
-    def __call__(self, x9: torch.Tensor, t: torch.Tensor, ctx: torch.Tensor, paired: bool, ctx_w=None) -> torch.Tensor:
-        """Same contract as ``unet.forward_nhwc(x9, t, ctx, paired=paired, context_weights=ctx_w)``.  The returned tensor is a static buffer that
+    def __call__(self, x9: torch.Tensor, t: torch.Tensor, ctx: torch.Tensor, paired: bool, ctx_w=None, ctx_r=None) -> torch.Tensor:
+        """Same contract as ``unet.forward_nhwc(x9, t, ctx, paired=paired, context_weights=ctx_w, context_regions=ctx_r)``.  The returned tensor is a static buffer that
         the next call overwrites (the samplers consume it before calling again)."""
         wkey = None if ctx_w is None else (ctx_w.data_ptr(), ctx_w._version, tuple(ctx_w.shape))      # (a tensor: plms.guidance_weights)
         key = (tuple(x9.shape), tuple(t.shape), ctx.data_ptr(), ctx._version, tuple(ctx.shape), bool(paired), wkey)
+        kw = {"context_weights": ctx_w}
+        if ctx_r is not None:                                                                         # (a tensor: plms.guidance_regions)
+            key += ((ctx_r.data_ptr(), ctx_r._version, tuple(ctx_r.shape)),)
+            kw["context_regions"] = ctx_r
         if key != self.key:
-            self.sx, self.st, self.ctx, self.ctx_w = x9.clone(), t.clone(), ctx, ctx_w
-            out = self.unet.forward_nhwc(self.sx, self.st, ctx, paired=paired, context_weights=ctx_w)     # eager: builds packs / caches / function attributes
+            self.sx, self.st, self.ctx, self.ctx_w, self.ctx_r = x9.clone(), t.clone(), ctx, ctx_w, ctx_r
+            out = self.unet.forward_nhwc(self.sx, self.st, ctx, paired=paired, **kw)     # eager: builds packs / caches / function attributes
             torch.cuda.current_stream().synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self.out = self.unet.forward_nhwc(self.sx, self.st, ctx, paired=paired, context_weights=ctx_w)
+                self.out = self.unet.forward_nhwc(self.sx, self.st, ctx, paired=paired, **kw)
             self.graph, self.key = g, key
             return out
         self.sx.copy_(x9)

@@ -600,17 +600,23 @@ class CtxOperands:
     """The per-context operands of pbe_ctx_attention_f16 (include/pbe_hip.h): kq fp16 [B, HJ, C], colsum / kbias fp32 [B, HJ], vo fp16
     [B, C, HJP] (rows padded to a multiple of 8 columns, zeros), bias fp32 [C]; HJ = H * Nk.  Computed once per context
     (BasicTransformerBlock.context_operands); a slice of the batch (`rows`) serves one half of a guidance pair.  log2w: fp32 [B, Nk]
-    log2 of the exemplar weights (-inf: token absent) or None; it rides beside the folded operands, which do not depend on it."""
-    __slots__ = ("kq", "colsum", "kbias", "vo", "bias", "B", "H", "Nk", "C", "log2w")
+    log2 of the exemplar weights (-inf: token absent) or None; it rides beside the folded operands, which do not depend on it.
+    log2rw: fp32 [B, tokens, Nk] (unit stride over the Nk tokens of the context) log2 of the weight of token j at query row t, for
+    regional exemplars (pbe_ctx_attention_rw_f16), or None.  It REPLACES log2w - the host has multiplied the exemplar weights in."""
+    __slots__ = ("kq", "colsum", "kbias", "vo", "bias", "B", "H", "Nk", "C", "log2w", "log2rw")
 
-    def __init__(self, kq, colsum, kbias, vo, bias, H, Nk, log2w=None):
+    def __init__(self, kq, colsum, kbias, vo, bias, H, Nk, log2w=None, log2rw=None):
         self.kq, self.colsum, self.kbias, self.vo, self.bias, self.H, self.Nk = kq, colsum, kbias, vo, bias, int(H), int(Nk)
         self.B, self.C = kq.shape[0], kq.shape[2]
-        self.log2w = log2w
+        self.log2w, self.log2rw = log2w, log2rw
 
     def rows(self, b0: int, b1: int) -> "CtxOperands":
         return CtxOperands(self.kq[b0:b1], self.colsum[b0:b1], self.kbias[b0:b1], self.vo[b0:b1], self.bias, self.H, self.Nk,
-                           None if self.log2w is None else self.log2w[b0:b1])
+                           None if self.log2w is None else self.log2w[b0:b1], None if self.log2rw is None else self.log2rw[b0:b1])
+
+    def with_row_weights(self, log2rw) -> "CtxOperands":
+        """The same folded operands with the per-row table in place of the per-sample weights (nothing is re-folded)."""
+        return CtxOperands(self.kq, self.colsum, self.kbias, self.vo, self.bias, self.H, self.Nk, None, log2rw)
 
 
 def ctx_attention_check(C_: int, H: int, Nk: int, tokens: int, M: int) -> None:
@@ -662,6 +668,19 @@ def ctx_attention(x: torch.Tensor, ops_ctx: CtxOperands, stats: "RowStats", eps:
     d = _l.CtxAttnDesc(_p(x), _p(out), _p(o.kq), _p(o.colsum), _p(o.kbias), _p(o.vo), _p(o.bias), stats.ptr(), None if rs is None else rs.ptr(),
                        M, Cc, int(tokens), o.H, o.Nk, ldx, out.stride(0), o.kq.stride(0), o.kq.stride(1), o.vo.stride(0), o.vo.stride(1),
                        o.colsum.stride(0), stats.parts, stats.ld, float(eps))
+    if o.log2rw is not None:
+        if o.log2w is not None:
+            raise _l.PbeError("ctx_attention: log2rw replaces log2w (the row table holds the exemplar weights already): give one of them")
+        t = _f(o.log2rw, "ctx_attention log2rw")
+        if t.device != x.device:
+            raise _l.PbeError(f"ctx_attention: log2rw is on {t.device}, x on {x.device}")
+        if t.dim() != 3 or tuple(t.shape) != (o.B, int(tokens), o.Nk):
+            raise _l.PbeError(f"ctx_attention: log2rw must be [{o.B}, {int(tokens)}, {o.Nk}] (samples, tokens, context tokens), got {tuple(t.shape)}")
+        if t.stride(2) != 1 or t.stride(1) < o.Nk or t.stride(0) < 0:
+            raise _l.PbeError(f"ctx_attention: log2rw needs unit stride over the context tokens and rows of >= {o.Nk} floats, got strides {tuple(t.stride())}")
+        with _timed(f"xar:{M}:{Cc}:{o.H}:{o.Nk}"):
+            _l.check(_l.load().pbe_ctx_attention_rw_f16(C.byref(d), _p(t), t.stride(0), t.stride(1), _stream()), "pbe_ctx_attention_rw_f16")
+        return out, rs
     if o.log2w is not None:
         _f(o.log2w, "ctx_attention log2w")
         if tuple(o.log2w.shape) != (o.B, o.Nk) or o.log2w.stride(1) != 1:

@@ -41,6 +41,22 @@ def pad_conditionings(conds: Sequence[torch.Tensor], weights: Optional[Sequence]
     return ctx, w
 
 
+def pad_regions(regions: Sequence, K_max: int) -> torch.Tensor:
+    """The region maps of a ragged batch -> one padded tensor: regions holds per sample a [k_i, Hr, Wr] tensor (1 <= k_i <= K_max maps
+    >= 0, one Hr x Wr for all), the result is fp64 [B, K_max, Hr, Wr] on the host with ZEROS on the padding tokens (absent everywhere,
+    as their weight 0 from pad_conditionings already makes them) - pass it as conditioning_regions / context_regions beside the pair
+    pad_conditionings returns."""
+    if len(regions) == 0:
+        raise PbeError("pad_regions: no regions")
+    rs = [torch.as_tensor(r).detach().to("cpu", torch.float64) for r in regions]
+    if any(r.dim() != 3 or r.shape[0] < 1 or r.shape[0] > K_max or tuple(r.shape[1:]) != tuple(rs[0].shape[1:]) for r in rs):
+        raise PbeError(f"pad_regions: every sample needs a [k_i, Hr, Wr] tensor with 1 <= k_i <= {K_max} and one Hr x Wr")
+    out = torch.zeros((len(rs), int(K_max), *rs[0].shape[1:]), dtype=torch.float64)
+    for i, r in enumerate(rs):
+        out[i, :r.shape[0]] = r
+    return out
+
+
 def resize_mask(mask: torch.Tensor, size, antialias: bool = True) -> torch.Tensor:
     """scripts/inference.py:332 ``Resize([h, w])(mask)``: bilinear, align_corners=False; the
     antialias default differs across torchvision versions -> exposed, default True.
@@ -51,9 +67,11 @@ def resize_mask(mask: torch.Tensor, size, antialias: bool = True) -> torch.Tenso
 @torch.no_grad()
 def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *, steps: int = 50, scale: float = 5.0,
             x_T: Optional[torch.Tensor] = None, post_eps: Optional[torch.Tensor] = None, sampler: str = "plms",
-            antialias: bool = True, timings: Optional[Dict[str, float]] = None, ref_weights=None) -> Dict[str, torch.Tensor]:
+            antialias: bool = True, timings: Optional[Dict[str, float]] = None, ref_weights=None, ref_regions=None) -> Dict[str, torch.Tensor]:
     """image [B,3,H,W] in [-1,1], mask [B,1,H,W] in {0,1} (1 = keep), ref [B,3,224,224] CLIP-normalised (or [B,K,3,224,224]: K
-    exemplars per sample, with ref_weights [B, K] their non-negative weights or None); everything on the model's GPU.  Returns {'image' [B,3,H,W] in [0,1], 'latent', 'c', 'z_inpaint', 'mask_lat'}."""
+    exemplars per sample, with ref_weights [B, K] their non-negative weights or None and ref_regions [B, K, Hr, Wr] >= 0 where each of
+    them applies - 1 = fully, 0 = not there; the latent grid and its halvings down to the coarsest attention level must divide
+    Hr x Wr - or None); everything on the model's GPU.  Returns {'image' [B,3,H,W] in [0,1], 'latent', 'c', 'z_inpaint', 'mask_lat'}."""
     from ldm.models.diffusion.ddim import DDIMSampler
     from ldm.models.diffusion.plms import PLMSSampler
     dev = model.device
@@ -75,7 +93,8 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     smp = (PLMSSampler if sampler == "plms" else DDIMSampler)(model)
     z0, _ = smp.sample(S=steps, batch_size=B, shape=list(z_inp.shape[1:]), conditioning=c, verbose=False,
                        unconditional_guidance_scale=scale, unconditional_conditioning=uc, eta=0.0, x_T=x_T,
-                       test_model_kwargs={"inpaint_image": z_inp, "inpaint_mask": m_lat}, conditioning_weights=ref_weights)
+                       test_model_kwargs={"inpaint_image": z_inp, "inpaint_mask": m_lat}, conditioning_weights=ref_weights,
+                       **({} if ref_regions is None else {"conditioning_regions": ref_regions}))
     if ev:
         ev[3].record()
     img = ops.image_post(model.decode_first_stage_nhwc(z0))                              # inference.py:346-347

@@ -10,6 +10,9 @@ sampler -> decode -> clamp) and the same output tree, running on the MI355X HIP 
 `--reference_path` may name several images (not in the reference): each becomes one context token of the sample.
 `--reference_weight w1 w2 ...` gives each of them a non-negative weight (default: all 1): its share of the cross-attention is
 proportional to w exp(score), so `2 1` equals naming the first image twice and `1 0` equals naming the first image alone.
+`--reference_region a.png b.png` gives each of them a grayscale image of where it applies (white = there, black = not there; grey
+in between): it is resized to the latent grid and every position of the picture attends to the exemplars whose region covers it,
+weighted by region x weight; a position that no region covers blends them by their weights alone.
 
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
@@ -54,6 +57,8 @@ def parse(argv=None):
                    "become the context tokens of the sample")
     p.add_argument("--reference_weight", type=float, nargs="+", default=None, help="(not in the reference) one non-negative weight per "
                    "--reference_path, default all 1; at least one must be positive")
+    p.add_argument("--reference_region", type=str, nargs="+", default=None, help="(not in the reference) one grayscale image per "
+                   "--reference_path: white where that exemplar applies")
     p.add_argument("--random_weights", action="store_true", help="name-seeded random weights instead of --ckpt")
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
@@ -64,7 +69,26 @@ def parse(argv=None):
             p.error(f"--reference_weight: {len(w)} weights for {len(refs)} --reference_path images")
         if any(not (x >= 0.0) or x == float("inf") for x in w) or not sum(w) > 0.0:
             p.error("--reference_weight: weights must be finite and >= 0 with a positive sum")
+    if opt.reference_region is not None:
+        refs = opt.reference_path if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
+        if len(opt.reference_region) != len(refs):
+            p.error(f"--reference_region: {len(opt.reference_region)} region images for {len(refs)} --reference_path images")
     return opt
+
+
+def load_regions(paths, size, device):
+    """One grayscale image per exemplar -> region maps fp32 [1, K, h, w] in [0, 1] on `device`: decoded to uint8, scaled to [0, 1],
+    resized on the device to the latent grid `size` (pipeline.resize_mask: antialiased bilinear, a convex combination, so the values
+    stay in [0, 1] up to the rounding of the fp32 filter sums; no threshold).  The clamp takes that rounding away: a sum of -1e-8
+    where the image is black would otherwise be refused as a negative region."""
+    import numpy as np
+    from PIL import Image
+    from pbe_amd import pipeline
+    maps = []
+    for path in paths:
+        u8 = torch.from_numpy(np.array(Image.open(path).convert("L"), dtype=np.uint8)).to(device)
+        maps.append(pipeline.resize_mask(u8.float()[None, None] / 255.0, size))
+    return torch.cat(maps, 1).clamp_(0.0, 1.0)
 
 
 def seed_everything(seed):
@@ -123,10 +147,14 @@ def main(argv=None):
         z_inpaint = model.get_first_stage_encoding(post, noise=None if post_eps is None else post_eps.to(device))
         test_model_kwargs["inpaint_image"] = z_inpaint
         test_model_kwargs["inpaint_mask"] = pipeline.resize_mask(test_model_kwargs["inpaint_mask"], z_inpaint.shape[-2:])
+        cr, extra = None, {}
+        if opt.reference_region is not None:                                           # one map per exemplar token, the same for every sample
+            cr = load_regions(opt.reference_region, z_inpaint.shape[-2:], device).expand(c.shape[0], -1, -1, -1).contiguous()
+            extra["conditioning_regions"] = cr
         shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
         samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=opt.n_samples, shape=shape, verbose=False,
                                     unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc, eta=opt.ddim_eta,
-                                    x_T=start_code, test_model_kwargs=test_model_kwargs, conditioning_weights=cw)
+                                    x_T=start_code, test_model_kwargs=test_model_kwargs, conditioning_weights=cw, **extra)
         xd = ops.image_post(model.decode_first_stage_nhwc(samples))                  # clamp((x+1)/2, 0, 1), still on the GPU
         if not opt.skip_save:
             for i in range(xd.shape[0]):
@@ -137,7 +165,8 @@ def main(argv=None):
             np.savez(opt.dump_tensors, x_T=(start_code if start_code is not None else torch.zeros(0)).float().cpu().numpy(),
                      post_eps=post_eps.numpy(), c=c.float().cpu().numpy(), z_inpaint=z_inpaint.float().cpu().numpy(),
                      mask64=test_model_kwargs["inpaint_mask"].float().cpu().numpy(), latent=samples.float().cpu().numpy(), image=x.numpy(),
-                     reference_weight=(cw if cw is not None else torch.ones(c.shape[:2])).double().numpy())
+                     reference_weight=(cw if cw is not None else torch.ones(c.shape[:2])).double().numpy(),
+                     **({} if cr is None else {"reference_region": cr.double().cpu().numpy()}))
     print(f"Your samples are ready and waiting for you here: \n{opt.outdir} \n \nEnjoy.")
     return x
 

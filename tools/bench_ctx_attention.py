@@ -17,7 +17,14 @@ of the composition.  The variants' results are compared first (rel-L2 of fused a
 times the exemplar-weight forms against their unweighted ones instead, arms alternating the same way: pbe_ctx_attention_w_f16 against
 pbe_ctx_attention_f16 at the shapes above, and pbe_attention_kbias_f16 against pbe_attention_f16 at the cross-attention shapes the
 existing-kernel route launches (a:8:8:256:4:160, a:8:8:64:4:160, a:8:8:4096:20:40).  Weights: exp2(randn), the last token of every
-second sample absent.  "spread" is (p90 - p10) / median of the unweighted arm."""
+second sample absent.  "spread" is (p90 - p10) / median of the unweighted arm.
+
+    python tools/bench_ctx_attention.py --regions [--out profiles/ctx_regions_timing.txt]
+
+times the row-weight form (pbe_ctx_attention_rw_f16, launch key xar) against the weighted form (pbe_ctx_attention_w_f16, xaw) at the
+shapes above, arms alternating the same way.  Table: exp2(randn) weights times uniform regions zeroed below 0.6 (about 60 % of the
+entries -inf, rows without a token fall back to the weights), one [B, tokens, Nk] table per shape: it adds 4 Nk bytes per row to the
+about 6 C the kernel moves.  "spread" is (p90 - p10) / median of the weighted arm."""
 import argparse
 import os
 import sys
@@ -137,10 +144,39 @@ def weights_table(a, dev):
     return "\n".join(lines) + "\n"
 
 
+def regions_table(a, dev):
+    cell = lambda q: f"{q[1]:8.1f} [{q[0]:7.1f} .. {q[2]:7.1f}]"      # noqa: E731
+    lines = [f"# row-weight form vs the weighted form; device: {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}); "
+             f"B = {B} samples, {H} heads",
+             f"# per launch, microseconds: median [p10 .. p90] over {a.reps} repetitions of {a.inner} back-to-back launches, arms alternating",
+             f"# pbe_ctx_attention_rw_f16 (xar) vs pbe_ctx_attention_w_f16 (xaw)\n# {'M':>6} {'C':>5} {'Nk':>3} | {'xaw':>28} | {'xar':>28} | xar/xaw  spread"]
+    g = torch.Generator().manual_seed(0)
+    for M, C in SHAPES:
+        nbuf = max(2, min(16, -(-(512 << 20) // (2 * M * C))))
+        xs = [(torch.randn(M, C, generator=g) * 0.8 + 0.1).half().to(dev) for _ in range(nbuf)]
+        sts = [ops.row_stats(x) for x in xs]
+        for Nk in TOKENS:
+            oc, _ = build(M, C, Nk, dev, g)
+            lw = _log2w(Nk, dev, g)
+            ow = ops.CtxOperands(oc.kq, oc.colsum, oc.kbias, oc.vo, oc.bias, oc.H, oc.Nk, lw)
+            r = torch.rand(B, M // B, Nk, generator=g)
+            e = torch.where(r < 0.6, torch.zeros_like(r), r) * torch.exp2(lw.cpu())[:, None, :]
+            e = torch.where(e.sum(-1, keepdim=True) <= 0, torch.exp2(lw.cpu())[:, None, :].expand_as(e), e)
+            orw = oc.with_row_weights(torch.log2(e).float().to(dev).contiguous())
+            q = _time({"w": lambda i: ops.ctx_attention(xs[i], ow, sts[i], 1e-5, tokens=M // B),
+                       "rw": lambda i: ops.ctx_attention(xs[i], orw, sts[i], 1e-5, tokens=M // B)}, a, nbuf)
+            lines.append(f"  {M:6d} {C:5d} {Nk:3d} | {cell(q['w']):>28} | {cell(q['rw']):>28} | {q['rw'][1] / q['w'][1]:7.3f}  "
+                         f"{(q['w'][2] - q['w'][0]) / q['w'][1]:6.2f}")
+            print(lines[-1], flush=True)
+        del xs, sts
+    return "\n".join(lines) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--weights", action="store_true", help="time the exemplar-weight forms against the unweighted ones instead")
+    ap.add_argument("--regions", action="store_true", help="time the row-weight form (xar) against the weighted form (xaw) instead")
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -148,8 +184,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_ctx_attention.py needs an MI355X: a timing taken anywhere else says nothing")
     dev = torch.device("cuda:0")
-    if a.weights:
-        text = weights_table(a, dev)
+    if a.weights or a.regions:
+        text = regions_table(a, dev) if a.regions else weights_table(a, dev)
         print(text)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
