@@ -1434,7 +1434,8 @@ static constexpr TileCfg kTiles[] = {
     {256, 320, 2, 4, 2, 1, 1.05, 0.80, 0, F_DENSE | F_CONV, 8},                     // 7: 144 KiB: N = 320 / 640 / 960 / 1280 without column padding (142 FLOP per staged byte)
     {128, 320, 2, 4, 2, 1, 0.96, 0.95, 0, F_DENSE | F_CONV | F_EX | F_F8, 8},       // 8: 112 KiB: same, half the rows: fills the chip when M / 256 < 256 tiles
     {128, 160, 2, 2, 2, 2, 0.90, 0.97, 0, F_DENSE | F_CONV | F_EX | F_F8, 9},       // 9:  72 KiB, 4 waves: two workgroups per CU overlap each other's prologue / epilogue
-    // halo-resident 3x3 conv tiles (stride 1, pad 1, image width 8 .. 128 = tile width): only the weights stream per k-tile
+    // halo-resident 3x3 conv tiles (stride 1, pad 1, image width 8 .. 128 = tile width, and the tile's bm pixels are whole rows of one
+    // image or a whole number of images - halo_rows(); any other map runs the gather tiles): only the weights stream per k-tile
     {256, 160, 4, 2, 3, 1, 1.40, 1.40, 392, F_HALO, 9},                   // 10: 160 KiB: 256 pixels (4 rows at 64x64) x 160 channels, 8 waves, ping-pong
     {128, 160, 4, 2, 3, 1, 1.20, 1.20, 264, F_HALO, 9},                   // 11: 128 KiB: 128 pixels x 160 channels
     {128, 320, 2, 4, 2, 1, 1.25, 1.25, 264, F_HALO, 9},                   // 12: 149 KiB: 128 pixels x 320 channels
@@ -1503,9 +1504,9 @@ static int halo_rows(const IGemmP& p, int mode, int bm, int hpa) {
     const int W = p.Wd, H = p.H;
     if (W < 8 || W > 128 || (W & (W - 1)) || bm % W || (p.M % bm)) return 0;
     const int th = bm / W < H ? bm / W : H;
-    if (H % th) return 0;
+    if (H % th || bm % (th * W)) return 0;                        // a tile is whole rows of one image or a whole number of images:
     const int nsub = bm / (th * W);                               // whole images per tile when the image is smaller than the tile
-    if (nsub > 1 && th != H) return 0;
+    if (nsub > 1 && th != H) return 0;                            // the kernel derives image and row of a pixel from nsub * th * W == bm
     if (nsub * ((th + 2) * (W + 1) + 1) > hpa) return 0;       // halo rows: row stride W + 1 (shared zero column) + 1
     return th;
 }
