@@ -361,6 +361,30 @@ int pbe_ctx_attention_w_f16(const pbe_ctx_attn_desc* d, const float* log2w, int6
  * Required: log2rw non-null and 4-byte aligned, rw_rs >= Nk, rw_bs >= 0; additive to the ABI (same descriptor). */
 int pbe_ctx_attention_rw_f16(const pbe_ctx_attn_desc* d, const float* log2rw, int64_t rw_bs, int64_t rw_rs, pbe_stream_t stream);
 
+/* pbe_ctx_attention_map_f16 — any of the three launches above with the ATTRIBUTION MAP as a side output: the softmax weights of
+ * attention.py:207-230 (`attn = sim.softmax(dim=-1)`), which the reference discards after `einsum('b i j, b j d -> b i d', attn, v)`,
+ * averaged over the heads.  amap fp32, element (b, t, j) at amap[b*am_bs + t*am_rs + j] for t < tokens, j < Nk, takes
+ *   (1 / H) * sum_{h = 0 .. H-1} p[b, t, h, j]
+ * where p are the fp16 weights the second product really multiplies, summed in that fixed order in fp32 and multiplied by the fp32
+ * value 1.0f / H: the share of cross-attention context token j received at row t.  accumulate == 0 stores it; accumulate != 0 adds it
+ * to what is there with one fp32 add (a plain read-modify-write by the one thread that owns the element - no atomics: launches on one
+ * stream accumulate deterministically).  log2w / w_bs as pbe_ctx_attention_w_f16 or NULL, log2rw / rw_bs / rw_rs as
+ * pbe_ctx_attention_rw_f16 or NULL, not both non-NULL; both NULL is pbe_ctx_attention_f16.  Y and row_stats_out carry the bits of the
+ * corresponding entry without the map.  Rows past a sample's last token are not written; nothing outside t < tokens, j < Nk of a
+ * sample's map is touched (rows may be padded: am_rs >= Nk).
+ * Required: amap non-null and 4-byte aligned, am_rs >= Nk, am_bs >= 0; additive to the ABI (same descriptor). */
+int pbe_ctx_attention_map_f16(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, const float* log2rw, int64_t rw_bs,
+                              int64_t rw_rs, float* amap, int64_t am_bs, int64_t am_rs, int32_t accumulate, pbe_stream_t stream);
+
+/* pbe_ctx_map_gather_f32 — a level's attribution accumulator acc fp32 [B, h*w, K] (rows in NHWC order t = y*w + x, as
+ * pbe_ctx_attention_map_f16 fills it) onto a picture grid: out fp32 [B, K, fy*h, fx*w],
+ *   out[b, j, y, x] (+)= s * (acc[b, (y / fy) * w + (x / fx), j] / div)
+ * i.e. a nearest upsample by the integer factors (fy, fx) and the transposition to the [B, K, H, W] layout region maps use.  div > 0
+ * is the number of launches that accumulated into acc (an IEEE division: n launches that each added exactly 1 give exactly 1; 1 for
+ * none), s the weight of the level in the average.  accumulate == 0 stores, != 0 adds; every step is rounded on its own. */
+int pbe_ctx_map_gather_f32(const float* acc, float* out, int32_t B, int32_t K, int32_t h, int32_t w, int32_t fy, int32_t fx, float s,
+                           float div, int32_t accumulate, pbe_stream_t stream);
+
 /* pbe_softmax_rows_f16 — Y[r,:] = softmax(scale * X[r,:]) over rows of `cols` fp16 (VAE mid attention,
  * model.py:193-195: one head, d = 512, N = 4096, scores kept in HBM once per image). */
 int pbe_softmax_rows_f16(const void* X, void* Y, int64_t rows, int32_t cols, int64_t ldx, int64_t ldy,

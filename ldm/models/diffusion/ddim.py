@@ -10,7 +10,7 @@ import torch
 
 from pbe_amd import ops
 from pbe_amd.lib import PbeError
-from ldm.models.diffusion.plms import PLMSSampler, guidance_context, guidance_regions, guidance_weights, inpaint_kwargs
+from ldm.models.diffusion.plms import PLMSSampler, guidance_context, guidance_maps, guidance_regions, guidance_weights, inpaint_kwargs
 
 
 class DDIMSampler(PLMSSampler):
@@ -26,9 +26,10 @@ class DDIMSampler(PLMSSampler):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
                eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, disable_tqdm=True,
-               conditioning_weights=None, conditioning_regions=None, **kwargs):
+               conditioning_weights=None, conditioning_regions=None, conditioning_maps=None, **kwargs):
         """conditioning_weights: per-sample exemplar weights [batch_size, K] as in PLMSSampler.sample, or None; conditioning_regions:
-        region maps [batch_size, K, Hr, Wr] as there, or None."""
+        region maps [batch_size, K, Hr, Wr] as there, or None; conditioning_maps: an attention.ContextMaps that collects the run's
+        attribution maps (the conditional half of every U-Net call) as there, or None."""
         if conditioning is None:
             raise PbeError("DDIMSampler.sample: conditioning is required")
         if quantize_x0 or score_corrector is not None or noise_dropout != 0.:
@@ -40,12 +41,13 @@ class DDIMSampler(PLMSSampler):
         return self.ddim_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0, temperature=temperature,
-                                  conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions, **kwargs)
+                                  conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
+                                  conditioning_maps=conditioning_maps, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, timesteps=None, mask=None, x0=None, temperature=1., conditioning_weights=None,
-                      conditioning_regions=None, **kwargs):
+                      conditioning_regions=None, conditioning_maps=None, **kwargs):
         device = self.model.betas.device
         if self.require_gpu and device.type != "cuda":
             raise PbeError("DDIMSampler: the model must live on an MI355X; there is no CPU path")
@@ -66,6 +68,7 @@ class DDIMSampler(PLMSSampler):
         dup = 2 if guided else 1
         ctx_w = guidance_weights(conditioning_weights, cond, b, guided)
         ctx_r = guidance_regions(conditioning_regions, cond, b, guided)
+        ctx_m = guidance_maps(conditioning_maps, cond, b, device)
         time_range = np.flip(self._schedule_subset(timesteps))
         total = time_range.shape[0]
         if mask is not None:
@@ -75,7 +78,7 @@ class DDIMSampler(PLMSSampler):
             index = total - i - 1
             if mask is not None:
                 img = self._blend_known(img, x0, mask, step)
-            eps = self._eps(img, step, ctx, z_inp, msk, dup, ctx_w, ctx_r)
+            eps = self._eps(img, step, ctx, z_inp, msk, dup, ctx_w, ctx_r, ctx_m)
             coef = self._coef(index, (1.0,))
             sigma = float(self.ddim_sigmas[index])
             if sigma != 0.0:                                  # dir_xt = sqrt(1 - a_prev - sigma_t^2) e_t (ddim.py:234)

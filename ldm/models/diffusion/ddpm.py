@@ -63,12 +63,15 @@ class DiffusionWrapper(nn.Module):
             raise PbeError(f"DiffusionWrapper: conditioning_key={conditioning_key!r}; Paint-by-Example uses 'crossattn' (configs/v1.yaml:15)")
         self.conditioning_key = conditioning_key
 
-    def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, context_weights=None, context_regions=None):
+    def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, context_weights=None, context_regions=None, context_maps=None):
         """context_weights: exemplar weights [B, K] over the K tokens of the (concatenated) cross-attention context, or None;
-        context_regions: region maps [B, K, Hr, Wr] over the same tokens, or None."""
+        context_regions: region maps [B, K, Hr, Wr] over the same tokens, or None; context_maps: an attention.ContextMaps that collects
+        the attribution maps of the call (UNetModel.forward_nhwc), or None."""
         if self.conditioning_key is None:
             raise PbeError("DiffusionWrapper: unconditional U-Net is not on the Paint-by-Example path")
         cc = c_crossattn[0] if len(c_crossattn) == 1 else torch.cat(c_crossattn, 1)
+        if context_maps is not None:
+            return self.diffusion_model(x, t, context=cc, context_weights=context_weights, context_regions=context_regions, context_maps=context_maps)
         if context_regions is not None:
             return self.diffusion_model(x, t, context=cc, context_weights=context_weights, context_regions=context_regions)
         if context_weights is None:
@@ -244,15 +247,18 @@ class LatentDiffusion(DDPM):
         return img
 
     # ---- denoiser ----------------------------------------------------------------------------------
-    def apply_model(self, x_noisy, t, cond, return_ids=False, context_weights=None, context_regions=None):
+    def apply_model(self, x_noisy, t, cond, return_ids=False, context_weights=None, context_regions=None, context_maps=None):
         """context_weights: per-sample exemplar weights [B, K] (>= 0, positive sum; 0 = token absent: a padded ragged batch) or None.
-        context_regions: per-sample, per-token region maps [B, K, Hr, Wr] >= 0 (regional exemplars) or None."""
+        context_regions: per-sample, per-token region maps [B, K, Hr, Wr] >= 0 (regional exemplars) or None.
+        context_maps: an attention.ContextMaps that collects the attribution maps of the call, or None."""
         if not isinstance(cond, dict):
             cond = {"c_crossattn": cond if isinstance(cond, list) else [cond]}
         if context_weights is not None:
             cond = dict(cond, context_weights=context_weights)
         if context_regions is not None:
             cond = dict(cond, context_regions=context_regions)
+        if context_maps is not None:
+            cond = dict(cond, context_maps=context_maps)
         out = self.model(x_noisy, t, **cond)
         return out[0] if isinstance(out, tuple) and not return_ids else out
 

@@ -90,6 +90,16 @@ def guidance_regions(regions, cond, b, guided):
     return torch.cat((torch.ones_like(r), r)).contiguous() if guided else r.contiguous()
 
 
+def guidance_maps(maps, cond, b, device):
+    """conditioning_maps (an attention.ContextMaps or None) bound to the run: b samples x cond's K tokens.  In a guidance batch
+    cat([uc, c]) those are the LAST b samples - the conditional half; the unconditional half (one token repeated) is not collected."""
+    if maps is None:
+        return None
+    if not all(hasattr(maps, a) for a in ("bind", "level", "note", "result")):
+        raise PbeError("sampler: conditioning_maps must be an ldm.modules.attention.ContextMaps")
+    return maps.bind(b, cond.shape[1], device)
+
+
 class PLMSSampler(object):
     def __init__(self, model, schedule="linear", **kwargs):
         self.model = model
@@ -124,11 +134,15 @@ class PLMSSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
                eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, conditioning_weights=None,
-               conditioning_regions=None, **kwargs):
+               conditioning_regions=None, conditioning_maps=None, **kwargs):
         """conditioning_weights: per-sample exemplar weights [batch_size, K] over conditioning's K tokens (>= 0, positive sum per sample;
         0 = token absent, so a ragged batch is padded to one K), or None: every token counts once.
         conditioning_regions: per-sample, per-token region maps [batch_size, K, Hr, Wr] >= 0 (regional exemplars: where each token
-        applies; every transformer level's grid must divide Hr x Wr), or None: every token applies everywhere."""
+        applies; every transformer level's grid must divide Hr x Wr), or None: every token applies everywhere.
+        conditioning_maps: an attention.ContextMaps or None.  It collects the attribution maps of the run - the share of cross-attention
+        each conditioning token received at each position, from every U-Net call of the run (the probe call included); under guidance
+        only the CONDITIONAL half is collected.  With it every level runs the fused cross-attention kernel: with regions the samples are
+        those of the run without it bit for bit, without regions those of a run whose blocks have ctx_fused_max_width = 1280."""
         if conditioning is None:
             raise PbeError("PLMSSampler.sample: conditioning is required")
         if conditioning.shape[0] != batch_size:
@@ -142,10 +156,11 @@ class PLMSSampler(object):
         return self.plms_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
-                                  conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions, **kwargs)
+                                  conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
+                                  conditioning_maps=conditioning_maps, **kwargs)
 
     # ---- one U-Net evaluation with guidance (plms.py:181-195) -----------------------------------
-    def _eps(self, x, step, ctx, z_inp, msk, dup, ctx_w=None, ctx_r=None):
+    def _eps(self, x, step, ctx, z_inp, msk, dup, ctx_w=None, ctx_r=None, ctx_m=None):
         b = x.shape[0]
         t = torch.full((dup * b,), int(step), device=x.device, dtype=torch.int64)
         unet = self.model.model.diffusion_model
@@ -155,9 +170,13 @@ class PLMSSampler(object):
         if (graphs_enabled(dup * b) if self.use_graph is None else self.use_graph) and x.is_cuda:      # launch-bound regime: one HIP graph per call
             if self._graphed is None or self._graphed.unet is not unet:
                 self._graphed = GraphedUNet(unet)
+            if ctx_m is not None:
+                return self._graphed(x9, t, ctx, paired, ctx_w, ctx_r, ctx_m)
             if ctx_r is not None:
                 return self._graphed(x9, t, ctx, paired, ctx_w, ctx_r)
             return self._graphed(x9, t, ctx, paired) if ctx_w is None else self._graphed(x9, t, ctx, paired, ctx_w)
+        if ctx_m is not None:                                                     # the collector covers the last b samples: the conditional half
+            return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step), context_weights=ctx_w, context_regions=ctx_r, context_maps=ctx_m)
         if ctx_r is not None:
             return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step), context_weights=ctx_w, context_regions=ctx_r)
         if ctx_w is not None:                                                     # (without weights: exactly the call made before they existed)
@@ -185,7 +204,7 @@ class PLMSSampler(object):
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, callback=None, timesteps=None, img_callback=None, log_every_t=100,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, mask=None, x0=None, conditioning_weights=None,
-                      conditioning_regions=None, **kwargs):
+                      conditioning_regions=None, conditioning_maps=None, **kwargs):
         device = self.model.betas.device
         if self.require_gpu and device.type != "cuda":
             raise PbeError("PLMSSampler: the model must live on an MI355X (model.to('cuda')); there is no CPU path")
@@ -203,6 +222,7 @@ class PLMSSampler(object):
         dup = 2 if guided else 1
         ctx_w = guidance_weights(conditioning_weights, cond, b, guided)
         ctx_r = guidance_regions(conditioning_regions, cond, b, guided)
+        ctx_m = guidance_maps(conditioning_maps, cond, b, device)
         scale = float(unconditional_guidance_scale)
 
         time_range = np.flip(self._schedule_subset(timesteps))
@@ -216,11 +236,11 @@ class PLMSSampler(object):
             step_next = time_range[min(i + 1, total - 1)]
             if mask is not None:
                 img = self._blend_known(img, x0, mask, step)
-            eps = self._eps(img, step, ctx, z_inp, msk, dup, ctx_w, ctx_r)
+            eps = self._eps(img, step, ctx, z_inp, msk, dup, ctx_w, ctx_r, ctx_m)
             if len(old) == 0:
                 # pseudo improved Euler (plms.py:230-235): probe x_prev with e_t, re-evaluate at t_next, average
                 x_probe, _, e_t = ops.plms_update(eps, dup, scale, img, [], self._coef(index, _AB[0]), want_pred=False)
-                eps2 = self._eps(x_probe, step_next, ctx, z_inp, msk, dup, ctx_w, ctx_r)
+                eps2 = self._eps(x_probe, step_next, ctx, z_inp, msk, dup, ctx_w, ctx_r, ctx_m)
                 # e' = (e_t + e_next)/2 : c0 weights the fresh eps (= e_next), history slot 1 = e_t
                 img, pred_x0, _ = ops.plms_update(eps2, dup, scale, img, [e_t], self._coef(index, (0.5, 0.5)), want_e_t=False)
             else:

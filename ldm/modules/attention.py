@@ -17,6 +17,8 @@ ldm/modules/attention.py in zhanwenchen/pbe (GEGLU :38-45, FeedForward :48-65, C
     DESIGN.md section 4.11); contexts longer than that kernel takes run q / attention / to_out,
   * exemplar tokens may carry a weight per sample (``context_weights``) and a map of where each applies (``context_regions``:
     regional exemplars, a weight per query row - pbe_ctx_attention_rw_f16 on the same folded operands),
+  * the softmax weights of that launch can be collected as attribution maps (``ContextMaps``: which exemplar each position attended
+    to - pbe_ctx_attention_map_f16, the same launch with a side output),
   * bias, residual and the row-broadcast adds are GEMM epilogues.
 """
 from types import SimpleNamespace
@@ -343,6 +345,101 @@ def prepare_row_weights(x_shape, context, row_weights):
     return torch.log2(e).to(torch.float32).to(context.device).contiguous()
 
 
+class ContextMaps:
+    """Collector of exemplar ATTRIBUTION MAPS: per sample and context token, the share of cross-attention that token received at each
+    position - the softmax weights of attention.py:207-230, averaged over the heads (in the kernel: pbe_ctx_attention_map_f16), the
+    transformer blocks of a level, the U-Net calls of a run and the levels.  One zero-initialised fp32 accumulator [B, h*w, K] per level
+    grid, into which every multi-token cross-attention launch of that level adds its head-mean weights, and a launch count per level.
+
+    level(h, w) allocates the accumulator at the first (eager) call, so a graph capture finds it in place; launches captured into a graph
+    are counted when the graph is replayed (begin_tape / end_tape / replayed - pbe_amd.graph.GraphedUNet).  The collector covers the
+    LAST B samples of the batch it is handed with: all of it, or the conditional half of a guidance batch cat([uc, c]).  A one-token
+    context launches nothing: its maps are identically 1 (the softmax over one key).
+
+    With a collector a K > 1 context always takes the fused kernel (as regional exemplars do), so WITHOUT regions the levels wider than
+    BasicTransformerBlock.ctx_fused_max_width change route: the result then equals, bit for bit, the collector-less run with
+    ctx_fused_max_width = 1280, and the default collector-less run within the samplers' tolerance.  With regions the route is the
+    same with and without a collector, and so are the bits."""
+
+    def __init__(self):
+        self.B = self.K = self.device = None
+        self._levels, self._counts, self._tape = {}, {}, None
+
+    def bind(self, B, K, device):
+        """Fix the collector's shape (the first user does; a second user must agree)."""
+        B, K, device = int(B), int(K), torch.device(device)
+        if self.B is None:
+            self.B, self.K, self.device = B, K, device
+        elif (self.B, self.K, self.device) != (B, K, device):
+            raise PbeError(f"ContextMaps: collecting for {self.B} samples x {self.K} tokens on {self.device}, handed {B} x {K} on {device}")
+        return self
+
+    def level(self, h, w):
+        """The accumulator fp32 [B, h*w, K] of the h x w level (zeros at first use)."""
+        if self.B is None:
+            raise PbeError("ContextMaps: not bound to a batch yet (bind(B, K, device))")
+        k = (int(h), int(w))
+        t = self._levels.get(k)
+        if t is None and self.K > 1:
+            t = self._levels[k] = torch.zeros((self.B, k[0] * k[1], self.K), dtype=torch.float32, device=self.device)
+            self._counts.setdefault(k, 0)
+        return t
+
+    def note(self, h, w, launches):
+        """`launches` launches were issued (or, inside begin_tape / end_tape, captured) that add to level (h, w)."""
+        k = (int(h), int(w))
+        tgt = self._counts if self._tape is None else self._tape
+        tgt[k] = tgt.get(k, 0) + int(launches)
+        self._counts.setdefault(k, 0)
+
+    def begin_tape(self):
+        self._tape = {}
+
+    def end_tape(self):
+        t, self._tape = self._tape, None
+        return t
+
+    def replayed(self, tape):
+        for k, n in tape.items():
+            self._counts[k] = self._counts.get(k, 0) + n
+
+    def counts(self):
+        """{(h, w): launches that have added to the level}."""
+        return dict(self._counts)
+
+    def grids(self):
+        return sorted(self._counts, reverse=True)
+
+    def per_level(self):
+        """{(h, w): fp32 [B, K, h, w]}: each level's accumulator divided by its launch count, unmerged (K = 1: ones)."""
+        out = {}
+        for k in self.grids():
+            if self.K == 1:
+                out[k] = torch.ones((self.B, 1, *k), dtype=torch.float32, device=self.device)
+            elif self._counts[k] > 0:
+                out[k] = ops.ctx_map_gather(self._levels[k], k, div=float(self._counts[k]))
+        return out
+
+    def result(self, grid):
+        """fp32 [B, K, Hl, Wl] on grid = (Hl, Wl) (the latent grid: every level's grid must divide it): each level's accumulator divided
+        by its launch count, gathered to the grid (nearest; pbe_ctx_map_gather_f32) and the levels averaged with equal weight.  K = 1: ones."""
+        if self.B is None:
+            raise PbeError("ContextMaps.result: nothing was collected")
+        Hl, Wl = int(grid[0]), int(grid[1])
+        if self.K == 1:
+            return torch.ones((self.B, 1, Hl, Wl), dtype=torch.float32, device=self.device)
+        live = [k for k in self.grids() if self._counts[k] > 0]
+        if not live:
+            raise PbeError("ContextMaps.result: nothing was collected")
+        for h, w in live:
+            if Hl % h or Wl % w:
+                raise PbeError(f"ContextMaps.result: the {Hl} x {Wl} grid is not a whole multiple of the {h} x {w} level")
+        out = torch.empty((self.B, self.K, Hl, Wl), dtype=torch.float32, device=self.device)
+        for i, k in enumerate(live):
+            ops.ctx_map_gather(self._levels[k], k, 1.0 / len(live), out=out, accumulate=i > 0, div=float(self._counts[k]))
+        return out
+
+
 class RegionalVectors:
     """What SpatialTransformer.context_vectors returns for a context WITH regions: the per-block list and the context's
     ContextRegions.  The level is known only where the grid is: run / run_paired resolve it there (SpatialTransformer._levelled)."""
@@ -424,17 +521,18 @@ class BasicTransformerBlock(HipModule):
         return K <= min(self.ctx_fused_max_tokens, ops.CTX_MAX_TOKENS) and a2.heads * K <= ops.CTX_MAX_HJ and Cq % 64 == 0 and \
             64 <= Cq <= min(self.ctx_fused_max_width, ops.CTX_MAX_C)
 
-    def _ctx_regional(self, K):
-        """Regions need the fused kernel (the only per-row form): raise PbeError naming the limit a K-token context breaks."""
+    def _ctx_regional(self, K, what="regional exemplars"):
+        """Regions (and attribution maps: `what`) need the fused kernel - the only per-row form, and the only one whose softmax weights
+        can be brought out: raise PbeError naming the limit a K-token context breaks."""
         a2, Cq = self.attn2, self.attn2.to_q.weight.shape[1]
         if K > ops.CTX_MAX_TOKENS:
-            raise PbeError(f"BasicTransformerBlock: regional exemplars take at most {ops.CTX_MAX_TOKENS} context tokens, got {K}")
+            raise PbeError(f"BasicTransformerBlock: {what} take at most {ops.CTX_MAX_TOKENS} context tokens, got {K}")
         if a2.heads * K > ops.CTX_MAX_HJ:
-            raise PbeError(f"BasicTransformerBlock: regional exemplars need heads * tokens <= {ops.CTX_MAX_HJ}, got {a2.heads} * {K}")
+            raise PbeError(f"BasicTransformerBlock: {what} need heads * tokens <= {ops.CTX_MAX_HJ}, got {a2.heads} * {K}")
         if Cq % 64 or not 64 <= Cq <= ops.CTX_MAX_C:
-            raise PbeError(f"BasicTransformerBlock: regional exemplars need a width that is a multiple of 64 in 64..{ops.CTX_MAX_C}, got {Cq}")
+            raise PbeError(f"BasicTransformerBlock: {what} need a width that is a multiple of 64 in 64..{ops.CTX_MAX_C}, got {Cq}")
 
-    def context_operands(self, context, weights=None, regional=False):
+    def context_operands(self, context, weights=None, regional=False, maps=False):
         """What run() needs of a context, computed once per context.  weights: exemplar weights [B, K] or a ContextWeights
         (prepare_context_weights: validated there), None = every token counts once; their log2 rides beside the operands (CtxOperands.log2w /
         ContextKV.log2w), which do not depend on it.  [B, 1, Dc]: attn2's constant to_out(to_v(context)) as [B, C]
@@ -443,7 +541,8 @@ class BasicTransformerBlock(HipModule):
         Vo = Wo_h v_h, colsum = row sums of the fp16 Kq) - or, beyond that kernel's dispatch bound (K > 16, heads * K > 128, C > 640), a ContextKV
         for the q projection / pbe_attention_f16 / to_out route.  All products are pbe_gemm_f16 launches.  regional: the caller will hand
         the operands a per-row table (CtxOperands.with_row_weights), so K > 1 always takes the fused kernel, at every width it accepts,
-        and a context beyond its limits is refused."""
+        and a context beyond its limits is refused.  maps: the caller will hand the operands an attribution-map target
+        (CtxOperands.with_map; ContextMaps) - the same route as regional, for the same reason: only the fused kernel has the form."""
         c = _tokens(context)
         if c.dim() != 3:
             raise PbeError(f"BasicTransformerBlock: context must be [B, K, Dc], got {tuple(c.shape)}")
@@ -458,8 +557,10 @@ class BasicTransformerBlock(HipModule):
         inner = a2.heads * a2.dim_head
         if regional:
             self._ctx_regional(K)
+        elif maps:
+            self._ctx_regional(K, "attribution maps")
         k = ops.gemm(c.view(B * K, -1), p2.wk)                                    # [B*K, inner]
-        if not regional and not self._ctx_fused(K):
+        if not (regional or maps) and not self._ctx_fused(K):
             npad = (K + 7) // 8 * 8
             vt = torch.zeros((B, inner, npad), dtype=torch.float16, device=c.device)
             ops.gemm(p2.wv.unsqueeze(0).expand(B, -1, -1), c, out=vt[:, :, :K] if npad != K else vt)
@@ -495,7 +596,22 @@ class BasicTransformerBlock(HipModule):
         p, a2, p2 = self._pack_multi(), self.attn2, self.attn2.pk()
         want = False if not folded else (stats_out if stats_out is not None else True)
         if isinstance(ctx, ops.CtxOperands):
-            return ops.ctx_attention(x1, ctx, st2 if st2 is not None else ops.row_stats(x1), p.eps2, tokens=N, out=out, row_stats=want)
+            st = st2 if st2 is not None else ops.row_stats(x1)
+            ranges = ctx.map_ranges()
+            if len(ranges) == 1:
+                return ops.ctx_attention(x1, ctx, st, p.eps2, tokens=N, out=out, row_stats=want)
+            # an attribution map for SOME of the samples (the conditional half of a guidance batch): one launch per range.  Row tiles never
+            # straddle samples and a workgroup sees its own sample only, so Y and the statistics are those of the one launch, bit for bit.
+            M = x1.shape[0]
+            y = out if out is not None else torch.empty_like(x1)
+            rs = None
+            if want is not False:
+                rs = want if isinstance(want, ops.RowStats) else ops.RowStats(torch.empty((1, M, 2), dtype=torch.float32, device=x1.device), 1, M)
+            for b0, b1 in ranges:
+                r0, r1 = b0 * N, b1 * N
+                ops.ctx_attention(x1[r0:r1], ctx.rows(b0, b1), ops.RowStats(st.buf, st.parts, st.ld, st.row0 + r0), p.eps2, tokens=N, out=y[r0:r1],
+                                  row_stats=False if rs is None else ops.RowStats(rs.buf, 1, rs.ld, rs.row0 + r0))
+            return y, (None if rs is None else ops.RowStats(rs.buf, 1, rs.ld, rs.row0))
         inner = a2.heads * a2.dim_head
         if folded:
             q = ops.gemm(x1, p.wq2, p.c2q2, ln=(st2 if st2 is not None else ops.row_stats(x1), p.c1q2, p.eps2))
@@ -611,8 +727,9 @@ class BasicTransformerBlock(HipModule):
             return self.ff.run_f8(*ops.layernorm_f8(x1, p.g3, p.b3, p.eps3), resid=x1)
         return self.ff.run(ops.layernorm(x1, p.g3, p.b3, p.eps3), resid=x1)
 
-    def forward(self, x, context=None, context_weights=None, context_row_weights=None):
+    def forward(self, x, context=None, context_weights=None, context_row_weights=None, attn_map=None):
         """x [B, N, C], context [B, K, Dc] with K >= 1 tokens per sample (context_weights [B, K] or None) -> [B, N, C].
+        attn_map: (fp32 [B, N, K], accumulate) - the block's head-mean cross-attention weights are stored / added there (K > 1).
         context_row_weights: the already-levelled regional form, effective weights e [B, N, K] >= 0 of token j at query row t (they
         hold the exemplar weights already, so context_weights must be None with them)."""
         x = _tokens(x)
@@ -626,8 +743,11 @@ class BasicTransformerBlock(HipModule):
             o = self.context_operands(context, None, regional=True)
             if isinstance(o, ops.CtxOperands):               # (K = 1: validated, otherwise ignored - the softmax over one key is 1)
                 o = o.with_row_weights(table)
-            return self.run(x.view(B * N, Cc), B, N, o).view(B, N, Cc)
-        return self.run(x.view(B * N, Cc), B, N, self.context_operands(context, context_weights)).view(B, N, Cc)
+        else:
+            o = self.context_operands(context, context_weights, maps=attn_map is not None)
+        if attn_map is not None and isinstance(o, ops.CtxOperands):
+            o = o.with_map(attn_map[0], attn_map[1])
+        return self.run(x.view(B * N, Cc), B, N, o).view(B, N, Cc)
 
 
 class SpatialTransformer(HipModule):
@@ -648,46 +768,60 @@ class SpatialTransformer(HipModule):
                                wi=ops.pack_linear(self.proj_in.weight), bi=f32(self.proj_in.bias),
                                wo=ops.pack_linear(self.proj_out.weight), bo=f32(self.proj_out.bias))
 
-    def context_vectors(self, context, context_weights=None, context_regions=None):
+    def context_vectors(self, context, context_weights=None, context_regions=None, maps=False):
         """Per block, what its run() needs of context [B, K, Dc]: the [B, C] constant for K = 1, the multi-token operands for K > 1
         (BasicTransformerBlock.context_operands).  context_weights: exemplar weights [B, K] (or a ContextWeights), validated once here.
         context_regions: region maps [B, K, Hr, Wr] (or a ContextRegions), validated once here; with them the result is a
-        RegionalVectors (the list and the regions), which run() / run_paired() resolve at their grid."""
+        RegionalVectors (the list and the regions), which run() / run_paired() resolve at their grid.  maps: run() / run_paired() will
+        be handed a ContextMaps, so a K > 1 context takes the fused kernel at every width (BasicTransformerBlock.context_operands)."""
         cw = prepare_context_weights(context, context_weights)
         cr = prepare_context_regions(context, context_regions, cw)
-        vecs = [blk.context_operands(context, cw, regional=cr is not None) for blk in self.transformer_blocks]
+        vecs = [blk.context_operands(context, cw, regional=cr is not None, maps=bool(maps)) for blk in self.transformer_blocks]
         return vecs if cr is None else RegionalVectors(vecs, cr)
 
     @staticmethod
-    def _levelled(ctx_vecs, H, W):
+    def _levelled(ctx_vecs, H, W, maps=None):
         """The per-block list of ctx_vecs; a RegionalVectors gets the regions' table of the H x W grid on every multi-token block's
-        operands (one-token constants: unchanged)."""
-        if not isinstance(ctx_vecs, RegionalVectors):
-            return ctx_vecs
-        vecs = ctx_vecs.vecs
-        if not any(isinstance(cv, ops.CtxOperands) for cv in vecs):      # (K = 1: validated, otherwise ignored)
+        operands (one-token constants: unchanged).  maps (a ContextMaps): every multi-token block's operands also get the level's
+        accumulator as their attribution-map target, in accumulate mode, for the LAST maps.B samples of the operands' batch."""
+        vecs = ctx_vecs
+        if isinstance(ctx_vecs, RegionalVectors):
+            vecs = ctx_vecs.vecs
+            if any(isinstance(cv, ops.CtxOperands) for cv in vecs):      # (K = 1: validated, otherwise ignored)
+                table = ctx_vecs.regions.level(H, W)
+                vecs = [cv.with_row_weights(table) if isinstance(cv, ops.CtxOperands) else cv for cv in vecs]
+        if maps is None:
             return vecs
-        table = ctx_vecs.regions.level(H, W)
-        return [cv.with_row_weights(table) if isinstance(cv, ops.CtxOperands) else cv for cv in vecs]
+        if any(isinstance(cv, ContextKV) for cv in vecs):
+            raise PbeError("SpatialTransformer: attribution maps need the fused cross-attention kernel: build the context's operands with "
+                           "context_vectors(..., maps=True)")
+        multi = [cv for cv in vecs if isinstance(cv, ops.CtxOperands)]
+        for cv in multi:
+            if cv.Nk != maps.K or cv.B < maps.B:
+                raise PbeError(f"SpatialTransformer: the ContextMaps collects {maps.B} samples x {maps.K} tokens, the context has {cv.B} x {cv.Nk}")
+        acc = maps.level(H, W)
+        maps.note(H, W, len(multi))                                      # (K = 1: the level is known, nothing is launched)
+        return [cv.with_map(acc, True, cv.B - maps.B) if isinstance(cv, ops.CtxOperands) else cv for cv in vecs]
 
-    def run(self, x, ctx_vecs):
-        """x [B, H, W, C] fp16 NHWC -> same shape; ctx_vecs = context_vectors(context)."""
+    def run(self, x, ctx_vecs, maps=None):
+        """x [B, H, W, C] fp16 NHWC -> same shape; ctx_vecs = context_vectors(context); maps: a ContextMaps that collects the blocks'
+        cross-attention weights at this grid (context_vectors(..., maps=True)), or None."""
         p = self.pk()
         B, H, W, Cc = x.shape
         N = H * W
-        ctx_vecs = self._levelled(ctx_vecs, H, W)
+        ctx_vecs = self._levelled(ctx_vecs, H, W, maps)
         h, st = ops.gemm(ops.groupnorm(x, p.g, p.b, p.eps, False).view(B * N, Cc), p.wi, p.bi, row_stats=True)   # statistics for the first block's norm1
         for blk, cv in zip(self.transformer_blocks, ctx_vecs):
             h, st = blk.run(h, B, N, cv, stats=st), None
         return ops.gemm(h, p.wo, p.bo, resid=x.view(B * N, Cc)).view(B, H, W, Cc)
 
-    def run_paired(self, x, ctx_vecs):
+    def run_paired(self, x, ctx_vecs, maps=None):
         """x [B, H, W, C] shared by the two halves of a guidance pair, ctx_vecs = context_vectors of the 2B contexts (one- or multi-token)
-        -> [2B, H, W, C]."""
+        -> [2B, H, W, C].  maps: as run(); a collector for B samples takes the second (conditional) half's own launch."""
         p = self.pk()
         B, H, W, Cc = x.shape
         N = H * W
-        ctx_vecs = self._levelled(ctx_vecs, H, W)
+        ctx_vecs = self._levelled(ctx_vecs, H, W, maps)
         x2d = x.view(B * N, Cc)
         with ops.pinned_batch_scale(2):
             h, st = ops.gemm(ops.groupnorm(x, p.g, p.b, p.eps, False).view(B * N, Cc), p.wi, p.bi, row_stats=True)
@@ -700,11 +834,16 @@ class SpatialTransformer(HipModule):
                 ops.gemm(h[half * B * N:(half + 1) * B * N], p.wo, p.bo, resid=x2d, out=y[half * B * N:(half + 1) * B * N])
         return y.view(2 * B, H, W, Cc)
 
-    def forward(self, x, context=None, context_weights=None, context_regions=None):
+    def forward(self, x, context=None, context_weights=None, context_regions=None, context_maps=None):
         """Reference layout: x [B, C, H, W], context [B, K, Dc] (K >= 1 tokens), context_weights [B, K] or None, context_regions
-        [B, K, Hr, Wr] or None (H | Hr and W | Wr) -> [B, C, H, W]."""
+        [B, K, Hr, Wr] or None (H | Hr and W | Wr) -> [B, C, H, W].  context_maps: a ContextMaps that collects the attribution maps."""
         require_gpu(x, "SpatialTransformer")
         if context is None:
             raise PbeError("SpatialTransformer: context is required on the Paint-by-Example path")
+        if context_maps is not None:
+            if context_maps.B is None:
+                context_maps.bind(context.shape[0], context.shape[1], x.device)
+            y = self.run(ops.nchw_to_nhwc(x.float()), self.context_vectors(context, context_weights, context_regions, maps=True), context_maps)
+            return ops.nhwc_to_nchw(y).to(x.dtype)
         y = self.run(ops.nchw_to_nhwc(x.float()), self.context_vectors(context, context_weights, context_regions))
         return ops.nhwc_to_nchw(y).to(x.dtype)

@@ -237,14 +237,16 @@ class UNetModel(HipModule):
         self.__dict__["_ctx_cache"] = None
         self.__dict__["_emb_cache"] = {}
 
-    def context_vectors(self, context, context_weights=None, context_regions=None):
+    def context_vectors(self, context, context_weights=None, context_regions=None, maps=False):
         """What the 16 transformer blocks need of this context [N, K, context_dim] (cached while the same context tensor is presented,
         i.e. across the 51 calls of one PLMS run): for K = 1 the per-sample cross-attention constants, for K > 1 tokens per sample the
         operands of the multi-token cross-attention (BasicTransformerBlock.context_operands).  context_weights: exemplar weights [N, K]
         or None; the cache key holds the weights tensor's identity and version too (the same context with other weights is another
         entry), and the weights are validated and uploaded once per entry (attention.prepare_context_weights).  context_regions: region
         maps [N, K, Hr, Wr] or None (attention.prepare_context_regions), keyed and kept alive exactly as the weights are; the entry's
-        ContextRegions is shared by every transformer, so each level's table is built and uploaded once per entry."""
+        ContextRegions is shared by every transformer, so each level's table is built and uploaded once per entry.  maps: a ContextMaps
+        will collect the attribution maps; the key holds that too, because the levels wider than ctx_fused_max_width then take other
+        operands (ops.CtxOperands instead of ContextKV: BasicTransformerBlock.context_operands)."""
         def tkey(w):
             if isinstance(w, torch.Tensor):
                 return (w.data_ptr(), w._version, tuple(w.shape), w.dtype, str(w.device))
@@ -253,24 +255,26 @@ class UNetModel(HipModule):
         key = (context.data_ptr(), context._version, tuple(context.shape), context.dtype, tkey(w))
         if r is not None:                     # (without regions: the key as it was)
             key += (tkey(r),)
+        if maps:                              # (without a collector: the key as it was)
+            key += ("maps",)
         c = self.__dict__.get("_ctx_cache")
         if c is None or c[0] != key:
             cw = prepare_context_weights(context, w)
             cr = prepare_context_regions(context, r, cw)
-            vecs = {id(st): st.context_vectors(context, cw, cr) for st in self._transformers()}
+            vecs = {id(st): st.context_vectors(context, cw, cr, maps=bool(maps)) for st in self._transformers()}
             c = (key, vecs, context, w, r)    # keep `context` (and the weights / regions) alive so a data_ptr cannot be recycled
             self.__dict__["_ctx_cache"] = c
         return c[1]
 
     # ---- forward ---------------------------------------------------------------------------------
-    def _run_block(self, block, h, emb_all, p, ctx, skip=None):
+    def _run_block(self, block, h, emb_all, p, ctx, skip=None, maps=None):
         for layer in block:
             if isinstance(layer, ResBlock):
                 off, n = p.emb_off[id(layer)]
                 h = layer.run(h, emb_all[:, off:off + n], skip)
                 skip = None
             elif isinstance(layer, SpatialTransformer):
-                h = layer.run(h, ctx[id(layer)])
+                h = layer.run(h, ctx[id(layer)], maps)
             else:
                 h = layer.run(h)
         return h
@@ -291,11 +295,17 @@ class UNetModel(HipModule):
             row = cache[(int(step), device)] = ops.gemm(e, p.emb_w, p.emb_b)
         return row
 
-    def forward_nhwc(self, x16, timesteps, context, paired=False, step=None, context_weights=None, context_regions=None):
+    def forward_nhwc(self, x16, timesteps, context, paired=False, step=None, context_weights=None, context_regions=None, context_maps=None):
         """x16 [B,H,W,cin_pad] fp16 (channels >= in_channels zero), context [B, K, context_dim] (K >= 1) -> eps [B,H,W,out_channels] fp16.
         context_weights: per-sample exemplar weights [B, K] (>= 0, positive sum per sample; 0 = token absent) or None.
         context_regions: per-sample, per-token region maps [B, K, Hr, Wr] >= 0 (every transformer level's grid must divide Hr x Wr:
         the level's map is the area average, and a position no region covers blends the exemplars by their weights) or None.
+        context_maps: an attention.ContextMaps or None.  Every multi-token cross-attention launch of the call adds its head-mean softmax
+        weights to the collector's accumulator of its level (pbe_ctx_attention_map_f16); the collector covers the LAST context_maps.B
+        samples of the context's batch (unbound: all of them) - the conditional half of a guidance batch cat([uc, c]).  With it a K > 1
+        context takes the fused kernel at every level, so without regions the 1280-wide levels leave the q / attention / to_out
+        composition: eps then carries the bits of the call without a collector on blocks with ctx_fused_max_width = 1280 (within the
+        forward tolerance of the default call); with regions the bits are those of the call without a collector.
 
         paired=True is the classifier-free-guidance call of the samplers (plms.py:182-189): the reference feeds
         cat([x]*2), cat([t]*2), cat([uc, c]) - both halves share x and t and differ ONLY in the context.  Then x16 holds the
@@ -306,7 +316,13 @@ class UNetModel(HipModule):
         fp32 summation order - is pinned to the batch-2B choice, so the duplicated evaluation gives the same bits
         (tools/layer_diff.py shows where un-pinned batch sizes part ways)."""
         p = self.pk()
-        ctx = self.context_vectors(context, context_weights, context_regions)
+        maps = context_maps
+        if maps is not None:
+            if maps.B is None:
+                maps.bind(context.shape[0], context.shape[1], context.device)
+            if maps.K != context.shape[1] or maps.B > context.shape[0]:
+                raise PbeError(f"UNetModel: the ContextMaps collects {maps.B} samples x {maps.K} tokens, the context is {tuple(context.shape)}")
+        ctx = self.context_vectors(context, context_weights, context_regions, maps=maps is not None)
         if step is not None:                                           # the caller vouches that every entry of `timesteps` equals `step` (the samplers do)
             emb_all = self.embedding_rows(step, x16.device).expand(timesteps.shape[0], -1)      # one cached row, stride-0 broadcast over the samples
         else:
@@ -326,22 +342,22 @@ class UNetModel(HipModule):
                 h0 = ops.conv3x3_small(x16, p.w_in, p.b_in)
                 off, n = p.emb_off[id(first[0])]
                 r = first[0].run(h0, emb_all[:B, off:off + n])
-            h = first[1].run_paired(r, ctx[id(first[1])])          # pins its own batch-B launches
+            h = first[1].run_paired(r, ctx[id(first[1])], maps)    # pins its own batch-B launches
             hs = [torch.cat([h0, h0], 0), h]
             blocks = blocks[1:]
         else:
             h = ops.conv3x3_small(x16, p.w_in, p.b_in)
             hs = [h]
         for block in blocks:
-            h = self._run_block(block, h, emb_all, p, ctx)
+            h = self._run_block(block, h, emb_all, p, ctx, maps=maps)
             hs.append(h)
-        h = self._run_block(self.middle_block, h, emb_all, p, ctx)
+        h = self._run_block(self.middle_block, h, emb_all, p, ctx, maps=maps)
         for block in self.output_blocks:
-            h = self._run_block(block, h, emb_all, p, ctx, skip=hs.pop())
+            h = self._run_block(block, h, emb_all, p, ctx, skip=hs.pop(), maps=maps)
         h = ops.groupnorm(h, p.go, p.bo, p.eps_o, True)
         return ops.conv3x3(h, p.w_out, p.b_out)
 
-    def forward(self, x, timesteps=None, context=None, y=None, context_weights=None, context_regions=None, **kwargs):
+    def forward(self, x, timesteps=None, context=None, y=None, context_weights=None, context_regions=None, context_maps=None, **kwargs):
         """x [N, in_channels, H, W] (fp32 or fp16), timesteps [N] int, context [N, K, context_dim] (K >= 1 tokens per sample),
         context_weights [N, K] exemplar weights or None, context_regions [N, K, Hr, Wr] region maps or None -> eps [N, out_channels, H, W] in fp16 (what the reference returns under
         torch.autocast)."""
@@ -352,5 +368,8 @@ class UNetModel(HipModule):
             raise PbeError("UNetModel.forward needs timesteps and context")
         p = self.pk()
         x16 = ops.nchw_to_nhwc(x.float(), p.cin_pad)
+        if context_maps is not None:          # (an attention.ContextMaps: see forward_nhwc)
+            out = self.forward_nhwc(x16, timesteps, context, context_weights=context_weights, context_regions=context_regions, context_maps=context_maps)
+            return ops.nhwc_to_nchw(out).to(torch.float16)
         out = self.forward_nhwc(x16, timesteps, context, context_weights=context_weights, context_regions=context_regions)
         return ops.nhwc_to_nchw(out).to(torch.float16)

@@ -24,6 +24,14 @@
 // table entries are fetched into <= 4 registers per thread before phase 1 (their latency hides under it) and parked in an LDS
 // array that only this form has (4352 B; the occupancy of 2 is set by the registers, 57344 B fit twice), so the softmax stage stays
 // one pass.  The RW = false instantiation is the kernel as it was.
+//
+// Map form (template AM, pbe_ctx_attention_map_f16): the softmax weights are also a RESULT - the share of cross-attention each context
+// token received at each row, averaged over the heads (the attribution map of DESIGN.md section 4.11).  After the barrier that
+// completes P the weights are only read, so one thread per (row, token) of the tile, q = row Nk + j < 64 Nk <= 1024 (<= 4 per thread),
+// sums the fp16 weights phase 2 multiplies over h = 0 .. H-1 in that order in fp32, multiplies by 1.0f / H and stores the result to
+// amap[b am_bs + t am_rs + j], or adds it to what is there: a plain read-modify-write by the one thread that owns the element, no
+// atomics, so launches on one stream accumulate deterministically.  No new barrier, no new LDS; rows past the sample's last token
+// are not written.  Y and the row statistics keep the bits of the AM = false instantiations, which are the kernel as it was.
 #include "common.h"
 #include "../../include/pbe_hip.h"
 
@@ -35,6 +43,7 @@ struct CtxP {
     int ln_parts; float ln_eps; double inv_c;
     const float* log2w; long w_bs;          // pbe_ctx_attention_w_f16: per-(sample, token) log2 weight added to kbias, or null
     const float* log2rw; long rw_bs, rw_rs; // RW form: per-(sample, row, token) log2 weight, element (b, t, j) at b rw_bs + t rw_rs + j
+    float* amap; long am_bs, am_rs; int am_acc; // AM form: head-mean softmax weight of (b, t, j) at b am_bs + t am_rs + j, stored or added
 };
 
 #define CTX_TM 64          // rows per workgroup
@@ -44,7 +53,7 @@ struct CtxP {
 #define CTX_PS 136         // halfs per row of P (17 slots)
 #define CTX_RS 17          // RW form: floats per parked table row (odd: the 64 rows of a wave hit 64 different banks)
 
-template <bool RW>
+template <bool RW, bool AM>
 __global__ void __launch_bounds__(256) ctx_attn_kernel(const CtxP p) {
     // [0, 33024): phase 1 staging (X tile 64 x 72, Kq tile 128 x 72 halfs = 27648 B), then S fp32 [64][129]
     __shared__ __attribute__((aligned(16))) unsigned char smem[CTX_TM * CTX_SS * 4 + CTX_TM * CTX_PS * 2];
@@ -233,6 +242,22 @@ __global__ void __launch_bounds__(256) ctx_attn_kernel(const CtxP p) {
     const int nct = p.C / 32;
     h16x8 vf[8];
     if (cw < nct) load_vo(vf, cw * 32);
+    if constexpr (AM) {                                      // P is complete and only read from here on: the map rides beside phase 2
+#pragma clang fp contract(off)                               // (the product is rounded before the add: accumulate = base + stored, bit for bit)
+        const float inv_h = 1.0f / (float)p.H;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int q = tid + 256 * u, r = q / p.Nk, j = q - r * p.Nk;
+            if (q < CTX_TM * p.Nk && row0 + r < p.tokens) {
+                const h16* pr = P + r * CTX_PS + j;
+                float a = 0.f;
+                for (int h = 0; h < p.H; ++h) a += (float)pr[h * p.Nk];   // fixed order: the fp16 weights phase 2 multiplies
+                a *= inv_h;
+                float* dst = p.amap + (long)b * p.am_bs + (long)(row0 + r) * p.am_rs + j;
+                *dst = p.am_acc ? *dst + a : a;
+            }
+        }
+    }
     for (int ct = cw; ct < nct; ct += 2) {
         f32x16 o;
 #pragma unroll
@@ -271,7 +296,7 @@ __global__ void __launch_bounds__(256) ctx_attn_kernel(const CtxP p) {
 extern "C" size_t pbe_sizeof_ctx_attn_desc(void) { return sizeof(pbe_ctx_attn_desc); }
 
 static int ctx_attention_launch(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, const float* log2rw, int64_t rw_bs, int64_t rw_rs,
-                                pbe_stream_t stream) {
+                                pbe_stream_t stream, float* amap = nullptr, int64_t am_bs = 0, int64_t am_rs = 0, int accumulate = 0) {
     PBE_REQUIRE(d && d->X && d->Y && d->Kq && d->colsum && d->kbias && d->Vo && d->bias && d->ln_stats, "pbe_ctx_attention_f16: null operand");
     PBE_REQUIRE(d->C % 64 == 0 && d->C >= 64 && d->C <= 1280, "pbe_ctx_attention_f16: C = %d unsupported (multiple of 64, 64..1280)", d->C);
     PBE_REQUIRE(d->Nk >= 1 && d->Nk <= 16, "pbe_ctx_attention_f16: Nk = %d unsupported (1..16 context tokens)", d->Nk);
@@ -295,10 +320,15 @@ static int ctx_attention_launch(const pbe_ctx_attn_desc* d, const float* log2w, 
     p.ldx = d->ldx; p.ldy = d->ldy; p.kq_bs = d->kq_bs; p.kq_rs = d->kq_rs; p.vo_bs = d->vo_bs; p.vo_rs = d->vo_rs; p.cs_bs = d->cs_bs;
     p.ln_ld = d->ln_stats_ld; p.ln_parts = d->ln_parts; p.ln_eps = d->ln_eps; p.inv_c = 1.0 / (double)d->C;
     p.log2w = log2w; p.w_bs = w_bs; p.log2rw = log2rw; p.rw_bs = rw_bs; p.rw_rs = rw_rs;
+    p.amap = amap; p.am_bs = am_bs; p.am_rs = am_rs; p.am_acc = accumulate ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     pbe_prof_begin(PBE_K_CTXATTN, s);
-    if (log2rw) hipLaunchKernelGGL(ctx_attn_kernel<true>, dim3((unsigned)(B * tps)), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(ctx_attn_kernel<false>, dim3((unsigned)(B * tps)), dim3(256), 0, s, p);
+    const dim3 grid((unsigned)(B * tps));
+    if (amap) {
+        if (log2rw) hipLaunchKernelGGL((ctx_attn_kernel<true, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((ctx_attn_kernel<false, true>), grid, dim3(256), 0, s, p);
+    } else if (log2rw) hipLaunchKernelGGL((ctx_attn_kernel<true, false>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((ctx_attn_kernel<false, false>), grid, dim3(256), 0, s, p);
     // a class of its own, accounted in bytes like the norms (memory-bound: 4 HJ FLOP per byte of X at most): X twice (the 2nd from L2 at
     // best), Y, Kq, Vo
     pbe_prof_end(PBE_K_CTXATTN, s, 2.0 * (3.0 * (double)d->M * d->C + 2.0 * (double)B * HJ * d->C));
@@ -324,4 +354,19 @@ extern "C" int pbe_ctx_attention_rw_f16(const pbe_ctx_attn_desc* d, const float*
     PBE_REQUIRE(log2rw && ((uintptr_t)log2rw & 3) == 0, "pbe_ctx_attention_rw_f16: log2rw must be a 4-byte aligned pointer");
     PBE_REQUIRE(d && rw_rs >= d->Nk && rw_bs >= 0, "pbe_ctx_attention_rw_f16: rw_rs must cover Nk, rw_bs >= 0");
     return ctx_attention_launch(d, nullptr, 0, log2rw, rw_bs, rw_rs, stream);
+}
+
+// Any of the three launches above with the attribution map as a side output: amap fp32, element (b, t, j) at amap[b * am_bs + t * am_rs + j]
+// for t < tokens, j < Nk, takes (accumulate = 0) or is increased by (accumulate != 0) the mean over the heads of the fp16 softmax
+// weights of token j at row t.  log2w / log2rw as in the _w / _rw entries, or NULL; not both.  Y and row_stats_out are those of the
+// entry without the map, bit for bit.  Nothing outside t < tokens, j < Nk of a sample's map is touched.
+extern "C" int pbe_ctx_attention_map_f16(const pbe_ctx_attn_desc* d, const float* log2w, int64_t w_bs, const float* log2rw, int64_t rw_bs,
+                                         int64_t rw_rs, float* amap, int64_t am_bs, int64_t am_rs, int32_t accumulate, pbe_stream_t stream) {
+    PBE_REQUIRE(!(log2w && log2rw), "pbe_ctx_attention_map_f16: log2rw replaces log2w: give one of them");
+    PBE_REQUIRE(!log2w || (((uintptr_t)log2w & 3) == 0 && w_bs >= 0), "pbe_ctx_attention_map_f16: log2w must be 4-byte aligned, w_bs >= 0");
+    PBE_REQUIRE(!log2rw || (((uintptr_t)log2rw & 3) == 0 && d && rw_rs >= d->Nk && rw_bs >= 0),
+                "pbe_ctx_attention_map_f16: log2rw must be 4-byte aligned, rw_rs must cover Nk, rw_bs >= 0");
+    PBE_REQUIRE(amap && ((uintptr_t)amap & 3) == 0, "pbe_ctx_attention_map_f16: amap must be a 4-byte aligned pointer");
+    PBE_REQUIRE(d && am_rs >= d->Nk && am_bs >= 0, "pbe_ctx_attention_map_f16: am_rs must cover Nk, am_bs >= 0");
+    return ctx_attention_launch(d, log2w, w_bs, log2rw, rw_bs, rw_rs, stream, amap, am_bs, am_rs, accumulate);
 }

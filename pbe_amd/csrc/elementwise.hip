@@ -424,6 +424,34 @@ extern "C" int pbe_mul_planes_f32(const float* x, const float* m, float* out, in
     EW_END(s, (double)total * 12.0, "pbe_mul_planes_f32");
 }
 
+// pbe_ctx_map_gather_f32: out[b, j, y, x] (+)= s * (acc[b, (y / fy) * w + (x / fx), j] / div) - a transformer level's attribution
+// accumulator [B, h * w, K] (pbe_ctx_attention_map_f16) as planes on the picture grid [B, K, fy * h, fx * w]: nearest upsample and the
+// transposition to the layout region maps use.  div = the level's launch count: an IEEE division, so n launches that each added
+// exactly 1 give exactly 1.  Every step is rounded on its own (no contraction, whatever the compiler flag says).
+__global__ void ctx_map_gather_kernel(const float* acc, float* out, int K, int h, int w, int fy, int fx, float s, float div, int accumulate,
+                                      long total) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;           // over B * K * Hl * Wl
+    if (i >= total) return;
+    const int Wl = fx * w, Hl = fy * h;
+    const long bj = i / ((long)Hl * Wl);
+    const int rem = (int)(i - bj * (long)Hl * Wl), y = rem / Wl, x = rem - y * Wl;
+    const long b = bj / K;
+    const int j = (int)(bj - b * K);
+    const float v = s * (acc[(b * h * w + (long)(y / fy) * w + x / fx) * K + j] / div);
+    out[i] = accumulate ? out[i] + v : v;
+}
+extern "C" int pbe_ctx_map_gather_f32(const float* acc, float* out, int32_t B, int32_t K, int32_t h, int32_t w, int32_t fy, int32_t fx, float s,
+                                      float div, int32_t accumulate, pbe_stream_t stream) {
+    PBE_REQUIRE(acc && out && B > 0 && K > 0 && h > 0 && w > 0 && fy > 0 && fx > 0 && div > 0.f, "pbe_ctx_map_gather_f32: bad arguments");
+    PBE_REQUIRE((long)h * fy * w * fx < (1L << 31), "pbe_ctx_map_gather_f32: grid too large");
+    hipStream_t st = (hipStream_t)stream;
+    const long total = (long)B * K * h * fy * w * fx;
+    EW_BEGIN(st);
+    hipLaunchKernelGGL(ctx_map_gather_kernel, EW_GRID(total), dim3(256), 0, st, acc, out, K, h, w, fy, fx, s, div, accumulate ? 1 : 0, total);
+    EW_END(st, (double)total * (accumulate ? 12.0 : 8.0), "pbe_ctx_map_gather_f32");
+}
+
 // pbe_planes_to_u8_canvas: canvas[y0 + y, x0 + x, c] = (uint8) trunc(255 * clamp(src[c, y, x] * a[c] + b[c], 0, 1))  for one CHW plane
 // set (src channel stride HW; `bcast` = 1 repeats channel 0 into the 3 output channels: the mask file).  Truncation, multiply THEN
 // add (two roundings), like the reference's `(255. * x.numpy()).astype(np.uint8)` after `x * std + mean` / `(x + 1) / 2`.

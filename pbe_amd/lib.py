@@ -75,6 +75,8 @@ SYMBOLS = {
     "pbe_ctx_attention_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp]),
     "pbe_ctx_attention_w_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp, c_i64, c_vp]),
     "pbe_ctx_attention_rw_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp, c_i64, c_i64, c_vp]),
+    "pbe_ctx_attention_map_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp]),
+    "pbe_ctx_map_gather_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_vp]),
     "pbe_gemm_f16": (c_i32, [C.POINTER(GemmDesc), c_vp]),
     "pbe_conv3x3_f16": (c_i32, [C.POINTER(Conv3x3Desc), c_vp]),
     "pbe_gemm_plan": (c_i32, [C.POINTER(GemmDesc), C.POINTER(c_i32), C.POINTER(c_sz)]),

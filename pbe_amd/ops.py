@@ -602,21 +602,44 @@ class CtxOperands:
     (BasicTransformerBlock.context_operands); a slice of the batch (`rows`) serves one half of a guidance pair.  log2w: fp32 [B, Nk]
     log2 of the exemplar weights (-inf: token absent) or None; it rides beside the folded operands, which do not depend on it.
     log2rw: fp32 [B, tokens, Nk] (unit stride over the Nk tokens of the context) log2 of the weight of token j at query row t, for
-    regional exemplars (pbe_ctx_attention_rw_f16), or None.  It REPLACES log2w - the host has multiplied the exemplar weights in."""
-    __slots__ = ("kq", "colsum", "kbias", "vo", "bias", "B", "H", "Nk", "C", "log2w", "log2rw")
+    regional exemplars (pbe_ctx_attention_rw_f16), or None.  It REPLACES log2w - the host has multiplied the exemplar weights in.
+    amap: the attribution-map target of pbe_ctx_attention_map_f16 or None: (fp32 [Bm, tokens, Nk], accumulate, b0) - the head-mean
+    softmax weights of samples b0 .. b0 + Bm - 1 are stored to / added to it (ctx_attention launches it when it covers every sample
+    of the launch; a caller whose map covers some of the samples launches per range of `rows`)."""
+    __slots__ = ("kq", "colsum", "kbias", "vo", "bias", "B", "H", "Nk", "C", "log2w", "log2rw", "amap")
 
-    def __init__(self, kq, colsum, kbias, vo, bias, H, Nk, log2w=None, log2rw=None):
+    def __init__(self, kq, colsum, kbias, vo, bias, H, Nk, log2w=None, log2rw=None, amap=None):
         self.kq, self.colsum, self.kbias, self.vo, self.bias, self.H, self.Nk = kq, colsum, kbias, vo, bias, int(H), int(Nk)
         self.B, self.C = kq.shape[0], kq.shape[2]
-        self.log2w, self.log2rw = log2w, log2rw
+        self.log2w, self.log2rw, self.amap = log2w, log2rw, amap
 
     def rows(self, b0: int, b1: int) -> "CtxOperands":
+        amap = None
+        if self.amap is not None:                         # the part of the range the map covers must be all of it or none of it
+            t, acc, m0 = self.amap
+            m1 = m0 + t.shape[0]
+            if m0 <= b0 and b1 <= m1:
+                amap = (t[b0 - m0:b1 - m0], acc, 0)
+            elif not (b1 <= m0 or m1 <= b0):
+                raise _l.PbeError(f"CtxOperands.rows({b0}, {b1}): the attribution map covers samples {m0}..{m1 - 1}, a part of that range")
         return CtxOperands(self.kq[b0:b1], self.colsum[b0:b1], self.kbias[b0:b1], self.vo[b0:b1], self.bias, self.H, self.Nk,
-                           None if self.log2w is None else self.log2w[b0:b1], None if self.log2rw is None else self.log2rw[b0:b1])
+                           None if self.log2w is None else self.log2w[b0:b1], None if self.log2rw is None else self.log2rw[b0:b1], amap)
 
     def with_row_weights(self, log2rw) -> "CtxOperands":
         """The same folded operands with the per-row table in place of the per-sample weights (nothing is re-folded)."""
-        return CtxOperands(self.kq, self.colsum, self.kbias, self.vo, self.bias, self.H, self.Nk, None, log2rw)
+        return CtxOperands(self.kq, self.colsum, self.kbias, self.vo, self.bias, self.H, self.Nk, None, log2rw, self.amap)
+
+    def with_map(self, amap, accumulate=True, b0=0) -> "CtxOperands":
+        """The same folded operands (and weights / table) with an attribution-map target for samples b0 .. (nothing is re-folded)."""
+        return CtxOperands(self.kq, self.colsum, self.kbias, self.vo, self.bias, self.H, self.Nk, self.log2w, self.log2rw,
+                           None if amap is None else (amap, bool(accumulate), int(b0)))
+
+    def map_ranges(self):
+        """The sample ranges [(b0, b1), ..] one launch each must cover so that the map target covers all of a launch or none of it."""
+        if self.amap is None:
+            return [(0, self.B)]
+        m0, m1 = self.amap[2], self.amap[2] + self.amap[0].shape[0]
+        return [r for r in ((0, m0), (m0, m1), (m1, self.B)) if r[1] > r[0]]
 
 
 def ctx_attention_check(C_: int, H: int, Nk: int, tokens: int, M: int) -> None:
@@ -631,11 +654,31 @@ def ctx_attention_check(C_: int, H: int, Nk: int, tokens: int, M: int) -> None:
         raise _l.PbeError(f"ctx_attention: {M} rows are not whole samples of {tokens} tokens")
 
 
+def ctx_attention_map_check(amap, B: int, tokens: int, Nk: int, device=None):
+    """Host validation of an attribution-map target (no GPU needed): (tensor, accumulate) with tensor fp32 [B, tokens, Nk], unit stride
+    over the context tokens, rows of >= Nk floats, on `device`.  Raises PbeError naming what is wrong; returns (tensor, accumulate)."""
+    if not isinstance(amap, (tuple, list)) or len(amap) != 2 or not isinstance(amap[0], torch.Tensor):
+        raise _l.PbeError("ctx_attention: attn_map must be (fp32 tensor [B, tokens, Nk], accumulate)")
+    t, acc = amap
+    if t.dtype != torch.float32:
+        raise _l.PbeError(f"ctx_attention: attn_map must be fp32, got {t.dtype}")
+    if t.dim() != 3 or tuple(t.shape) != (B, int(tokens), Nk):
+        raise _l.PbeError(f"ctx_attention: attn_map must be [{B}, {int(tokens)}, {Nk}] (samples, tokens, context tokens), got {tuple(t.shape)}")
+    if t.stride(2) != 1 or t.stride(1) < Nk or t.stride(0) < 0:
+        raise _l.PbeError(f"ctx_attention: attn_map needs unit stride over the context tokens and rows of >= {Nk} floats, got strides {tuple(t.stride())}")
+    if device is not None and t.device != device:
+        raise _l.PbeError(f"ctx_attention: attn_map is on {t.device}, x on {device}")
+    return t, bool(acc)
+
+
 def ctx_attention(x: torch.Tensor, ops_ctx: CtxOperands, stats: "RowStats", eps: float, *, tokens: int, out: Optional[torch.Tensor] = None,
-                  row_stats=True):
+                  row_stats=True, attn_map=None):
     """y = x + attn2(LayerNorm(x), context) for a context of 1..16 tokens in one launch (pbe_ctx_attention_f16): x [M, C] fp16 is the RAW
     residual stream, `stats` the RowStats of its rows, ops_ctx the context's CtxOperands (sample b serves rows b * tokens ..).
-    Returns (y, RowStats of y's rows - one partial; row_stats may be a RowStats to fill, or False: (y, None))."""
+    Returns (y, RowStats of y's rows - one partial; row_stats may be a RowStats to fill, or False: (y, None)).
+    attn_map = (fp32 [B, tokens, Nk], accumulate) (default: ops_ctx.amap, which must then cover every sample): the launch is
+    pbe_ctx_attention_map_f16 - the same y and statistics bit for bit, and the head-mean softmax weights stored to (accumulate False)
+    or added to (True) the tensor; timing keys xam / xawm / xarm."""
     if not isinstance(ops_ctx, CtxOperands):
         raise _l.PbeError("ctx_attention: ops_ctx must be a CtxOperands")
     o = ops_ctx
@@ -668,6 +711,30 @@ def ctx_attention(x: torch.Tensor, ops_ctx: CtxOperands, stats: "RowStats", eps:
     d = _l.CtxAttnDesc(_p(x), _p(out), _p(o.kq), _p(o.colsum), _p(o.kbias), _p(o.vo), _p(o.bias), stats.ptr(), None if rs is None else rs.ptr(),
                        M, Cc, int(tokens), o.H, o.Nk, ldx, out.stride(0), o.kq.stride(0), o.kq.stride(1), o.vo.stride(0), o.vo.stride(1),
                        o.colsum.stride(0), stats.parts, stats.ld, float(eps))
+    am = None
+    if attn_map is None and o.amap is not None:
+        if o.amap[2] != 0 or o.amap[0].shape[0] != o.B:
+            raise _l.PbeError(f"ctx_attention: the operands' attribution map covers samples {o.amap[2]}..{o.amap[2] + o.amap[0].shape[0] - 1} of {o.B}: "
+                              "launch per range (CtxOperands.map_ranges / rows)")
+        attn_map = o.amap[:2]
+    if attn_map is not None:
+        am = ctx_attention_map_check(attn_map, o.B, int(tokens), o.Nk, x.device)
+
+    def launch(name, key, lw, rw):
+        """One of the three forms, with the map when there is one: lw / rw are (pointer, strides..) or None."""
+        lib = _l.load()
+        if am is not None:
+            with _timed(f"{key}m:{M}:{Cc}:{o.H}:{o.Nk}"):
+                _l.check(lib.pbe_ctx_attention_map_f16(C.byref(d), *(lw or (None, 0)), *(rw or (None, 0, 0)), _p(am[0]), am[0].stride(0), am[0].stride(1),
+                                                       1 if am[1] else 0, _stream()), "pbe_ctx_attention_map_f16")
+            return
+        with _timed(f"{key}:{M}:{Cc}:{o.H}:{o.Nk}"):
+            if rw is not None:
+                _l.check(lib.pbe_ctx_attention_rw_f16(C.byref(d), *rw, _stream()), name)
+            elif lw is not None:
+                _l.check(lib.pbe_ctx_attention_w_f16(C.byref(d), *lw, _stream()), name)
+            else:
+                _l.check(lib.pbe_ctx_attention_f16(C.byref(d), _stream()), name)
     if o.log2rw is not None:
         if o.log2w is not None:
             raise _l.PbeError("ctx_attention: log2rw replaces log2w (the row table holds the exemplar weights already): give one of them")
@@ -678,19 +745,41 @@ def ctx_attention(x: torch.Tensor, ops_ctx: CtxOperands, stats: "RowStats", eps:
             raise _l.PbeError(f"ctx_attention: log2rw must be [{o.B}, {int(tokens)}, {o.Nk}] (samples, tokens, context tokens), got {tuple(t.shape)}")
         if t.stride(2) != 1 or t.stride(1) < o.Nk or t.stride(0) < 0:
             raise _l.PbeError(f"ctx_attention: log2rw needs unit stride over the context tokens and rows of >= {o.Nk} floats, got strides {tuple(t.stride())}")
-        with _timed(f"xar:{M}:{Cc}:{o.H}:{o.Nk}"):
-            _l.check(_l.load().pbe_ctx_attention_rw_f16(C.byref(d), _p(t), t.stride(0), t.stride(1), _stream()), "pbe_ctx_attention_rw_f16")
+        launch("pbe_ctx_attention_rw_f16", "xar", None, (_p(t), t.stride(0), t.stride(1)))
         return out, rs
     if o.log2w is not None:
         _f(o.log2w, "ctx_attention log2w")
         if tuple(o.log2w.shape) != (o.B, o.Nk) or o.log2w.stride(1) != 1:
             raise _l.PbeError(f"ctx_attention: log2w must be [{o.B}, {o.Nk}] with unit stride over the tokens, got {tuple(o.log2w.shape)}")
-        with _timed(f"xaw:{M}:{Cc}:{o.H}:{o.Nk}"):
-            _l.check(_l.load().pbe_ctx_attention_w_f16(C.byref(d), _p(o.log2w), o.log2w.stride(0), _stream()), "pbe_ctx_attention_w_f16")
+        launch("pbe_ctx_attention_w_f16", "xaw", (_p(o.log2w), o.log2w.stride(0)), None)
         return out, rs
-    with _timed(f"xa:{M}:{Cc}:{o.H}:{o.Nk}"):
-        _l.check(_l.load().pbe_ctx_attention_f16(C.byref(d), _stream()), "pbe_ctx_attention_f16")
+    launch("pbe_ctx_attention_f16", "xa", None, None)
     return out, rs
+
+
+def ctx_map_gather(acc: torch.Tensor, grid, scale: float = 1.0, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                   div: float = 1.0) -> torch.Tensor:
+    """A level's attribution accumulator acc fp32 [B, h*w, K] (rows in NHWC order) with grid = (h, w) -> fp32 [B, K, Hl, Wl] planes
+    (pbe_ctx_map_gather_f32): out[b, j, y, x] (+)= scale * (acc[b, (y / fy) * w + (x / fx), j] / div), fy = Hl / h, fx = Wl / w whole
+    numbers; out None: the level's own grid (fy = fx = 1).  accumulate: add to `out` instead of storing.  div > 0: the launch count."""
+    _f(acc, "ctx_map_gather acc")
+    h, w = int(grid[0]), int(grid[1])
+    if acc.dim() != 3 or not acc.is_contiguous() or acc.shape[1] != h * w or h < 1 or w < 1:
+        raise _l.PbeError(f"ctx_map_gather: acc must be a contiguous [B, {h} * {w}, K] tensor, got {tuple(acc.shape)}")
+    B, _, K = acc.shape
+    if not float(div) > 0.0:
+        raise _l.PbeError(f"ctx_map_gather: div must be > 0, got {div}")
+    if out is None:
+        if accumulate:
+            raise _l.PbeError("ctx_map_gather: accumulate needs an `out` to add to")
+        out = torch.empty((B, K, h, w), dtype=torch.float32, device=acc.device)
+    _f(out, "ctx_map_gather out")
+    if out.dim() != 4 or tuple(out.shape[:2]) != (B, K) or not out.is_contiguous() or out.shape[2] % h or out.shape[3] % w or out.device != acc.device:
+        raise _l.PbeError(f"ctx_map_gather: out must be a contiguous [{B}, {K}, Hl, Wl] tensor on {acc.device} with Hl, Wl whole multiples of "
+                          f"{h}, {w}, got {tuple(out.shape)}")
+    _l.check(_l.load().pbe_ctx_map_gather_f32(_p(acc), _p(out), B, K, h, w, out.shape[2] // h, out.shape[3] // w, float(scale), float(div), 1 if accumulate else 0,
+                                              _stream()), "pbe_ctx_map_gather_f32")
+    return out
 
 
 MX8_TOKENS, MX8_VT = 0, 1          # include/pbe_hip.h PBE_MX8_*: q / k rows (contraction = channel) and V^T rows (contraction = token)

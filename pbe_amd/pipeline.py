@@ -67,11 +67,16 @@ def resize_mask(mask: torch.Tensor, size, antialias: bool = True) -> torch.Tenso
 @torch.no_grad()
 def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *, steps: int = 50, scale: float = 5.0,
             x_T: Optional[torch.Tensor] = None, post_eps: Optional[torch.Tensor] = None, sampler: str = "plms",
-            antialias: bool = True, timings: Optional[Dict[str, float]] = None, ref_weights=None, ref_regions=None) -> Dict[str, torch.Tensor]:
+            antialias: bool = True, timings: Optional[Dict[str, float]] = None, ref_weights=None, ref_regions=None,
+            return_ref_maps: bool = False) -> Dict[str, torch.Tensor]:
     """image [B,3,H,W] in [-1,1], mask [B,1,H,W] in {0,1} (1 = keep), ref [B,3,224,224] CLIP-normalised (or [B,K,3,224,224]: K
     exemplars per sample, with ref_weights [B, K] their non-negative weights or None and ref_regions [B, K, Hr, Wr] >= 0 where each of
     them applies - 1 = fully, 0 = not there; the latent grid and its halvings down to the coarsest attention level must divide
-    Hr x Wr - or None); everything on the model's GPU.  Returns {'image' [B,3,H,W] in [0,1], 'latent', 'c', 'z_inpaint', 'mask_lat'}."""
+    Hr x Wr - or None); everything on the model's GPU.  Returns {'image' [B,3,H,W] in [0,1], 'latent', 'c', 'z_inpaint', 'mask_lat'}.
+    return_ref_maps: also 'ref_maps' fp32 [B, K, h, w] on the latent grid - the share of cross-attention each exemplar received at each
+    position, averaged over heads, blocks, sampler steps and levels (ldm.modules.attention.ContextMaps; K = 1: ones).  Collecting them
+    sends every level through the fused cross-attention kernel: with ref_regions the picture is the one without return_ref_maps bit for
+    bit; without regions (and K > 1) it is the picture of blocks with ctx_fused_max_width = 1280, within the sampler tolerance of the default."""
     from ldm.models.diffusion.ddim import DDIMSampler
     from ldm.models.diffusion.plms import PLMSSampler
     dev = model.device
@@ -91,10 +96,15 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     if ev:
         ev[2].record()
     smp = (PLMSSampler if sampler == "plms" else DDIMSampler)(model)
+    more = {} if ref_regions is None else {"conditioning_regions": ref_regions}
+    cm = None
+    if return_ref_maps:
+        from ldm.modules.attention import ContextMaps
+        cm = more["conditioning_maps"] = ContextMaps()
     z0, _ = smp.sample(S=steps, batch_size=B, shape=list(z_inp.shape[1:]), conditioning=c, verbose=False,
                        unconditional_guidance_scale=scale, unconditional_conditioning=uc, eta=0.0, x_T=x_T,
                        test_model_kwargs={"inpaint_image": z_inp, "inpaint_mask": m_lat}, conditioning_weights=ref_weights,
-                       **({} if ref_regions is None else {"conditioning_regions": ref_regions}))
+                       **more)
     if ev:
         ev[3].record()
     img = ops.image_post(model.decode_first_stage_nhwc(z0))                              # inference.py:346-347
@@ -103,4 +113,15 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
         torch.cuda.synchronize()
         for k, i in (("clip_ms", 0), ("vae_encode_ms", 1), ("sampler_ms", 2), ("vae_decode_ms", 3)):
             timings[k] = timings.get(k, 0.0) + ev[i].elapsed_time(ev[i + 1])
-    return {"image": img, "latent": z0, "c": c, "z_inpaint": z_inp, "mask_lat": m_lat}
+    out = {"image": img, "latent": z0, "c": c, "z_inpaint": z_inp, "mask_lat": m_lat}
+    if cm is not None:
+        out["ref_maps"] = cm.result(z_inp.shape[-2:])
+    return out
+
+
+def ref_maps_u8(ref_maps: torch.Tensor, size, antialias: bool = True) -> torch.Tensor:
+    """Attribution maps fp32 [B, K, h, w] in [0, 1] -> uint8 [B, K, H, W] at the picture size `size` = (H, W): resized on the device
+    (pbe_resize_bilinear_f32, as the mask is) and quantised as round(255 * map).  What --save_reference_maps writes, one PNG per plane."""
+    B, K, h, w = ref_maps.shape
+    big = ops.resize_bilinear(ref_maps.float().reshape(B * K, 1, h, w).contiguous(), size, antialias)
+    return (big * 255.0).round_().clamp_(0.0, 255.0).to(torch.uint8).view(B, K, int(size[0]), int(size[1]))

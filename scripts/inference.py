@@ -13,6 +13,9 @@ proportional to w exp(score), so `2 1` equals naming the first image twice and `
 `--reference_region a.png b.png` gives each of them a grayscale image of where it applies (white = there, black = not there; grey
 in between): it is resized to the latent grid and every position of the picture attends to the exemplars whose region covers it,
 weighted by region x weight; a position that no region covers blends them by their weights alone.
+`--save_reference_maps` writes, beside the result, one 8-bit grayscale PNG per reference into `<outdir>/reference_maps/`, named after
+the result file with `_ref<j>`: the share of cross-attention that reference received at each position of the picture (white = all of
+it), averaged over heads, blocks, sampler steps and levels - whether a region "took", which exemplar wins where.
 
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
@@ -59,6 +62,8 @@ def parse(argv=None):
                    "--reference_path, default all 1; at least one must be positive")
     p.add_argument("--reference_region", type=str, nargs="+", default=None, help="(not in the reference) one grayscale image per "
                    "--reference_path: white where that exemplar applies")
+    p.add_argument("--save_reference_maps", action="store_true", help="(not in the reference) write one grayscale attribution map per "
+                   "--reference_path into <outdir>/reference_maps/: where the picture attended to that exemplar")
     p.add_argument("--random_weights", action="store_true", help="name-seeded random weights instead of --ckpt")
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
@@ -89,6 +94,23 @@ def load_regions(paths, size, device):
         u8 = torch.from_numpy(np.array(Image.open(path).convert("L"), dtype=np.uint8)).to(device)
         maps.append(pipeline.resize_mask(u8.float()[None, None] / 255.0, size))
     return torch.cat(maps, 1).clamp_(0.0, 1.0)
+
+
+def save_reference_maps(outdir, stem, seed, ref_maps, H, W):
+    """ref_maps fp32 [B, K, h, w] (ContextMaps.result) -> <outdir>/reference_maps/<stem>_<seed>[_<i>]_ref<j>.png, 8-bit grayscale
+    round(255 * map) at the picture size (pipeline.ref_maps_u8: resized on the device).  Returns the paths, sample-major."""
+    from PIL import Image
+    from pbe_amd import pipeline
+    d = os.path.join(outdir, "reference_maps")
+    os.makedirs(d, exist_ok=True)
+    u8 = pipeline.ref_maps_u8(ref_maps, (H, W)).cpu().numpy()
+    paths = []
+    for i in range(u8.shape[0]):
+        tag = f"{stem}_{seed}" if u8.shape[0] == 1 else f"{stem}_{seed}_{i}"
+        for j in range(u8.shape[1]):
+            paths.append(os.path.join(d, f"{tag}_ref{j}.png"))
+            Image.fromarray(u8[i, j], mode="L").save(paths[-1])
+    return paths
 
 
 def seed_everything(seed):
@@ -151,6 +173,10 @@ def main(argv=None):
         if opt.reference_region is not None:                                           # one map per exemplar token, the same for every sample
             cr = load_regions(opt.reference_region, z_inpaint.shape[-2:], device).expand(c.shape[0], -1, -1, -1).contiguous()
             extra["conditioning_regions"] = cr
+        cm = None
+        if opt.save_reference_maps:
+            from ldm.modules.attention import ContextMaps
+            cm = extra["conditioning_maps"] = ContextMaps()
         shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
         samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=opt.n_samples, shape=shape, verbose=False,
                                     unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc, eta=opt.ddim_eta,
@@ -159,6 +185,10 @@ def main(argv=None):
         if not opt.skip_save:
             for i in range(xd.shape[0]):
                 paths = preprocess.save_outputs_device(opt.outdir, filename[:-4], opt.seed, t, xd[i], opt.H, opt.W)
+        ref_maps = None
+        if cm is not None:                                                             # (an explicit request: written with --skip_save too)
+            ref_maps = cm.result(z_inpaint.shape[-2:])
+            save_reference_maps(opt.outdir, filename[:-4], opt.seed, ref_maps, opt.H, opt.W)
         x = xd.cpu()
         if opt.dump_tensors:
             import numpy as np
@@ -166,7 +196,8 @@ def main(argv=None):
                      post_eps=post_eps.numpy(), c=c.float().cpu().numpy(), z_inpaint=z_inpaint.float().cpu().numpy(),
                      mask64=test_model_kwargs["inpaint_mask"].float().cpu().numpy(), latent=samples.float().cpu().numpy(), image=x.numpy(),
                      reference_weight=(cw if cw is not None else torch.ones(c.shape[:2])).double().numpy(),
-                     **({} if cr is None else {"reference_region": cr.double().cpu().numpy()}))
+                     **({} if cr is None else {"reference_region": cr.double().cpu().numpy()}),
+                     **({} if ref_maps is None else {"ref_maps": ref_maps.float().cpu().numpy()}))
     print(f"Your samples are ready and waiting for you here: \n{opt.outdir} \n \nEnjoy.")
     return x
 

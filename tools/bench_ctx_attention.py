@@ -24,7 +24,14 @@ second sample absent.  "spread" is (p90 - p10) / median of the unweighted arm.
 times the row-weight form (pbe_ctx_attention_rw_f16, launch key xar) against the weighted form (pbe_ctx_attention_w_f16, xaw) at the
 shapes above, arms alternating the same way.  Table: exp2(randn) weights times uniform regions zeroed below 0.6 (about 60 % of the
 entries -inf, rows without a token fall back to the weights), one [B, tokens, Nk] table per shape: it adds 4 Nk bytes per row to the
-about 6 C the kernel moves.  "spread" is (p90 - p10) / median of the weighted arm."""
+about 6 C the kernel moves.  "spread" is (p90 - p10) / median of the weighted arm.
+
+    python tools/bench_ctx_attention.py --maps [--out profiles/ctx_maps_timing.txt]
+
+times the map-emitting form (pbe_ctx_attention_map_f16, launch key xawm) against the form without the map (pbe_ctx_attention_w_f16, xaw)
+at the shapes above, arms alternating the same way: the map stored, and the map accumulated (what the collector launches: the target is
+read as well).  One fp32 [B, tokens, Nk] target per input buffer, rotating with it: 4 Nk bytes per row written (and read) beside the
+about 6 C the kernel moves.  "spread" is (p90 - p10) / median of the arm without the map."""
 import argparse
 import os
 import sys
@@ -172,11 +179,39 @@ def regions_table(a, dev):
     return "\n".join(lines) + "\n"
 
 
+def maps_table(a, dev):
+    cell = lambda q: f"{q[1]:8.1f} [{q[0]:7.1f} .. {q[2]:7.1f}]"      # noqa: E731
+    lines = [f"# map-emitting form vs the form without the map; device: {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}); "
+             f"B = {B} samples, {H} heads",
+             f"# per launch, microseconds: median [p10 .. p90] over {a.reps} repetitions of {a.inner} back-to-back launches, arms alternating",
+             f"# pbe_ctx_attention_map_f16 (xawm: store / accumulate) vs pbe_ctx_attention_w_f16 (xaw)\n# {'M':>6} {'C':>5} {'Nk':>3} | {'xaw':>28} | "
+             f"{'xawm store':>28} | {'xawm accumulate':>28} | store/xaw  acc/xaw  spread"]
+    g = torch.Generator().manual_seed(0)
+    for M, C in SHAPES:
+        nbuf = max(2, min(16, -(-(512 << 20) // (2 * M * C))))
+        xs = [(torch.randn(M, C, generator=g) * 0.8 + 0.1).half().to(dev) for _ in range(nbuf)]
+        sts = [ops.row_stats(x) for x in xs]
+        for Nk in TOKENS:
+            oc, _ = build(M, C, Nk, dev, g)
+            ow = ops.CtxOperands(oc.kq, oc.colsum, oc.kbias, oc.vo, oc.bias, oc.H, oc.Nk, _log2w(Nk, dev, g))
+            maps = [torch.zeros(B, M // B, Nk, device=dev) for _ in range(nbuf)]
+            q = _time({"w": lambda i: ops.ctx_attention(xs[i], ow, sts[i], 1e-5, tokens=M // B),
+                       "st": lambda i: ops.ctx_attention(xs[i], ow, sts[i], 1e-5, tokens=M // B, attn_map=(maps[i], False)),
+                       "acc": lambda i: ops.ctx_attention(xs[i], ow, sts[i], 1e-5, tokens=M // B, attn_map=(maps[i], True))}, a, nbuf)
+            lines.append(f"  {M:6d} {C:5d} {Nk:3d} | {cell(q['w']):>28} | {cell(q['st']):>28} | {cell(q['acc']):>28} | {q['st'][1] / q['w'][1]:9.3f}  "
+                         f"{q['acc'][1] / q['w'][1]:7.3f}  {(q['w'][2] - q['w'][0]) / q['w'][1]:6.2f}")
+            print(lines[-1], flush=True)
+            del maps
+        del xs, sts
+    return "\n".join(lines) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--weights", action="store_true", help="time the exemplar-weight forms against the unweighted ones instead")
     ap.add_argument("--regions", action="store_true", help="time the row-weight form (xar) against the weighted form (xaw) instead")
+    ap.add_argument("--maps", action="store_true", help="time the map-emitting form (xawm, store and accumulate) against the form without the map (xaw) instead")
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -184,8 +219,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_ctx_attention.py needs an MI355X: a timing taken anywhere else says nothing")
     dev = torch.device("cuda:0")
-    if a.weights or a.regions:
-        text = regions_table(a, dev) if a.regions else weights_table(a, dev)
+    if a.weights or a.regions or a.maps:
+        text = maps_table(a, dev) if a.maps else regions_table(a, dev) if a.regions else weights_table(a, dev)
         print(text)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
