@@ -109,7 +109,10 @@ typedef struct pbe_gemm_desc {
      *  row_stats_out: float2 [column tiles][row_stats_ld] partial (sum, sumsq) of THIS launch's stored fp16 output rows, one partial per column tile
      *    (pbe_gemm_plan's out6[5] tells how many), for the LayerNorm that reads the output;
      *  VT: columns n >= vt_col0 go to VT[b * vt_bs + (n - vt_col0) * vt_rs + tok] instead of C (row m = b * vt_tokens + tok): V^T for
-     *    pbe_attention_f16 out of the same launch as q | k.  vt_col0 must be a multiple of the tile width the plan picks. */
+     *    pbe_attention_f16 out of the same launch as q | k.  The V^T columns start on a column tile: vt_col0 must be a multiple of the
+     *    width of at least one extended-epilogue tile (64, 128, 160 or 320 columns), and the plan picks among the tiles whose width divides
+     *    it (a requested tile_cfg whose width does not is replaced by one).  Any other vt_col0 is refused with PBE_EINVAL, by pbe_gemm_plan
+     *    and pbe_gemm_f16 alike, before anything is launched. */
     int32_t alpha_cols;
     const float* ln_stats;
     int32_t ln_parts;

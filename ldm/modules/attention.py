@@ -505,7 +505,10 @@ class BasicTransformerBlock(HipModule):
     fold_layernorm = True       # False: the separate LayerNorm launches of rounds 1-2 (A/B runs, tools/)
 
     def _folded(self, p, N):
-        return self.fold_layernorm and not self.linear_fp8 and p.wqkv is not None and N % 8 == 0
+        """The LayerNorm-folded chain, which starts with the fused q | k | V^T projection: only where the library can run that projection
+        (N % 8 == 0 and an inner width whose V^T columns start on a column tile, ops.qkv_fusable); other blocks take the unfused launches."""
+        return self.fold_layernorm and not self.linear_fp8 and p.wqkv is not None and N % 8 == 0 and \
+            ops.qkv_fusable(self.attn1.heads * self.attn1.dim_head, N)
 
     # The dispatch bound of pbe_ctx_attention_f16, from profiles/ctx_attention_timing.txt: at C = 320 and 640 the fused kernel takes 0.41 ..
     # 0.95 of the faster composition for 2 .. 16 tokens; at C = 1280 (M = 2048 / 512 rows at the headline batch: 32 / 8 workgroups, each

@@ -154,9 +154,10 @@ def spatial_transformer(sd: SD, p: str, x: torch.Tensor, context: torch.Tensor, 
     """attention.py:287-298: GN(eps 1e-6) -> 1x1 -> tokens -> block -> 1x1 -> + x_in."""
     b, c, hh, ww = x.shape
     h = conv(group_norm(x, sd, p + "norm", 1e-6), sd, p + "proj_in")
-    h = h.reshape(b, c, hh * ww).transpose(1, 2)
+    inner = h.shape[1]                                    # heads x dim_head (= c in the U-Net)
+    h = h.reshape(b, inner, hh * ww).transpose(1, 2)
     h = transformer_block(sd, p + "transformer_blocks.0.", h, context, heads)
-    h = h.transpose(1, 2).reshape(b, c, hh, ww)
+    h = h.transpose(1, 2).reshape(b, inner, hh, ww)
     return conv(h, sd, p + "proj_out") + x
 
 

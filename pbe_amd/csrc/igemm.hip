@@ -70,6 +70,9 @@ static int fill_gemm(const pbe_gemm_desc* d, IGemmP& p, const char* who) {
         PBE_REQUIRE(d->vt_col0 > 0 && d->vt_col0 < d->N && d->vt_tokens > 0 && d->vt_tokens % 8 == 0 && d->M % d->vt_tokens == 0 && d->vt_rs % 8 == 0 &&
                     d->vt_bs % 8 == 0 && d->vt_rs >= d->vt_tokens && al16(d->VT) && !d->resid && !geglu && d->batch == 1 && p.vec,
                     "%s: VT needs 0 < vt_col0 < N, vt_tokens %% 8 == 0 dividing M, strides %% 8 == 0, no resid / GEGLU, batch 1", who);
+        char widths[64];
+        PBE_REQUIRE(vt_tile_exists(d->vt_col0), "%s: vt_col0=%d is a multiple of no extended-epilogue tile width (%s): the V^T columns must start on a column tile",
+                    who, d->vt_col0, ex_tile_widths(widths, sizeof(widths)));
         p.vt = (h16*)d->VT; p.vt_col0 = d->vt_col0; p.vt_tok = d->vt_tokens; p.vt_bs = d->vt_bs; p.vt_rs = d->vt_rs;
     }
     PBE_REQUIRE(!ex_needed(p) || d->operand_dtype == PBE_DTYPE_F16, "%s: the extended epilogue takes fp16 operands", who);

@@ -1533,6 +1533,27 @@ static inline bool mx_tile_ok(const IGemmP& p, const TileCfg& t) {
 }
 static inline bool ex_needed(const IGemmP& p) { return p.alpha_cols > 0 || p.ln_stat || p.rstat || p.vt; }
 
+// V^T columns start on a column tile (igemm_kernel's vtile): a tile with n0 < vt_col0 stores ALL its columns to C.  The widths the
+// extended-epilogue heuristic can choose among: is one of them a divisor of vt_col0?  (A requested tile that cannot run the problem
+// falls back to the heuristic, and the forced-only A-stationary tiles are as wide as streaming ones, so this decides every tile_cfg.)
+static inline bool vt_tile_exists(int vt_col0) {
+    for (const TileCfg& t : kTiles)
+        if ((t.forms & F_EX) && !(t.forms & F_FORCED) && vt_col0 % t.bn == 0) return true;
+    return false;
+}
+static inline const char* ex_tile_widths(char* buf, size_t n) {      // "64, 128, 160, 320": the distinct widths above, ascending, for error texts
+    size_t len = 0;
+    buf[0] = 0;
+    for (int last = 0;;) {
+        int next = 0;
+        for (const TileCfg& t : kTiles)
+            if ((t.forms & F_EX) && !(t.forms & F_FORCED) && t.bn > last && (!next || t.bn < next)) next = t.bn;
+        if (!next || len + 8 > n) return buf;
+        len += snprintf(buf + len, n - len, "%s%d", len ? ", " : "", next);
+        last = next;
+    }
+}
+
 // want_cfg: -1 = heuristic; else (tile config index) | (split-K factor << 8), factor 0 = heuristic factor for that tile.
 // A requested factor is clamped to what the problem allows (batch 1, >= 4 k-tiles of 64 per slice, slabs fit the workspace).
 // (the developer knobs g_pbe_force_cfg / g_pbe_allow_splitk are READ here and never written outside pbe_tune: a caller that must

@@ -172,7 +172,8 @@ def _mx8_tile(d, mx, cfg: int) -> int:
 def _pinned(kind: str, d, mx=None, stats: bool = False) -> int:
     """tile_cfg under pinned_batch_scale: the tile and split-K factor planned for the launch at _PIN_SCALE times the batch - M of a 2-D GEMM
     (statistics planes as long as its rows), the batch count of a strided batch, B of a conv, M and every range's B of an MX copy-out (MX
-    rule applied).  A launch that cannot take that pair (other fp32 summation order, still correct) is recorded in _PIN_MISSES and warned."""
+    rule applied).  A launch that cannot take that pair, or whose row-statistics partials come from column tiles of another width (other
+    fp32 summation order, still correct) is recorded in _PIN_MISSES and warned."""
     s, big = _PIN_SCALE, type(d).from_buffer_copy(d)
     bmx = None if mx is None else type(mx).from_buffer_copy(mx)
     if kind == "conv":
@@ -196,7 +197,7 @@ def _pinned(kind: str, d, mx=None, stats: bool = False) -> int:
     small = type(d).from_buffer_copy(d)
     small.tile_cfg = hit
     got = _plan(kind, small, mx)
-    if got[1] != max(1, pl[1]):
+    if got[1] != max(1, pl[1]) or (kind == "gemm" and small.row_stats_out and got[3] != pl[3]):      # (row statistics: one partial per column tile of BN)
         import warnings
         _PIN_MISSES.append((key, pl[0], pl[1], got[0], got[1]))
         warnings.warn(f"pinned_batch_scale({s}): {key} plans tile {pl[0]} / split-K {pl[1]} at the scaled batch but the "
@@ -225,13 +226,15 @@ def _mx8_tile_cfg(d, mx, key: str, D: int) -> int:
 
 
 def _launch(kind: str, d, mx=None, row_stats=None):
-    """Launch a filled descriptor (but for tile_cfg: _tile, chosen before row_stats_out is set).  row_stats (GEMM): called with the
-    planned column-tile count once the tile is settled, returns the RowStats the epilogue fills; _launch returns it."""
+    """Launch a filled descriptor (but for tile_cfg: _tile).  row_stats (GEMM): called with the planned column-tile count once the tile is
+    settled, returns the RowStats the epilogue fills; _launch returns it.  The row-statistics form is set BEFORE the tile is chosen: every
+    plan query of _tile / _pinned (and the _PIN_CACHE key) then sees the extended-epilogue problem that launches, not a plain dense one."""
+    if row_stats is not None:
+        d.row_stats_out, d.row_stats_ld = 8, 0  # (any non-null value: the plans only need to know the form)
     key = _key(kind, d, row_stats is not None)
     d.tile_cfg = _tile(kind, d, key, mx, row_stats is not None)
     stats = None
     if row_stats is not None:                   # one partial per column tile of the plan this launch will take
-        d.row_stats_out = 8                     # (any non-null value: the plan only needs to know the form)
         stats = row_stats(_plan(kind, d)[5])
         d.row_stats_out, d.row_stats_ld = stats.ptr(), stats.ld
     if _PLANS is not None:
@@ -247,6 +250,22 @@ def _launch(kind: str, d, mx=None, row_stats=None):
         else:
             _l.check(_l.load().pbe_gemm_f16(C.byref(d), _stream()), "pbe_gemm_f16")
     return stats
+
+
+@functools.lru_cache(maxsize=None)
+def qkv_fusable(inner: int, tokens: int = 8) -> bool:
+    """Can the fused q | k | V^T projection (gemm(..., vt=..., vt_col0=2 * inner) with N = 3 * inner) run at this inner width and this
+    many tokens per sample?  Asked of the library's planner on a stand-in descriptor (host only, nothing is launched): the V^T columns
+    must start on a column tile, so 2 * inner has to be a multiple of some extended-epilogue tile width - pbe_gemm_plan refuses the rest."""
+    fake = 1 << 20                               # 16-byte aligned stand-in address, never read
+    d = _l.GemmDesc(fake, None, fake, fake, None, None, None, tokens, 3 * inner, 8, 8, 8, 0, 8, 2 * inner, 0, 0, 0, 0, 0, 0, 0, 1, 1.0, 0, 0,
+                    None, 0, -1)
+    d.alpha_cols, d.VT, d.vt_col0, d.vt_tokens, d.vt_bs, d.vt_rs = inner, fake, 2 * inner, tokens, inner * tokens, tokens
+    try:
+        _plan("gemm", d)
+        return True
+    except _l.PbeError:
+        return False
 
 
 def _splitk_ws(device):

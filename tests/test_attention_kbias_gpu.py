@@ -111,12 +111,19 @@ def test_kbias_two_query_blocks_two_tiles_per_barrier(dev):
     _gate(dev, q.cpu(), k.cpu(), v.cpu(), bias, B, H, Nq, Nk, D, what="<48,2,2> first tile absent")
 
 
-@pytest.mark.parametrize("D", [8, 64])
-def test_kbias_other_head_dims(dev, D):
+@pytest.mark.parametrize("D,qw", [(8, 0), (24, 0), (64, 0), (96, 0), (64, 2), (80, 2)], ids=["8", "24", "64", "96", "64-qw2", "80-qw2"])
+def test_kbias_other_head_dims(dev, D, qw):
+    """With the other tests, every branch of the pbe_attention_kbias_f16 dispatch: D = 24 and 96 take the 32- and 128-wide forms, and
+    ops.tune(3, 2) the 64-queries-per-wave forms of D = 64 and 80 (the heuristic takes them from 512 workgroups on)."""
+    from pbe_amd import ops
     B, H, Nq, Nk = 2, 3, 72, 130
     q, k, v = ag.attn_operands(B, H, Nq, Nk, D, 300 + D)
     bias = kr.kb_bias("middle_tile_absent", B, Nk, D)
-    _gate(dev, q, k, v, bias, B, H, Nq, Nk, D, guarded=True, what=f"D {D}")
+    try:
+        ops.tune(3, qw)
+        _gate(dev, q, k, v, bias, B, H, Nq, Nk, D, guarded=True, what=f"D {D} qw {qw}")
+    finally:
+        ops.tune(3, 0)
 
 
 def test_kbias_poison_is_live_inside_the_extent(dev):
