@@ -424,6 +424,17 @@ int pbe_plms_update(const void* eps_out, int32_t ld, int32_t dup, float cfg_scal
                     float* e_t, float* x_prev, float* pred_x0, int32_t B, int32_t HW,
                     pbe_stream_t stream);
 
+/* pbe_dpmpp_update — one step of the DPM-Solver++(2M) sampler (ldm/models/diffusion/dpm_solver.py), one launch:
+ *   e      = e_u + scale (e_c - e_u)                        (dup == 2; dup == 1: e = eps_out - the expression of the PLMS update)
+ *   x0     = (x - sigma_t e) * (1 / alpha_t)                (the data prediction: pred_x0, and the next step's history)
+ *   x_next = kx x + k0 x0 [+ k1 x0_prev]                    (first order: k1 = 0; second order: x0_prev = the previous step's x0)
+ * eps_out fp16 NHWC [dup*B, HW, ld], ld >= 4 (channels 4.. are padding, never read; with ld % 4 == 0 and an 8-byte aligned base the
+ * 4 values of a token are one read); x, x0_prev, x0_out, x_next fp32 NCHW [B,4,HW]; coef5 = {sigma_t, 1/alpha_t, kx, k0, k1} (host
+ * floats).  x0_prev may be NULL (then k1 must be 0: anything else is refused), x0_out may be NULL (the last step needs no history).
+ * fp32 throughout, every multiply-add fused: 4 roundings in x0, 7 in x_next. */
+int pbe_dpmpp_update(const void* eps_out, int32_t ld, int32_t dup, float cfg_scale, const float* x, const float* x0_prev,
+                     const float* coef5, float* x0_out, float* x_next, int32_t B, int32_t HW, pbe_stream_t stream);
+
 /* Stochastic sampler options reachable from the reference CLI (scripts/inference.py:164,342 --ddim_eta; plms.py:150-153 / ddim.py:178-181):
  * pbe_axpy_f32          y += a * x : the sigma_t * noise * temperature term of a DDIM step with eta > 0 (ddim.py:236-238);
  * pbe_qsample_blend_f32 out = (sqrt_ac x0 + sqrt_1m_ac noise) * mask + (1 - mask) * img : img_orig = q_sample(x0, ts) blended under `mask`

@@ -1,6 +1,6 @@
 // Small HBM / launch-latency bound kernels around the matrix-core ops: layout conversion at the
 // NCHW API boundary, im2col for the three tiny-Cin convs, GEGLU, timestep embedding, the fused
-// PLMS sampler update, VAE posterior sampling, CLIP patchify.
+// PLMS sampler update, the DPM-Solver++ sampler update, VAE posterior sampling, CLIP patchify.
 #include "common.h"
 #include "../../include/pbe_hip.h"
 
@@ -183,6 +183,65 @@ extern "C" int pbe_plms_update(const void* eps_out, int32_t ld, int32_t dup, flo
     hipLaunchKernelGGL(plms_update_kernel, EW_GRID(total), dim3(256), 0, s, (const h16*)eps_out, ld, dup, cfg_scale, x, h1, h2, h3, k, e_t,
                        x_prev, pred_x0, B, HW, total);
     EW_END(s, (double)total * 32.0, "pbe_plms_update");
+}
+
+// ---- DPM-Solver++(2M) sampler step (dpm_solver.py): guidance combine, data prediction, multistep update ---------------------------
+// One thread per token (b, pixel), its 4 channels there: the 4 fp16 of an eps half are one 8-byte read (VEC: ld % 4 == 0 and an
+// 8-byte aligned base, what the U-Net's output always is), the fp32 NCHW planes are read and written coalesced over the pixels.
+// Every multiply-add is an explicit fma, so the roundings per output are fixed: 4 for x0 (2 combine, 2 data prediction), 7 for x_next.
+struct DpmCoef { float sigma, inv_alpha, kx, k0, k1; };
+template <bool VEC>
+__device__ __forceinline__ void dpm_load4(const h16* p, float* e) {
+    if (VEC) {
+        const h16x4 v = *reinterpret_cast<const h16x4*>(p);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[c] = (float)v[c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[c] = (float)p[c];
+    }
+}
+template <bool VEC>
+__global__ void dpmpp_update_kernel(const h16* eps, int ld, int dup, float cfg, const float* x, const float* x0_prev, DpmCoef k,
+                                    float* x0_out, float* x_next, int HW, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;     // over B*HW tokens
+    if (i >= total) return;
+    const long b = i / HW, px = i - b * HW;
+    float e[4];
+    dpm_load4<VEC>(eps + i * ld, e);
+    if (dup == 2) {                                          // [uncond | cond] halves, B*HW tokens apart
+        float ec[4];
+        dpm_load4<VEC>(eps + (total + i) * ld, ec);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[c] = __builtin_fmaf(cfg, ec[c] - e[c], e[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const long j = (b * 4 + c) * HW + px;
+        const float xv = x[j];
+        const float x0 = __builtin_fmaf(-k.sigma, e[c], xv) * k.inv_alpha;
+        float xn = __builtin_fmaf(k.k0, x0, k.kx * xv);
+        if (x0_prev) xn = __builtin_fmaf(k.k1, x0_prev[j], xn);
+        if (x0_out) x0_out[j] = x0;
+        x_next[j] = xn;
+    }
+}
+extern "C" int pbe_dpmpp_update(const void* eps_out, int32_t ld, int32_t dup, float cfg_scale, const float* x, const float* x0_prev,
+                                const float* coef5, float* x0_out, float* x_next, int32_t B, int32_t HW, pbe_stream_t stream) {
+    PBE_REQUIRE(eps_out && x && coef5 && x_next && B > 0 && HW > 0 && ld >= 4 && (dup == 1 || dup == 2), "pbe_dpmpp_update: bad arguments");
+    PBE_REQUIRE(x0_prev || coef5[4] == 0.f, "pbe_dpmpp_update: k1 != 0 needs x0_prev (the second-order term has no operand)");
+    const DpmCoef k = {coef5[0], coef5[1], coef5[2], coef5[3], coef5[4]};
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)B * HW;
+    const bool vec = ld % 4 == 0 && ((uintptr_t)eps_out & 7) == 0;
+    EW_BEGIN(s);
+    if (vec)
+        hipLaunchKernelGGL(dpmpp_update_kernel<true>, EW_GRID(total), dim3(256), 0, s, (const h16*)eps_out, ld, dup, cfg_scale, x, x0_prev, k,
+                           x0_out, x_next, HW, total);
+    else
+        hipLaunchKernelGGL(dpmpp_update_kernel<false>, EW_GRID(total), dim3(256), 0, s, (const h16*)eps_out, ld, dup, cfg_scale, x, x0_prev, k,
+                           x0_out, x_next, HW, total);
+    EW_END(s, (double)total * (8.0 * dup + 32.0 + (x0_prev ? 16.0 : 0.0) + (x0_out ? 16.0 : 0.0)), "pbe_dpmpp_update");
 }
 
 // ---- stochastic sampler options: DDIM eta > 0 noise term (ddim.py:226-238), mask / x0 blending through q_sample (plms.py:150-153) ----

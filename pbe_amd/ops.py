@@ -1024,6 +1024,33 @@ def plms_update(eps_out: torch.Tensor, dup: int, cfg_scale: float, x: torch.Tens
     return x_prev, pred, e_t
 
 
+def dpmpp_update(eps_out: torch.Tensor, dup: int, cfg_scale: float, x: torch.Tensor, x0_prev: Optional[torch.Tensor], coef5,
+                 want_pred: bool = True):
+    """One DPM-Solver++(2M) step in one launch: CFG combine, x0 = (x - sigma_t e) / alpha_t, x_next = kx x + k0 x0 [+ k1 x0_prev].
+    eps_out fp16 NHWC [dup*B, H, W, ld >= 4], x / x0_prev fp32 NCHW [B, 4, H, W] (x0_prev None: first-order step, k1 must be 0),
+    coef5 = (sigma_t, 1/alpha_t, kx, k0, k1) -> (x_next, x0); x0 is None with want_pred=False (the last step keeps no history)."""
+    _h(eps_out, "dpmpp eps_out"); _f(x, "dpmpp x")
+    if dup not in (1, 2) or len(coef5) != 5:
+        raise _l.PbeError(f"dpmpp_update: dup must be 1 or 2 and coef5 five floats, got dup={dup}, {len(coef5)} coefficients")
+    if x.dim() != 4 or x.shape[1] != 4 or not x.is_contiguous():
+        raise _l.PbeError(f"dpmpp_update: x must be contiguous fp32 NCHW [B, 4, H, W], got {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    if eps_out.dim() != 4 or tuple(eps_out.shape[:3]) != (dup * B, H, W) or eps_out.shape[3] < 4 or not eps_out.is_contiguous() or eps_out.device != x.device:
+        raise _l.PbeError(f"dpmpp_update: eps_out must be contiguous fp16 NHWC [{dup * B}, {H}, {W}, ld >= 4] on x's device, got {tuple(eps_out.shape)}")
+    if x0_prev is not None:
+        _f(x0_prev, "dpmpp x0_prev")
+        if x0_prev.shape != x.shape or not x0_prev.is_contiguous() or x0_prev.device != x.device:
+            raise _l.PbeError(f"dpmpp_update: x0_prev must match x ({tuple(x.shape)}, contiguous, same device), got {tuple(x0_prev.shape)}")
+    elif float(coef5[4]) != 0.0:
+        raise _l.PbeError("dpmpp_update: k1 != 0 needs x0_prev")
+    x0 = torch.empty_like(x) if want_pred else None
+    x_next = torch.empty_like(x)
+    arr = (C.c_float * 5)(*[float(v) for v in coef5])
+    _l.check(_l.load().pbe_dpmpp_update(_p(eps_out), eps_out.shape[3], dup, float(cfg_scale), _p(x), _p(x0_prev), arr, _p(x0), _p(x_next),
+                                        B, H * W, _stream()), "pbe_dpmpp_update")
+    return x_next, x0
+
+
 def axpy_(y: torch.Tensor, a: float, x: torch.Tensor) -> torch.Tensor:
     """y += a * x in place (fp32): the sigma_t * noise term of a stochastic DDIM step (ddim.py:236-238)."""
     _f(y, "axpy y"); _f(x, "axpy x")

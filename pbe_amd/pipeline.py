@@ -73,6 +73,7 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     exemplars per sample, with ref_weights [B, K] their non-negative weights or None and ref_regions [B, K, Hr, Wr] >= 0 where each of
     them applies - 1 = fully, 0 = not there; the latent grid and its halvings down to the coarsest attention level must divide
     Hr x Wr - or None); everything on the model's GPU.  Returns {'image' [B,3,H,W] in [0,1], 'latent', 'c', 'z_inpaint', 'mask_lat'}.
+    sampler: "plms" (S + 1 U-Net calls), "dpm" (DPM-Solver++(2M), `steps` calls: about 20 do where the others take 50) or anything else: DDIM.
     return_ref_maps: also 'ref_maps' fp32 [B, K, h, w] on the latent grid - the share of cross-attention each exemplar received at each
     position, averaged over heads, blocks, sampler steps and levels (ldm.modules.attention.ContextMaps; K = 1: ones).  Collecting them
     sends every level through the fused cross-attention kernel: with ref_regions the picture is the one without return_ref_maps bit for
@@ -95,7 +96,11 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     m_lat = resize_mask(mask, z_inp.shape[-2:], antialias)                               # inference.py:332
     if ev:
         ev[2].record()
-    smp = (PLMSSampler if sampler == "plms" else DDIMSampler)(model)
+    if sampler == "dpm":                                                                 # DPM-Solver++(2M): `steps` U-Net calls
+        from ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        smp = DPMSolverSampler(model)
+    else:
+        smp = (PLMSSampler if sampler == "plms" else DDIMSampler)(model)
     more = {} if ref_regions is None else {"conditioning_regions": ref_regions}
     cm = None
     if return_ref_maps:

@@ -169,8 +169,11 @@ def iter_loaded(ds: COCOImageDataset, batches, pool: cf.ThreadPoolExecutor) -> I
 @torch.no_grad()
 def run_sweep(model, ds: COCOImageDataset, outdir: str, *, batch_size: int, steps: int = 50, scale: float = 1.0, plms: bool = False,
               fixed_code: bool = False, seed: int = 42, rank: int = 0, world: int = 1, skip_save: bool = False, C: int = 4, f: int = 8,
-              antialias: bool = True, max_batches: Optional[int] = None, io_threads: int = 4) -> Dict[str, object]:
-    """The loop of inference_test_bench.py:316-400 for this rank's share of the id list.  Returns counters."""
+              antialias: bool = True, max_batches: Optional[int] = None, io_threads: int = 4, dpm_solver: bool = False) -> Dict[str, object]:
+    """The loop of inference_test_bench.py:316-400 for this rank's share of the id list.  Returns counters.  dpm_solver: sample with
+    DPM-Solver++(2M) (`steps` U-Net calls) instead of PLMS / DDIM; it excludes plms."""
+    if plms and dpm_solver:
+        raise ValueError("run_sweep: plms and dpm_solver are mutually exclusive")
     from .pipeline import inpaint
     for d in ("samples", "results", "grid"):
         os.makedirs(os.path.join(outdir, d), exist_ok=True)
@@ -194,7 +197,7 @@ def run_sweep(model, ds: COCOImageDataset, outdir: str, *, batch_size: int, step
                     start_code = batch_noise(seed, -1, batch_size, C, H // f, W // f)["x_T"]
                 noise["x_T"] = start_code
             out = inpaint(model, t["image"], t["mask"], t["ref"], steps=steps, scale=scale, x_T=noise["x_T"].to(dev),
-                          post_eps=noise["post_eps"].to(dev), sampler="plms" if plms else "ddim", antialias=antialias)
+                          post_eps=noise["post_eps"].to(dev), sampler="dpm" if dpm_solver else ("plms" if plms else "ddim"), antialias=antialias)
             res_u8 = device_pack_u8(out["image"]).cpu().numpy()
             for i, it in enumerate(items):
                 writes.append(pool.submit(write_item, outdir, it[3], it[0], it[2], it[1], res_u8[i], skip_save))

@@ -7,6 +7,8 @@ sampler -> decode -> clamp) and the same output tree, running on the MI355X HIP 
         --image_path examples/image/example_1.png --mask_path examples/mask/example_1.png \
         --reference_path examples/reference/example_1.jpg --seed 321 --scale 5
 
+`--dpm_solver` (upstream Stable Diffusion's flag, not in the reference; excludes `--plms`) samples with DPM-Solver++(2M): `--ddim_steps`
+U-Net calls, so `--ddim_steps 20` is 20 calls where `--plms` makes 51 at its default.
 `--reference_path` may name several images (not in the reference): each becomes one context token of the sample.
 `--reference_weight w1 w2 ...` gives each of them a non-negative weight (default: all 1): its share of the cross-attention is
 proportional to w exp(score), so `2 1` equals naming the first image twice and `1 0` equals naming the first image alone.
@@ -39,6 +41,8 @@ def parse(argv=None):
     p.add_argument("--skip_save", action="store_true")
     p.add_argument("--ddim_steps", type=int, default=50)
     p.add_argument("--plms", action="store_true")
+    p.add_argument("--dpm_solver", action="store_true", help="(upstream Stable Diffusion's flag, not in the reference) sample with "
+                   "DPM-Solver++(2M): --ddim_steps U-Net calls, about 20 where PLMS / DDIM take 50; excludes --plms")
     p.add_argument("--fixed_code", action="store_true")
     p.add_argument("--ddim_eta", type=float, default=0.0)
     p.add_argument("--n_iter", type=int, default=2)
@@ -68,6 +72,10 @@ def parse(argv=None):
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
     opt = p.parse_args(argv)
+    if opt.plms and opt.dpm_solver:
+        p.error("--plms and --dpm_solver are mutually exclusive: name one sampler")
+    if opt.dpm_solver and opt.ddim_eta != 0.0:
+        p.error("--dpm_solver runs with --ddim_eta 0 (the stochastic variant is not built)")
     if opt.reference_weight is not None:
         w, refs = opt.reference_weight, opt.reference_path if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
         if len(w) != len(refs):
@@ -143,7 +151,11 @@ def main(argv=None):
         model = load_model_from_config(config, None, device="cpu")
         weights.fill_latent_diffusion_(model, seed=0)
         model = model.to(device).eval()
-    sampler = PLMSSampler(model) if opt.plms else DDIMSampler(model)
+    if opt.dpm_solver:
+        from ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        sampler = DPMSolverSampler(model)
+    else:
+        sampler = PLMSSampler(model) if opt.plms else DDIMSampler(model)
 
     start_code = None
     if opt.fixed_code:

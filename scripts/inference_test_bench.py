@@ -33,6 +33,7 @@ def parse(argv=None):
     p.add_argument("--skip_save", action="store_true")
     p.add_argument("--ddim_steps", type=int, default=50)
     p.add_argument("--plms", action="store_true")
+    p.add_argument("--dpm_solver", action="store_true", help="(not in the reference) DPM-Solver++(2M) with --ddim_steps U-Net calls; excludes --plms")
     p.add_argument("--laion400m", action="store_true")
     p.add_argument("--fixed_code", action="store_true")
     p.add_argument("--ddim_eta", type=float, default=0.0)
@@ -53,7 +54,10 @@ def parse(argv=None):
     p.add_argument("--test_bench_dir", type=str, default="test_bench")
     p.add_argument("--random_weights", action="store_true")
     p.add_argument("--max_batches", type=int, default=None)
-    return p.parse_args(argv)
+    opt = p.parse_args(argv)
+    if opt.plms and opt.dpm_solver:
+        p.error("--plms and --dpm_solver are mutually exclusive: name one sampler")
+    return opt
 
 
 def main(argv=None):
@@ -87,7 +91,7 @@ def main(argv=None):
     ds = testbench.COCOImageDataset(opt.test_bench_dir)
     if rank == 0:
         print("length of test bench", len(ds))
-    stats = testbench.run_sweep(model, ds, opt.outdir, batch_size=opt.n_samples, steps=opt.ddim_steps, scale=opt.scale, plms=opt.plms,
+    stats = testbench.run_sweep(model, ds, opt.outdir, batch_size=opt.n_samples, steps=opt.ddim_steps, scale=opt.scale, plms=opt.plms, dpm_solver=opt.dpm_solver,
                                 fixed_code=opt.fixed_code, seed=opt.seed, rank=rank, world=world, skip_save=opt.skip_save, C=opt.C, f=opt.f,
                                 max_batches=opt.max_batches)
     if world > 1:
