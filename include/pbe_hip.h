@@ -486,7 +486,39 @@ int pbe_mul_planes_f32(const float* x, const float* m, float* out, int32_t B, in
 int pbe_planes_to_u8_canvas(const float* src, void* canvas, int32_t H, int32_t W, int32_t Hc, int32_t Wc, int32_t y0, int32_t x0,
                             const float* a3, const float* b3, int32_t bcast, pbe_stream_t stream);
 
-/* pbe_tune — developer knobs for A/B runs in one process (never needed for correctness):
+/* Windowed pre/post-processing (pbe_amd/csrc/window.hip; not in the reference): inpaint a region of a picture of any size and paste it
+ * back.  picture: u8 [Hs, Ws, 3] contiguous; mask: u8 [Hs, Ws], a byte >= 128 is the hole; window (y0, x0, wh, ww) inside the picture;
+ * working size (H, W).  Edges up to 16384.  One picture per call.
+ * AA(src, (h, w) -> (h', w')) below is the antialiased triangle filter of pbe_resize_bilinear_f32 (ATen upsample_bilinear2d_aa), per axis
+ * n -> n': scale s = n / n', support sup = max(s, 1), centre c = s (o + 0.5), taps lo = max((int)(c - sup + 0.5), 0) ..
+ * min((int)(c + sup + 0.5), n) - 1, weight_j = max(1 - |j + 0.5 - c| / sup, 0) / (their sum) - evaluated in integers: with den = 2 max(n, n'),
+ * wnum_j = max(den - |(2j + 1) n' - (2o + 1) n|, 0) and weight_j = (float)wnum_j / (float)(sum_j wnum_j), so neither the tap range nor a
+ * weight carries a coordinate rounding and at n = n' the filter is exactly the identity.  out = sum_k wy_k * (sum_j src[k, j] * wx_j): row
+ * sums first, one fmaf per tap in tap order (r = fmaf(v, wx, r), then acc = fmaf(r, wy, acc)), weights recomputed per tap (no tap cap,
+ * no scratch).
+ * pbe_window_image_u8_f32    dst[c, Y, X] = (AA(window bytes / 255, (wh, ww) -> (H, W))[c] - mean[c]) / std[c], fp32 [3, H, W]; taps outside
+ *                            the window are clipped as at an image edge; v / 255, the subtraction and the division are IEEE fp32 in the order
+ *                            of pbe_u8_to_planes_f32, so a window of the working size gives that kernel's bits.
+ * pbe_window_mask_u8_f32     dst[0, Y, X] = 0 if any mask byte >= 128 lies in window rows (Y*wh)/H .. ceil((Y+1)*wh/H) - 1 and the columns
+ *                            likewise (integer arithmetic), else 1; fp32 [1, H, W].  Exact; at wh = H, ww = W it is binarize = 1 above.
+ * pbe_feather_alpha_f32      alpha[y, x] = (float)box_r(dilate_r(hole))(y0 + y, x0 + x) / (float)(2r+1)^2, fp32 [wh, ww]: dilate_r = maximum and
+ *                            box_r = integer count over the (2r+1)^2 square, both on picture coordinates clamped to the picture (replicate
+ *                            padding; they read the mask beyond the window); one IEEE division.  0 <= r <= 2047.  Four separable passes
+ *                            through `workspace`, at least pbe_feather_alpha_workspace_bytes(wh, ww, r) bytes of device scratch.
+ * pbe_paste_window_u8        for every window pixel with alpha > 0 and each channel: res = AA(result, (H, W) -> (wh, ww)), o = byte / 255,
+ *                            v = fmaf(alpha, res, (1 - alpha) * o), byte = rint(255 * clamp(v, 0, 1)) (half to even); result fp32 [3, H, W].
+ *                            Pixels with alpha == 0 and everything outside the window are not written. */
+int pbe_window_image_u8_f32(const void* picture, float* dst, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
+                            int32_t H, int32_t W, const float* mean3, const float* std3, pbe_stream_t stream);
+int pbe_window_mask_u8_f32(const void* mask, float* dst, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
+                           int32_t H, int32_t W, pbe_stream_t stream);
+size_t pbe_feather_alpha_workspace_bytes(int32_t wh, int32_t ww, int32_t r);
+int pbe_feather_alpha_f32(const void* mask, float* alpha, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww, int32_t r,
+                          void* workspace, size_t workspace_bytes, pbe_stream_t stream);
+int pbe_paste_window_u8(const float* result, const float* alpha, void* picture, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh,
+                        int32_t ww, int32_t H, int32_t W, pbe_stream_t stream);
+
+/* pbe_tune— developer knobs for A/B runs in one process (never needed for correctness):
  * key 1: force an implicit-GEMM tile config index (-1 = heuristic); key 2: allow split-K (0/1);
  * key 3: attention queries-per-wave factor (0 = heuristic, 1, 2); key 4: ping-pong main loop of the halo-resident conv tiles (0/1);
  * key 5: per-launch choice of the XCD tile order (m fastest where that fetches fewer bytes into the 8 L2s; 0 = always n fastest);

@@ -1158,6 +1158,91 @@ def planes_to_canvas(src: torch.Tensor, canvas: torch.Tensor, y0: int, x0: int, 
                                                _stream()), "pbe_planes_to_u8_canvas")
 
 
+# ---- windowed pre/post-processing (csrc/window.hip): one picture per call ---------------------------------------------------------
+def _window_args(what: str, plane: torch.Tensor, channels: int, window) -> Tuple[int, int, int, int, int, int]:
+    """(Hs, Ws, y0, x0, wh, ww) of a contiguous uint8 [Hs, Ws, 3] picture (channels = 3) or [Hs, Ws] mask (channels = 1) on the GPU and a
+    window (y0, x0, wh, ww) of integers inside it."""
+    _req(plane, torch.uint8, f"{what}")
+    if plane.dim() != (3 if channels == 3 else 2) or (channels == 3 and plane.shape[2] != 3) or not plane.is_contiguous() or plane.numel() == 0:
+        raise _l.PbeError(f"{what}: expected a contiguous uint8 {'[Hs, Ws, 3] picture' if channels == 3 else '[Hs, Ws] mask'}, got {tuple(plane.shape)} "
+                          f"with strides {tuple(plane.stride())}")
+    Hs, Ws = int(plane.shape[0]), int(plane.shape[1])
+    try:
+        y0, x0, wh, ww = (int(v) for v in window)
+        exact = all(int(v) == v for v in window)
+    except (TypeError, ValueError) as e:
+        raise _l.PbeError(f"{what}: the window must be four integers (y0, x0, wh, ww), got {window!r}") from e
+    if not exact or y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > Hs or x0 + ww > Ws:
+        raise _l.PbeError(f"{what}: window (y0, x0, wh, ww) = {tuple(window)} is not inside the {Hs} x {Ws} picture")
+    return Hs, Ws, y0, x0, wh, ww
+
+
+def _window_out(what: str, out: Optional[torch.Tensor], shape, device) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    _f(out, f"{what} out")
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise _l.PbeError(f"{what}: out must be a contiguous fp32 {tuple(shape)} tensor on {device}, got {tuple(out.shape)}")
+    return out
+
+
+def window_image(picture: torch.Tensor, window, size, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [Hs, Ws, 3] picture, window (y0, x0, wh, ww) -> fp32 [3, H, W] at the working size `size` = (H, W): the antialiased triangle
+    filter (pbe_resize_bilinear_f32's, any scale) over bytes / 255 of the window alone, then (v - mean) / std.  A window of the working
+    size gives u8_to_planes of the cropped bytes bit for bit."""
+    Hs, Ws, y0, x0, wh, ww = _window_args("window_image picture", picture, 3, window)
+    H, W = int(size[0]), int(size[1])
+    y = _window_out("window_image", out, (3, H, W), picture.device)
+    m, sd = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    _l.check(_l.load().pbe_window_image_u8_f32(_p(picture), _p(y), Hs, Ws, y0, x0, wh, ww, H, W, m, sd, _stream()), "pbe_window_image_u8_f32")
+    return y
+
+
+def window_mask(mask: torch.Tensor, window, size, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [Hs, Ws] mask (a byte >= 128 is the hole), window -> the keep plane fp32 [1, H, W] in {0, 1}: working pixel (Y, X) is 0 iff a
+    hole byte lies in window rows (Y wh) // H .. ceil((Y + 1) wh / H) - 1 and the columns likewise.  No filter: exact, no hole pixel is
+    lost at any scale; at the working size it is u8_to_planes(mask_mode=1)."""
+    Hs, Ws, y0, x0, wh, ww = _window_args("window_mask mask", mask, 1, window)
+    H, W = int(size[0]), int(size[1])
+    y = _window_out("window_mask", out, (1, H, W), mask.device)
+    _l.check(_l.load().pbe_window_mask_u8_f32(_p(mask), _p(y), Hs, Ws, y0, x0, wh, ww, H, W, _stream()), "pbe_window_mask_u8_f32")
+    return y
+
+
+def feather_alpha(mask: torch.Tensor, window, feather: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [Hs, Ws] mask, window, r = feather >= 0 -> alpha fp32 [wh, ww] = box_r(dilate_r(hole)) / (2r + 1)^2 with replicate padding at
+    the picture's border: 1 on the hole, > 0 exactly within Chebyshev distance 2r of it, 0 beyond; r = 0 is the hole itself."""
+    Hs, Ws, y0, x0, wh, ww = _window_args("feather_alpha mask", mask, 1, window)
+    r = int(feather)
+    if r != feather or r < 0 or r > 2047:
+        raise _l.PbeError(f"feather_alpha: feather must be an integer in 0 .. 2047, got {feather!r}")
+    y = _window_out("feather_alpha", out, (wh, ww), mask.device)
+    lib = _l.load()
+    need = lib.pbe_feather_alpha_workspace_bytes(wh, ww, r)
+    key = (mask.device.index, "feather")
+    ws = _ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=mask.device)
+        _ws[key] = ws
+    _l.check(lib.pbe_feather_alpha_f32(_p(mask), _p(y), Hs, Ws, y0, x0, wh, ww, r, _p(ws), ws.numel(), _stream()), "pbe_feather_alpha_f32")
+    return y
+
+
+def paste_window(result: torch.Tensor, alpha: torch.Tensor, picture: torch.Tensor, window) -> torch.Tensor:
+    """result fp32 [3, H, W] in [0, 1] (one image of image_post), alpha fp32 [wh, ww], window -> `picture` (uint8 [Hs, Ws, 3]) changed IN
+    PLACE and returned: where alpha > 0, byte = rint(255 clamp(fma(alpha, res, (1 - alpha) byte / 255), 0, 1)) with res the antialiased
+    filter of result to (wh, ww).  Where alpha == 0 and outside the window no byte is written."""
+    Hs, Ws, y0, x0, wh, ww = _window_args("paste_window picture", picture, 3, window)
+    _f(result, "paste_window result"); _f(alpha, "paste_window alpha")
+    if result.dim() != 3 or result.shape[0] != 3 or not result.is_contiguous() or result.device != picture.device:
+        raise _l.PbeError(f"paste_window: result must be a contiguous fp32 [3, H, W] tensor on the picture's device, got {tuple(result.shape)}")
+    if tuple(alpha.shape) != (wh, ww) or not alpha.is_contiguous() or alpha.device != picture.device:
+        raise _l.PbeError(f"paste_window: alpha must be a contiguous fp32 [{wh}, {ww}] tensor on the picture's device, got {tuple(alpha.shape)}")
+    _l.check(_l.load().pbe_paste_window_u8(_p(result), _p(alpha), _p(picture), Hs, Ws, y0, x0, wh, ww, int(result.shape[1]), int(result.shape[2]),
+                                           _stream()), "pbe_paste_window_u8")
+    return picture
+
+
 def bcast_row(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, B: int, y_bs: int) -> None:
     """out[bi * y_bs + c] = a[c] + b[c] for bi < B."""
     _h(a, "bcast_row a"); _h(b, "bcast_row b"); _h(out, "bcast_row out")

@@ -124,6 +124,51 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     return out
 
 
+def window_inputs(pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], windows: Sequence, size) -> Dict[str, torch.Tensor]:
+    """The stacked model inputs of inpaint_window: {'image' [B,3,H,W] in [-1,1], 'mask' [B,1,H,W] in {0,1}, 'inpaint' = image * mask},
+    sample i from windows[i] of pictures[i] / masks[i] (ops.window_image, ops.window_mask, ops.mul_planes: HIP kernels only)."""
+    B, (H, W), dev = len(pictures), (int(size[0]), int(size[1])), pictures[0].device
+    image = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    for i in range(B):
+        ops.window_image(pictures[i], windows[i], (H, W), out=image[i])
+        ops.window_mask(masks[i], windows[i], (H, W), out=mask[i])
+    return {"image": image, "mask": mask, "inpaint": ops.mul_planes(image, mask)}
+
+
+@torch.no_grad()
+def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], ref: torch.Tensor, *, size=(512, 512), context=0.5,
+                   feather: int = 8, windows: Optional[Sequence] = None, **inpaint_kwargs) -> Dict[str, object]:
+    """Inpaint a region of pictures of any size and paste it back in place.  pictures: per sample a uint8 [Hs, Ws, 3] tensor, masks: a
+    uint8 [Hs, Ws] tensor of the same Hs x Ws (a byte >= 128 is the hole), both contiguous and on the model's GPU; the sizes may differ
+    from sample to sample.  Per sample ONE window is planned around the hole (pbe_amd.window.plan_window with `size`, `context`,
+    `feather`; or windows[i] = (y0, x0, wh, ww), validated), brought to the working size `size` = (H, W) (ops.window_image /
+    ops.window_mask), and the stacked batch goes through the unchanged `inpaint`, which receives **inpaint_kwargs as they are (steps,
+    scale, sampler, x_T, post_eps, ref_weights, ref_regions, return_ref_maps ...).  The result is resampled to the window and blended
+    into a CLONE of each picture under alpha = ops.feather_alpha(mask, window, feather) by ops.paste_window: every byte with
+    alpha == 0 - all of the picture farther than 2 feather from the hole - keeps its value, and with the planner's margin alpha is 0 on
+    every window border inside the picture, so no seam shows.
+    Returns inpaint's dict ('image', 'latent', ... at the working size) plus 'pictures' (list of uint8 [Hs, Ws, 3]), 'windows' (list of
+    (y0, x0, wh, ww)), 'alphas' (list of fp32 [wh, ww]) and 'inputs' (window_inputs: what the model saw).  ref_regions and 'ref_maps' stay
+    on the WINDOW's grid: a region map describes the window at the working size, not the picture, and the attribution maps come back on
+    the window's latent grid."""
+    from . import window as _w
+    B = len(pictures)
+    if B == 0 or len(masks) != B or (windows is not None and len(windows) != B):
+        raise PbeError(f"inpaint_window: {B} pictures, {len(masks)} masks" + ("" if windows is None else f", {len(windows)} windows"))
+    for i, (p, m) in enumerate(zip(pictures, masks)):
+        if not isinstance(p, torch.Tensor) or not isinstance(m, torch.Tensor) or p.dim() != 3 or m.dim() != 2 or tuple(p.shape[:2]) != tuple(m.shape):
+            raise PbeError(f"inpaint_window: sample {i} needs a uint8 [Hs, Ws, 3] picture and a uint8 [Hs, Ws] mask of one size")
+    wins = [_w.plan_window(masks[i], size, context, feather, None if windows is None else windows[i]) for i in range(B)]
+    inputs = window_inputs(pictures, masks, wins, size)
+    out: Dict[str, object] = dict(inpaint(model, inputs["image"], inputs["mask"], ref, **inpaint_kwargs))
+    alphas = [ops.feather_alpha(masks[i], wins[i], feather) for i in range(B)]
+    result = out["image"].float().contiguous()
+    out["pictures"] = [ops.paste_window(result[i], alphas[i], pictures[i].clone(), wins[i]) for i in range(B)]
+    out["windows"], out["alphas"], out["inputs"] = wins, alphas, inputs
+    return out
+
+
 def ref_maps_u8(ref_maps: torch.Tensor, size, antialias: bool = True) -> torch.Tensor:
     """Attribution maps fp32 [B, K, h, w] in [0, 1] -> uint8 [B, K, H, W] at the picture size `size` = (H, W): resized on the device
     (pbe_resize_bilinear_f32, as the mask is) and quantised as round(255 * map).  What --save_reference_maps writes, one PNG per plane."""

@@ -1,0 +1,89 @@
+"""Window planning for inpainting a region of a picture of any size (pipeline.inpaint_window): which rectangle of the picture goes
+through the model.  Host side, integers only - the pixels are handled by the kernels of csrc/window.hip (ops.window_image,
+ops.window_mask, ops.feather_alpha, ops.paste_window)."""
+from __future__ import annotations
+
+from fractions import Fraction
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+from .lib import PbeError
+
+HOLE = 128          # a mask byte >= 128 is the hole: the byte form of the (1 - v / 255) < 0.5 threshold of preprocess.load_triple
+Window = Tuple[int, int, int, int]
+
+
+def _ceil_div(a: int, b: int) -> int:
+    return -((-a) // b)
+
+
+def _host_mask(mask_u8) -> np.ndarray:
+    if hasattr(mask_u8, "detach"):                         # a torch tensor, on any device
+        mask_u8 = mask_u8.detach().cpu().numpy()
+    m = np.asarray(mask_u8)
+    if m.ndim != 2 or m.dtype != np.uint8 or m.size == 0:
+        raise PbeError(f"plan_window: the mask must be a non-empty uint8 [Hs, Ws] array, got {m.dtype} {m.shape}")
+    return m
+
+
+def hole_box(mask_u8) -> Tuple[int, int, int, int]:
+    """(ya, yb, xa, xb), inclusive: the bounding box of the bytes >= 128.  An empty hole raises."""
+    hole = _host_mask(mask_u8) >= HOLE
+    rows, cols = np.flatnonzero(hole.any(1)), np.flatnonzero(hole.any(0))
+    if rows.size == 0:
+        raise PbeError("plan_window: the mask has no hole (no byte >= 128): nothing to inpaint")
+    return int(rows[0]), int(rows[-1]), int(cols[0]), int(cols[-1])
+
+
+def validate_window(window, picture_hw: Sequence[int]) -> Window:
+    """window as four Python ints (y0, x0, wh, ww), or PbeError if they are not integers or not inside the Hs x Ws picture."""
+    Hs, Ws = int(picture_hw[0]), int(picture_hw[1])
+    try:
+        vals = tuple(window)
+        y0, x0, wh, ww = (int(v) for v in vals)
+        ok = len(vals) == 4 and all(int(v) == v for v in vals)
+    except (TypeError, ValueError) as e:
+        raise PbeError(f"window: expected four integers (y0, x0, wh, ww), got {window!r}") from e
+    if not ok or y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > Hs or x0 + ww > Ws:
+        raise PbeError(f"window (y0, x0, wh, ww) = {window!r} is not inside the {Hs} x {Ws} picture")
+    return y0, x0, wh, ww
+
+
+def plan_window(mask_u8, working: Sequence[int], context=0.5, feather: int = 8, window: Optional[Sequence[int]] = None) -> Window:
+    """The window (y0, x0, wh, ww) of the picture to inpaint at the working size `working` = (H, W), from the hole's bounding box
+    bh x bw (rows ya .. yb, columns xa .. xb), r = feather and m = 2r + 1:
+
+      need_h = bh + 2 max(m, ceil(context bh)), need_w likewise: the box plus `context` of its size, and never less than the width m of
+               the feather (ops.feather_alpha is positive up to 2r from the hole), on each side;
+      the smallest window of aspect H : W that holds need_h x need_w: (need_h, ceil(need_h W / H)) if need_h W >= need_w H, else
+               (ceil(need_w H / W), need_w);
+      never smaller than (H, W): the crop is not magnified when the picture allows it;
+      clamped per dimension to the picture (Hs, Ws).  A picture too small in one dimension therefore gives an ANISOTROPIC window: its
+               aspect is no longer H : W and the two axes are resampled by different factors (the kernels take any pair of scales);
+      centred on the box: y0 = floor((ya + yb + 1 - wh) / 2) shifted into [0, Hs - wh], x0 likewise.
+
+    So the window lies in the picture, the box lies in the window with a margin >= m on every side that is not the picture's border
+    (where alpha is therefore 0), and a picture of exactly the working size gives the whole picture.  Integer arithmetic throughout
+    (context is taken as the exact rational value of the float).  An empty hole raises PbeError.  `window`: a caller's own window, only
+    validated (four integers inside the picture) and returned."""
+    m8 = _host_mask(mask_u8)
+    Hs, Ws = m8.shape
+    if window is not None:
+        return validate_window(window, (Hs, Ws))
+    H, W = int(working[0]), int(working[1])
+    r = int(feather)
+    if H < 1 or W < 1 or r != feather or r < 0 or not (context >= 0) or context == float("inf"):
+        raise PbeError(f"plan_window: working size {tuple(working)!r} must be positive, feather {feather!r} an integer >= 0, context {context!r} finite and >= 0")
+    ya, yb, xa, xb = hole_box(m8)
+    bh, bw, m, ctx = yb - ya + 1, xb - xa + 1, 2 * r + 1, Fraction(context)
+    need_h = bh + 2 * max(m, int(-((-ctx * bh) // 1)))
+    need_w = bw + 2 * max(m, int(-((-ctx * bw) // 1)))
+    if need_h * W >= need_w * H:
+        wh, ww = need_h, _ceil_div(need_h * W, H)
+    else:
+        wh, ww = _ceil_div(need_w * H, W), need_w
+    wh, ww = min(max(wh, H), Hs), min(max(ww, W), Ws)
+    y0 = min(max((ya + yb + 1 - wh) // 2, 0), Hs - wh)
+    x0 = min(max((xa + xb + 1 - ww) // 2, 0), Ws - ww)
+    return y0, x0, wh, ww

@@ -18,6 +18,12 @@ weighted by region x weight; a position that no region covers blends them by the
 `--save_reference_maps` writes, beside the result, one 8-bit grayscale PNG per reference into `<outdir>/reference_maps/`, named after
 the result file with `_ref<j>`: the share of cross-attention that reference received at each position of the picture (white = all of
 it), averaged over heads, blocks, sampler steps and levels - whether a region "took", which exemplar wins where.
+`--paste_back` (not in the reference) lets `--image_path` / `--mask_path` be a picture of ANY size: one window around the hole (the
+hole's box plus `--context` of its size and the feather's width on each side, at the aspect of `--H` x `--W`, never smaller than
+`--H` x `--W` where the picture allows) is brought to `--H` x `--W` on the device and goes through the model; `source/`, `results/`
+and `grid/` show that window as before, and `pasted/<stem>_<seed>.png` is the whole picture with the result blended in under a mask
+feathered over `--feather` pixels (default 8): every pixel farther than 2 x feather from the hole keeps its bytes.  `--reference_region`
+images are then picture-sized and cropped to the window; the attribution maps stay on the window.
 
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
@@ -68,6 +74,10 @@ def parse(argv=None):
                    "--reference_path: white where that exemplar applies")
     p.add_argument("--save_reference_maps", action="store_true", help="(not in the reference) write one grayscale attribution map per "
                    "--reference_path into <outdir>/reference_maps/: where the picture attended to that exemplar")
+    p.add_argument("--paste_back", action="store_true", help="(not in the reference) --image_path / --mask_path of any size: inpaint a "
+                   "window around the hole at --H x --W and write the whole picture, the result blended in, to <outdir>/pasted/")
+    p.add_argument("--context", type=float, default=0.5, help="with --paste_back: the window holds the hole's box plus this fraction of its size on each side")
+    p.add_argument("--feather", type=int, default=8, help="with --paste_back: the blend mask falls off over 2 x this many picture pixels around the hole")
     p.add_argument("--random_weights", action="store_true", help="name-seeded random weights instead of --ckpt")
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
@@ -82,6 +92,8 @@ def parse(argv=None):
             p.error(f"--reference_weight: {len(w)} weights for {len(refs)} --reference_path images")
         if any(not (x >= 0.0) or x == float("inf") for x in w) or not sum(w) > 0.0:
             p.error("--reference_weight: weights must be finite and >= 0 with a positive sum")
+    if not (opt.context >= 0.0) or opt.context == float("inf") or opt.feather < 0 or opt.feather > 2047:
+        p.error("--context must be finite and >= 0, --feather an integer in 0 .. 2047")
     if opt.reference_region is not None:
         refs = opt.reference_path if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
         if len(opt.reference_region) != len(refs):
@@ -89,8 +101,9 @@ def parse(argv=None):
     return opt
 
 
-def load_regions(paths, size, device):
-    """One grayscale image per exemplar -> region maps fp32 [1, K, h, w] in [0, 1] on `device`: decoded to uint8, scaled to [0, 1],
+def load_regions(paths, size, device, window=None):
+    """One grayscale image per exemplar -> region maps fp32 [1, K, h, w] in [0, 1] on `device`: decoded to uint8 (with --paste_back:
+    cropped on the host to `window` = (y0, x0, wh, ww) of the picture, which the region images then have the size of), scaled to [0, 1],
     resized on the device to the latent grid `size` (pipeline.resize_mask: antialiased bilinear, a convex combination, so the values
     stay in [0, 1] up to the rounding of the fp32 filter sums; no threshold).  The clamp takes that rounding away: a sum of -1e-8
     where the image is black would otherwise be refused as a negative region."""
@@ -99,7 +112,11 @@ def load_regions(paths, size, device):
     from pbe_amd import pipeline
     maps = []
     for path in paths:
-        u8 = torch.from_numpy(np.array(Image.open(path).convert("L"), dtype=np.uint8)).to(device)
+        img = Image.open(path).convert("L")
+        if window is not None:
+            y0, x0, wh, ww = window
+            img = img.crop((x0, y0, x0 + ww, y0 + wh))
+        u8 = torch.from_numpy(np.array(img, dtype=np.uint8)).to(device)
         maps.append(pipeline.resize_mask(u8.float()[None, None] / 255.0, size))
     return torch.cat(maps, 1).clamp_(0.0, 1.0)
 
@@ -163,7 +180,18 @@ def main(argv=None):
 
     with torch.no_grad(), model.ema_scope():
         refs = list(opt.reference_path) if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
-        t = preprocess.load_triple_device(opt.image_path, opt.mask_path, refs[0], device)      # uint8 up, arithmetic on the GPU
+        win = None
+        if opt.paste_back:                                                             # a picture of any size: one window of it at H x W
+            from pbe_amd import window as pbe_window
+            u8 = preprocess.load_triple_u8(opt.image_path, opt.mask_path, refs[0])
+            if u8["image"].shape[:2] != u8["mask"].shape:
+                raise SystemExit(f"--paste_back: the image is {u8['image'].shape[:2]}, the mask {u8['mask'].shape}")
+            picture, picture_mask = torch.from_numpy(u8["image"]).to(device), torch.from_numpy(u8["mask"]).to(device)
+            win = pbe_window.plan_window(u8["mask"], (opt.H, opt.W), opt.context, opt.feather)
+            t = pipeline.window_inputs([picture], [picture_mask], [win], (opt.H, opt.W))
+            t["ref"] = ops.u8_to_planes(torch.from_numpy(u8["ref"]).to(device)[None], preprocess.CLIP_MEAN, preprocess.CLIP_STD)
+        else:
+            t = preprocess.load_triple_device(opt.image_path, opt.mask_path, refs[0], device)  # uint8 up, arithmetic on the GPU
         filename = os.path.basename(opt.image_path)
         test_model_kwargs = {"inpaint_mask": t["mask"], "inpaint_image": t["inpaint"]}
         ref = t["ref"]
@@ -183,7 +211,7 @@ def main(argv=None):
         test_model_kwargs["inpaint_mask"] = pipeline.resize_mask(test_model_kwargs["inpaint_mask"], z_inpaint.shape[-2:])
         cr, extra = None, {}
         if opt.reference_region is not None:                                           # one map per exemplar token, the same for every sample
-            cr = load_regions(opt.reference_region, z_inpaint.shape[-2:], device).expand(c.shape[0], -1, -1, -1).contiguous()
+            cr = load_regions(opt.reference_region, z_inpaint.shape[-2:], device, win).expand(c.shape[0], -1, -1, -1).contiguous()
             extra["conditioning_regions"] = cr
         cm = None
         if opt.save_reference_maps:
@@ -197,6 +225,13 @@ def main(argv=None):
         if not opt.skip_save:
             for i in range(xd.shape[0]):
                 paths = preprocess.save_outputs_device(opt.outdir, filename[:-4], opt.seed, t, xd[i], opt.H, opt.W)
+        if win is not None:                                                            # (an explicit request: written with --skip_save too)
+            from PIL import Image
+            os.makedirs(os.path.join(opt.outdir, "pasted"), exist_ok=True)
+            alpha = ops.feather_alpha(picture_mask, win, opt.feather)
+            for i in range(xd.shape[0]):
+                pasted = ops.paste_window(xd[i].contiguous(), alpha, picture.clone(), win)
+                Image.fromarray(pasted.cpu().numpy()).save(os.path.join(opt.outdir, "pasted", f"{filename[:-4]}_{opt.seed}.png"))
         ref_maps = None
         if cm is not None:                                                             # (an explicit request: written with --skip_save too)
             ref_maps = cm.result(z_inpaint.shape[-2:])
@@ -208,6 +243,7 @@ def main(argv=None):
                      post_eps=post_eps.numpy(), c=c.float().cpu().numpy(), z_inpaint=z_inpaint.float().cpu().numpy(),
                      mask64=test_model_kwargs["inpaint_mask"].float().cpu().numpy(), latent=samples.float().cpu().numpy(), image=x.numpy(),
                      reference_weight=(cw if cw is not None else torch.ones(c.shape[:2])).double().numpy(),
+                     **({} if win is None else {"window": np.array(win, dtype=np.int64)}),
                      **({} if cr is None else {"reference_region": cr.double().cpu().numpy()}),
                      **({} if ref_maps is None else {"ref_maps": ref_maps.float().cpu().numpy()}))
     print(f"Your samples are ready and waiting for you here: \n{opt.outdir} \n \nEnjoy.")
