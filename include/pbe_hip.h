@@ -62,6 +62,10 @@ size_t pbe_sizeof_attn_desc(void);
 size_t pbe_sizeof_attn_mx8_desc(void);
 size_t pbe_sizeof_mx8_out_desc(void);
 size_t pbe_sizeof_ctx_attn_desc(void);
+/* The implicit-GEMM kernels' parameter block (internal to the library; for layout tests): its size, and the size of its HEAD - the leading
+ * bytes that hold everything a workgroup reads before its first fetch; epilogue, statistics and diagnostic fields lie behind it. */
+size_t pbe_sizeof_igemm_params(void);
+size_t pbe_sizeof_igemm_head(void);
 
 /* ---------------------------------------------------------------------------------------------
  * pbe_gemm_f16 — C[m,n] = act(alpha * sum_k A[m,k] * W[n,k] + bias + rowvec[m / group_rows, n]) + R[m,n]
@@ -175,6 +179,13 @@ typedef struct pbe_conv3x3_desc {
 } pbe_conv3x3_desc;
 int pbe_conv3x3_f16(const pbe_conv3x3_desc* d, pbe_stream_t stream);
 int pbe_conv3x3_plan(const pbe_conv3x3_desc* d, int32_t* out6, size_t* workspace_needed); /* as pbe_gemm_plan */
+/* Host only, nothing is launched: the launch-invariant values the planned tile's kernel receives for its prologue (tile order, split-K
+ * slice, halo geometry and the reciprocals it divides with).  out32 = {tile, split-K, BM, BN, mode (1 gather, 2 halo-resident), m_fast,
+ * tdiv, mg_tdiv, split_per, sv_ns, sv_gdiv, mg_sv_gdiv, hw, mg_hw, mg_wo, per_blk, mg_per_blk, mg_kb, th, hw2, hps, nsub, halo rows, tiles
+ * per image, mg_tpi, mh_hps, mh_hw2, log2 W, log2 pixels per (sub-)image, halo image rows of the tile,
+ * offset of the parameter block's first tail field (= head size), offset of its last tail field}; mg_x = floor(2^32 / x) and
+ * mh_x = ceil(2^20 / x) as 32-bit patterns (pbe_amd/csrc/igemm_kernel.h: udiv_mg, udiv_h). */
+int pbe_conv3x3_prologue(const pbe_conv3x3_desc* d, int32_t* out32);
 
 /* im2col for the three small-Cin convs (9->320 U-Net in, 3->128 VAE in, 4->512 VAE decoder in):
  * X fp16 NHWC [B,H,W,Cp] -> out fp16 [B*Ho*Wo, 9*Cp]. */

@@ -188,6 +188,28 @@ extern "C" int pbe_conv3x3_plan(const pbe_conv3x3_desc* d, int32_t* out6, size_t
     return PBE_OK;
 }
 
+extern "C" size_t pbe_sizeof_igemm_params(void) { return sizeof(IGemmP); }
+extern "C" size_t pbe_sizeof_igemm_head(void) { return kIGemmHeadBytes; }
+
+extern "C" int pbe_conv3x3_prologue(const pbe_conv3x3_desc* d, int32_t* out32) {
+    PBE_REQUIRE(out32, "pbe_conv3x3_prologue: null output");
+    IGemmP p;
+    const int rc = fill_conv(d, p, "pbe_conv3x3_prologue");
+    if (rc != PBE_OK) return rc;
+    const int batch = p.phase ? 4 : 1;
+    const Plan pl = plan_igemm(p, batch, d->workspace ? d->workspace_bytes : 0, d->tile_cfg, 1);
+    const TileCfg& t = kTiles[pl.cfg];
+    const int mode = (t.forms & F_HALO) ? 2 : 1;
+    p.splits = pl.splits;
+    igemm_prologue(p, batch, t.bm, t.bn, mode);
+    const int32_t v[32] = {pl.cfg, pl.splits, t.bm, t.bn, mode, p.m_fast, p.tdiv, (int32_t)p.mg_tdiv, p.split_per, p.sv_ns, p.sv_gdiv, (int32_t)p.mg_sv_gdiv,
+                           p.hw, (int32_t)p.mg_hw, (int32_t)p.mg_wo, p.per_blk, (int32_t)p.mg_per_blk, (int32_t)p.mg_kb, p.th, p.h_hw2, p.h_hps, p.h_nsub,
+                           p.h_rows, p.h_tpi, (int32_t)p.mg_h_tpi, (int32_t)p.mh_hps, (int32_t)p.mh_hw2, p.h_lgw, p.h_lgimg, t.hpa,
+                           (int32_t)offsetof(IGemmP, C), (int32_t)offsetof(IGemmP, sv_ok)};
+    memcpy(out32, v, sizeof(v));
+    return PBE_OK;
+}
+
 // ---- MX-fp8 output (pbe_gemm_mx8out_f16): the GEMM's output columns leave as pbe_attention_mx8 operands ----
 static int fill_mx8(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, IGemmP& p, const char* who) {
     PBE_REQUIRE(d && mx, "%s: null descriptor", who);

@@ -46,7 +46,8 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wm = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int mb = blockIdx.x % tiles_m, rn = blockIdx.x / tiles_m;
+    // (launch-invariant divisors, reciprocals from the host - launch_regs: tdiv = tiles_m, per_blk = run)
+    const int rn = (int)udiv_mg(blockIdx.x, (unsigned)tiles_m, p.mg_tdiv), mb = (int)blockIdx.x - rn * tiles_m;
     const int m0 = mb * ABM, nt0 = rn * run;
     const int Q = run * AKT;
     h16* stg = reinterpret_cast<h16*>(smem + RS * SLOT + wm * STGW);
@@ -64,7 +65,7 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
 #ifdef PBE_ASTAT_NOROT
     const int rot = 0;
 #else
-    const int rot = (mb + (mb >> 3)) % run;
+    const int rsum = mb + (mb >> 3), rot = rsum - (int)udiv_mg((unsigned)rsum, (unsigned)run, p.mg_per_blk) * run;
 #endif
     const h16* w_src[PW];
 #pragma unroll
@@ -300,6 +301,8 @@ static void launch_regs(IGemmP p, hipStream_t s) {
     const int tiles_m = p.M / ABM, tiles_n = p.N / BN;
     int run = tiles_n;                                     // the longest run of column tiles that still gives every CU its two workgroups
     while (run > 1 && ((long)tiles_m * (tiles_n / run) < 512 || tiles_n % run)) --run;
+    p.tdiv = tiles_m; p.mg_tdiv = mg_of((unsigned)tiles_m);                   // the kernel's prologue divides by multiplying (igemm_kernel.h, udiv_mg)
+    p.per_blk = run; p.mg_per_blk = mg_of((unsigned)run);
     static std::atomic<uint64_t> attr_done{0};
     pbe_raise_dynamic_lds(attr_done, reinterpret_cast<const void*>(&astat_regs_kernel<TN, FORM>), lds);
     pbe_prof_begin(PBE_K_GEMM, s);

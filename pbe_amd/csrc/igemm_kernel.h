@@ -30,27 +30,49 @@
 //   * what bounds the big conv tiles on real data is the power limit: cycles removed from the schedule come back
 //     as a lower clock.
 #pragma once
+#include <cstddef>
 #include <type_traits>
 #include <utility>
 #include "common.h"
 #include "../../include/pbe_hip.h"
 
 struct IGemmP {
-    const h16* A; const h16* A2; const h16* W; h16* C;
-    const float* bias; const h16* rowvec; const h16* resid;
+    // ---- HEAD: everything a workgroup reads between kernel entry and its first LDS-DMA, contiguous so the scalar loads of the prologue
+    //      come from the first cache lines of the kernarg segment (offsets pinned by the static_asserts below).  A REORDER ONLY: the
+    //      compiler still fetches the head as the code reaches it, and a mode skips the fields of the others
+    //      (hw / mg_hw .. mg_kb: MODE 1; h_*: MODE 2).  astat_regs_kernel reads mg_tdiv (divisor tiles_m) and mg_per_blk (its run) ----
+    const h16* A; const h16* A2; const h16* W;
+    long lda, lda2, ldw;
+    long sA, sW;
     int M, N, K, K1;
-    long lda, lda2, ldw, ldc, ldr;
-    int ldv, group_rows;
-    long sA, sW, sC, sR;
-    float alpha; int act; int bias_row; int vec;
+    int splits;
+    int m_fast;     // an XCD's run of tiles walks m fastest (one weight panel, many activation rows) instead of n fastest (launch_cfg)
+    // launch-invariant prologue values (igemm_prologue, host): the kernel holds no run-time division before its first fetch.
+    // mg_* = floor(2^32 / divisor) for udiv_mg (exact for every 32-bit numerator), mh_* = ceil(2^20 / divisor) for the halo rows' udiv_h
+    int tdiv; unsigned mg_tdiv;                          // tile id -> (tm_i, tn_i): divisor tiles_m (m fastest) or tiles_n
+    int split_per;                                       // split-K: k-tiles (MODE 0 / 1) or channel blocks (MODE 2) per slice
+    int sv_ns;                                           // samples per tile of the staged epilogue vectors
+    int sv_gdiv; unsigned mg_sv_gdiv;                    // row tiles per sample (group_rows / BM, >= 1): first sample of a tile = tm_i / sv_gdiv
     // conv gather
     int H, Wd, C1, C2, Ho, Wo, cstride, pad, ups, cb;   // cb = channel block of the K order (multiple of 64)
     int phase;                                           // MODE 1: nearest-2x upsample + 3x3 conv as FOUR 2x2 convs on the source grid (see the tap table); blockIdx.y = output phase
     int th;                                              // MODE 2: image rows per tile (tile = th full rows, or whole images)
+    int hw; unsigned mg_hw, mg_wo;                       // MODE 1 tap table: output pixels per sample, m -> (b, oy, ox)
+    int per_blk; unsigned mg_per_blk, mg_kb;             // MODE 1 split-K resume: k-tiles per channel block (taps x cb / 64), per tap
+    // MODE 2 halo geometry: row stride W + 1, halo rows per (sub-)image, whole images per tile, valid halo rows, row tiles per image,
+    // log2 of the image width and of the pixels per (sub-)image (both powers of two: halo_rows)
+    int h_hw2, h_hps, h_nsub, h_rows, h_tpi; unsigned mg_h_tpi, mh_hps, mh_hw2; int h_lgw, h_lgimg;
+    // ---- TAIL: epilogue, statistics and diagnostic fields ----
+    h16* C;
+    const float* bias; const h16* rowvec; const h16* resid;
+    long ldc, ldr;
+    int ldv, group_rows;
+    long sC, sR;
+    float alpha; int act; int bias_row; int vec;
     // fp8 (OCP e4m3) operands: rows are bytes (the loader sees them as K/2 halfs); C = acc * sa[m] * sw[n] (* alpha) + ...
     const float* sa; const float* sw; long ssa, ssw;
     // split-K: gridDim.z slices of the k-tile range, fp32 partial slabs [splits][M][N]
-    int splits; float* ws;
+    float* ws;
     // extended epilogue of the dense tiles (EX instantiations, the transformer block's GEMM chain; ldm/modules/attention.py:198-252):
     int alpha_cols;                  // > 0: alpha multiplies columns n < alpha_cols only (q of a fused q | k | v launch, pre-scaled for the attention kernel)
     const float* ln_stat;            // LayerNorm folded into THIS GEMM: A holds the raw rows x, W = W * gamma, bias = W beta (+ bias), and
@@ -71,11 +93,17 @@ struct IGemmP {
     int mx_c0[3], mx_layout[3]; float mx_alpha[3]; int mx_nr, mx_crow;
     int mx_H, mx_N, mx_D, mx_DP, mx_DV;
     int sv_ok;      // bias + row vector of a tile come from LDS (set per tile shape in launch_cfg)
-    int m_fast;     // an XCD's run of tiles walks m fastest (one weight panel, many activation rows) instead of n fastest (launch_cfg)
 #ifdef PBE_STAMPS
     unsigned long long* stamps;     // diagnostic build only (tools/phase_stamps.py): 16 words per workgroup
 #endif
 };
+// the head is what the host fills for the prologue and what a workgroup fetches first: four 64-byte lines of the kernarg segment
+constexpr size_t kIGemmHeadBytes = offsetof(IGemmP, C);
+static_assert(offsetof(IGemmP, A) == 0 && offsetof(IGemmP, lda) == 24 && offsetof(IGemmP, M) == 64 && offsetof(IGemmP, tdiv) == 88 &&
+              offsetof(IGemmP, H) == 112 && offsetof(IGemmP, hw) == 160 && offsetof(IGemmP, h_hw2) == 184 && kIGemmHeadBytes == 224,
+              "IGemmP: the prologue head moved");
+static_assert(offsetof(IGemmP, bias) == 232 && offsetof(IGemmP, ldc) == 256 && offsetof(IGemmP, alpha) == 296 && offsetof(IGemmP, ws) == 344 &&
+              offsetof(IGemmP, ln_stat) == 360, "IGemmP: the epilogue tail moved");
 
 // Diagnostic build (-DPBE_STAMPS, never the shipped library): wave 0 of every workgroup records s_memtime at its phase
 // boundaries into a buffer of its own; no output value depends on a stamp (cdna_hip_programming.md section 7, in-kernel stamps).
@@ -84,7 +112,7 @@ struct IGemmP {
     do {                                                                                                               \
         if (p.stamps && threadIdx.x == 0) {                                                                            \
             const long wg_ = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;                     \
-            p.stamps[wg_ * 16 + (i)] = (i) >= 7 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();    \
+            p.stamps[wg_ * 16 + (i)] = ((i) == 7 || (i) == 8) ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();    \
         }                                                                                                              \
     } while (0)
 // main-loop accounting of wave 0: cycles inside the counted vmcnt waits (words 9), the barrier after the fragment reads (10) and
@@ -130,15 +158,27 @@ static __device__ __attribute__((aligned(16))) unsigned int g_pbe_zero16[4] = {0
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc),         \
                                      (__attribute__((address_space(3))) void*)(ldst), 16, 0, 0)
 
-// a / b for 0 <= a < 2^20, 1 <= b < 2^20, rb = 1.0f / b: the float quotient is off by at most one, two fix-ups make it exact
-// (9 instructions against ~40 of the generic 32-bit division: the halo tile's setup does ~50 of them per thread)
-__device__ __forceinline__ int small_div(int a, int b, float rb) {
-    int q = (int)((float)a * rb);
-    const int r = a - q * b;
-    q += (r >= b) ? 1 : 0;
-    q -= (r < 0) ? 1 : 0;
+// Divisions of the prologue by launch-invariant divisors: the host passes a reciprocal (igemm_prologue), the kernel multiplies.
+// n / d for ANY 32-bit n and 1 <= d < 2^31, mg = floor(2^32 / d) (2^32 - 1 for d = 1): n mg / 2^32 lies in (n / d - 1, n / d], so the
+// estimate is the quotient or one less and one fix-up makes it exact (5 scalar instructions against ~40 of the generic division)
+__host__ __device__ __forceinline__ unsigned udiv_mg(unsigned n, unsigned d, unsigned mg) {
+    unsigned q = (unsigned)(((unsigned long long)n * mg) >> 32);
+    q += (n - q * d >= d) ? 1u : 0u;
     return q;
 }
+static inline unsigned mg_of(unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)((1ull << 32) / d); }
+// a / d for 0 <= a < 1024 and 1 <= d <= 512 (halo rows and their divisors: HPA <= 512), mh = ceil(2^20 / d).  With e = mh d - 2^20, 0 <= e < d:
+// a mh / 2^20 = a / d + a e / (d 2^20), and the excess a e / (d 2^20) < a / 2^20 < 2^-10 < 1 / d.  a / d lies at least 1 / d below the next
+// integer, so the floor is the quotient - exact without a fix-up, one 24-bit multiply and a shift
+// (the float-reciprocal form this replaces took 9 instructions, ~50 times per lane of a halo tile)
+__host__ __device__ __forceinline__ int udiv_h(int a, unsigned mh) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return (int)(__umul24((unsigned)a, mh) >> 20);
+#else
+    return (int)(((unsigned)a * mh) >> 20);
+#endif
+}
+static inline unsigned mh_of(unsigned d) { return (unsigned)(((1u << 20) + d - 1) / d); }
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -286,7 +326,7 @@ template <int BM, int BN, int NWM, int NWN, int MODE, int S, int HPA = 0, bool P
 #ifndef PBE_EX_MINWAVES
 #define PBE_EX_MINWAVES 2
 #endif
-__global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 4 && S == 2) ? PBE_EX_MINWAVES : 1) igemm_kernel(const IGemmP p, int tiles_n) {
+__global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 4 && S == 2) ? PBE_EX_MINWAVES : 1) igemm_kernel(const IGemmP p) {
     // EX (MODE 0, fp16 operands, one-pass epilogue tiles): the extended epilogue, a bit mask of what THIS instantiation carries -
     // EX_LN LayerNorm folded in, EX_ST row statistics out, EX_VT column-range alpha + transposed V^T tiles (see IGemmP).  Separate
     // instantiations per combination in use (GEGLU: EX_LN; proj_in / to_out: EX_ST; q|k|v^T: EX_LN | EX_VT): a kernel's registers are
@@ -339,10 +379,14 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     // Each XCD's L2 fetches what ITS tiles touch.  n fastest: an XCD's run covers few row blocks of A and every column block of
     // W - right where A is the big operand (64x64 maps).  m fastest: few column blocks of W and every row block of A - right where
     // W is (16x16 / 8x8 maps: 29 MB of weights against 5 MB of activations; n fastest made all 8 L2s fetch all 29).
-    const int tiles_m = gridDim.x / tiles_n;
-    const int tn_i = p.m_fast ? tile / tiles_m : tile % tiles_n, tm_i = p.m_fast ? tile - tn_i * tiles_m : tile / tiles_n;
+    // (tile / tiles_m | tile / tiles_n: one divisor per launch, its reciprocal from the host)
+    const int tq = (int)udiv_mg((unsigned)tile, (unsigned)p.tdiv, p.mg_tdiv), tr = tile - tq * p.tdiv;
+    const int tn_i = p.m_fast ? tq : tr, tm_i = p.m_fast ? tr : tq;
     const int m0 = tm_i * BM, n0 = tn_i * BN;
     const long bz = blockIdx.y;
+#ifdef PBE_STAMPS
+    if (m0 >= 0) PBE_STAMP(14);                      // first kernarg-dependent value (tile origin) ready
+#endif
 
     // ---- loader state: this lane's row inside an 8-row DMA piece and its source chunk ----
     // LDS rows are 128 B (64 halfs = 8 chunks of 16 B) = one whole cache line per row: a wave's DMA instruction fetches 8
@@ -377,9 +421,9 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     // Epilogue vectors of this tile, staged ONCE (their global latency hides under the first DMA tile):
     // svec[s][c] = bias[n0 + c] + rowvec[first sample of the tile + s][n0 + c], up to 4 samples per tile.
     float* svec = reinterpret_cast<float*>(smem + (RING > WM * CLD * 2 ? RING : WM * CLD * 2) + (MODE == 1 ? 9 * BM * 4 : 0));
-    const int sv_ns = (p.rowvec && p.group_rows < BM) ? BM / p.group_rows : 1;       // samples per tile (tile is sample-aligned when sv_ok)
+    const int sv_ns = p.sv_ns;                       // samples per tile (tile is sample-aligned when sv_ok)
     if (MODE == 1) {
-        const int hw = p.Ho * p.Wo, Hv = p.H << p.ups, Wv = p.Wd << p.ups;
+        const int hw = p.hw, Hv = p.H << p.ups, Wv = p.Wd << p.ups;
         // Phase form (p.phase): a 3x3 conv over a nearest-2x upsampled image reads, for the output pixel (2y + py, 2x + px), only a 2x2
         // block of SOURCE pixels - rows {y - 1 + py, y + py}, columns {x - 1 + px, x + px} - because the 9 taps fall on 4 distinct
         // sources (py = 0: taps ky = 0 | 1, 2 -> rows y - 1 | y; py = 1: ky = 0, 1 | 2 -> y | y + 1).  The host sums the weights that
@@ -389,8 +433,8 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
         for (int row = tid; row < BM; row += NT) {            // one thread per tile row: one (b, oy, ox) decode, 9 (or 4) taps
             const int m = m0 + row;
             const bool rok = m < p.M;
-            const int b = m / hw, rem = m - b * hw;
-            const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
+            const int b = (int)udiv_mg((unsigned)m, (unsigned)hw, p.mg_hw), rem = m - b * hw;
+            const int oy = (int)udiv_mg((unsigned)rem, (unsigned)p.Wo, p.mg_wo), ox = rem - oy * p.Wo;
             const int iy0 = oy * p.cstride - p.pad, ix0 = ox * p.cstride - p.pad;
             if (p.phase) {
 #pragma unroll
@@ -420,17 +464,16 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     const int nk_all = (p.K + 63) >> 6;
     int kt0 = 0, nk = nk_all;                        // this workgroup's k-tile range [kt0, nk)
     if (p.splits > 1) {
-        const int per = (nk_all + p.splits - 1) / p.splits;
-        kt0 = blockIdx.z * per;
-        nk = min(nk_all, kt0 + per);
+        kt0 = blockIdx.z * p.split_per;
+        nk = min(nk_all, kt0 + p.split_per);
     }
     // conv K order: (channel block of cb, tap, channel): state of the NEXT k-tile to issue
     const int KB = MODE == 1 ? p.cb >> 6 : 1;        // k-tiles per (block, tap) visit
     const int ntap = (MODE == 1 && p.phase) ? 4 : 9;
     int tap = 0, c0 = 0, kj = 0;
     if (MODE == 1 && kt0 > 0) {
-        const int per_blk = ntap * KB, cblk = kt0 / per_blk, r = kt0 - cblk * per_blk;
-        tap = r / KB; kj = r - tap * KB; c0 = cblk * p.cb + kj * 64;
+        const int cblk = (int)udiv_mg((unsigned)kt0, (unsigned)p.per_blk, p.mg_per_blk), r = kt0 - cblk * p.per_blk;
+        tap = (int)udiv_mg((unsigned)r, (unsigned)KB, p.mg_kb); kj = r - tap * KB; c0 = cblk * p.cb + kj * 64;
     }
     // MODE 1: per piece the running source pointer and its advance per k-tile (a padding pixel keeps reading the zero block: advance 0)
     const h16* a_src[LA];
@@ -549,7 +592,8 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
             }
         }
         if (p.sv_ok && p.splits <= 1) {                  // staged AFTER the first DMAs are in flight: both latencies overlap
-            const int s0 = p.rowvec ? m0 / p.group_rows : 0;
+            // first sample of the tile: sv_ns whole samples per tile, or sv_gdiv row tiles per sample (tile and sample are aligned: sv_ok)
+            const int s0 = !p.rowvec ? 0 : sv_ns > 1 ? tm_i * sv_ns : (int)udiv_mg((unsigned)tm_i, (unsigned)p.sv_gdiv, p.mg_sv_gdiv);
             for (int idx = tid; idx < sv_ns * BN; idx += NT) {
                 const int si = idx / BN, c = idx - si * BN, n = n0 + c;
                 float v = 0.f;
@@ -573,28 +617,28 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
         // x = -1 and x = TW are always padding: the zero row right of image row y IS the zero row left of image row y + 1
         // (row stride TW + 1 instead of TW + 2; 4 rows of 64 pixels: 391 halo rows instead of 396 - what lets a third weight slot
         // fit beside two halo images of a 256-pixel tile).
-        const int TW = p.Wd, TH = p.th, HW2 = TW + 1, HPS = (TH + 2) * HW2 + 1;
-        const int img_px = TH * TW, nsub = BM / img_px;                             // nsub > 1: the tile holds nsub whole images
-        const int tiles_per_img = p.H / TH;
-        const int b0 = nsub > 1 ? tm_i * nsub : tm_i / tiles_per_img;
-        const int y0 = nsub > 1 ? 0 : (tm_i - b0 * tiles_per_img) * TH;
-        const float r_hps = 1.0f / (float)HPS, r_hw2 = 1.0f / (float)HW2, r_img = 1.0f / (float)img_px, r_tw = 1.0f / (float)TW;
-        int hpix[LAH];                                // source pixel of this lane's row in each of its halo pieces (-1: zero)
-#pragma unroll
-        for (int i = 0; i < LAH; ++i) {
-            const int piece = min(wave + NW * i, PAH - 1), hp = piece * 8 + lrow;      // (padding pieces repeat the last real one)
+        // The geometry is the launch's (igemm_prologue): HW2 = TW + 1, HPS = (TH + 2) HW2 + 1 halo rows per (sub-)image, nsub whole images
+        // per tile (nsub > 1) or tiles_per_img row tiles per image; only the base pixel (b0, y0) and the border test belong to the workgroup.
+        static_assert(HPA <= 512, "udiv_h: halo rows below 1024, divisors up to 512");
+        const int TW = p.Wd, TH = p.th, HW2 = p.h_hw2, HPS = p.h_hps, nsub = p.h_nsub;
+        const int b0 = nsub > 1 ? tm_i * nsub : (int)udiv_mg((unsigned)tm_i, (unsigned)p.h_tpi, p.mg_h_tpi);
+        const int y0 = nsub > 1 ? 0 : (tm_i - b0 * p.h_tpi) * TH;
+        auto halo_pix = [&](int hp) {                 // source pixel of halo row hp of this tile (-1: zero row)
             int pix = -1;
-            if (hp < nsub * HPS) {
-                const int sub = small_div(hp, HPS, r_hps), r = hp - sub * HPS, hy = small_div(r, HW2, r_hw2), hx = r - hy * HW2;
+            if (hp < p.h_rows) {
+                const int sub = udiv_h(hp, p.mh_hps), r = hp - sub * HPS, hy = udiv_h(r, p.mh_hw2), hx = r - hy * HW2;
                 const int y = y0 + hy - 1, x = hx - 1;
                 if ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)TW) pix = ((b0 + sub) * p.H + y) * TW + x;
             }
-            hpix[i] = pix;
-        }
+            return pix;
+        };
+        int hpix[LAH];                                // source pixel of this lane's row in each of its halo pieces (-1: zero)
+#pragma unroll
+        for (int i = 0; i < LAH; ++i) hpix[i] = halo_pix(min(wave + NW * i, PAH - 1) * 8 + lrow);      // (padding pieces repeat the last real one)
         int hc[TM];                                   // halo row of this lane's pixel in each of its 16-pixel groups (tap (1,1))
 #pragma unroll
-        for (int j = 0; j < TM; ++j) {
-            const int ml = wm * WM + j * 16 + fr, sub = small_div(ml, img_px, r_img), rr = ml - sub * img_px, ty = small_div(rr, TW, r_tw), tx = rr - ty * TW;
+        for (int j = 0; j < TM; ++j) {                // (image width and pixels per (sub-)image are powers of two: shifts and masks)
+            const int ml = wm * WM + j * 16 + fr, sub = ml >> p.h_lgimg, rr = ml - (sub << p.h_lgimg), ty = rr >> p.h_lgw, tx = rr - (ty << p.h_lgw);
             hc[j] = sub * HPS + (ty + 1) * HW2 + tx + 1;
         }
         // running source pointer of each halo piece (channel block by channel block, +64 channels; a padding row keeps reading the
@@ -604,7 +648,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
             const int c0b = blk * 64;
             const bool first = c0b < p.C1;
             const h16* base = (first ? p.A + c0b : p.A2 + (c0b - p.C1)) + gch * 8;
-            const long cs = first ? p.C1 : p.C2;
+            const int cs = first ? p.C1 : p.C2;         // (int x int -> 64 bits: one multiply-add per piece)
 #pragma unroll
             for (int i = 0; i < LAH; ++i) {
                 hptr[i] = hpix[i] >= 0 ? base + (long)hpix[i] * cs : zsrc;
@@ -629,9 +673,8 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
         const int nblk_all = (p.C1 + p.C2) >> 6;
         int blk0 = 0, blk1 = nblk_all;                // this workgroup's channel blocks (split-K at block granularity)
         if (p.splits > 1) {
-            const int per = (nblk_all + p.splits - 1) / p.splits;
-            blk0 = blockIdx.z * per;
-            blk1 = min(nblk_all, blk0 + per);
+            blk0 = blockIdx.z * p.split_per;
+            blk1 = min(nblk_all, blk0 + p.split_per);
         }
         const int nk2 = blk1 * 9;
         PBE_STAMP(1);
@@ -704,16 +747,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
             for (int i = 0; i < PWG; ++i)
                 wp[i] = p.W + bz * p.sW + (long)min(n0 + (gw * PWG + i) * 8 + lrow, p.N - 1) * p.ldw + gch * 8 + (long)(kt_first + 2) * 64;
 #pragma unroll
-            for (int i = 0; i < LAHG; ++i) {
-                const int hp = min(gw + 4 * i, PAH - 1) * 8 + lrow;
-                int pix = -1;
-                if (hp < nsub * HPS) {
-                    const int sub = small_div(hp, HPS, r_hps), r = hp - sub * HPS, hy = small_div(r, HW2, r_hw2), hx = r - hy * HW2;
-                    const int y = y0 + hy - 1, x = hx - 1;
-                    if ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)TW) pix = ((b0 + sub) * p.H + y) * TW + x;
-                }
-                hq[i] = pix;
-            }
+            for (int i = 0; i < LAHG; ++i) hq[i] = halo_pix(min(gw + 4 * i, PAH - 1) * 8 + lrow);
             // One MFMA block = the wave's 2 TM TN MFMAs + (a few VALU instructions after every other one) the LDS byte addresses of
             // the fragments of the tile this wave reads NEXT and the bumped weight pointers.
             auto mfmas = [&](int shift_n, int abase_n, int wb_n) {
@@ -1597,6 +1631,41 @@ static Plan plan_igemm(const IGemmP& p, int batch, size_t ws_bytes, int want_cfg
 extern int g_pbe_pingpong;      // pbe_tune(4, 0/1): ping-pong main loop of the halo-resident conv tiles
 extern int g_pbe_mfast;         // pbe_tune(5, 0/1): let a launch walk its tiles m fastest per XCD when that fetches fewer bytes
 
+// What a launch of tile bm x bn knows before any workgroup starts (p.splits set by the dispatch): the tile order, the halo tile's rows and
+// every launch-invariant value of the kernel's prologue (IGemmP head), so that no workgroup divides before its first fetch.
+// mode: 0 dense, 1 conv gather, 2 halo-resident conv.
+static void igemm_prologue(IGemmP& p, int batch, int bm, int bn, int mode) {
+    const int tiles_m = cdiv(p.M, bm), tiles_n = cdiv(p.N, bn);
+    {   // bytes the 8 L2s fetch under either tile order (an XCD owns a contiguous run of tiles_m * tiles_n / 8 tiles)
+        const double a_bytes = mode != 0 ? 2.0 * (double)(p.M / (p.Ho * p.Wo)) * p.H * p.Wd * (p.C1 + p.C2) : 2.0 * p.M * (double)p.K;
+        const double w_bytes = 2.0 * p.N * (double)p.K;
+        const double run = tiles_m * (double)tiles_n / 8.0;
+        auto frac = [](double blocks_touched, int blocks) { const double f = blocks_touched / blocks; return f < 1.0 ? f : 1.0; };
+        const double n_fast = a_bytes * frac(run / tiles_n + 1.0, tiles_m) + w_bytes * frac(run, tiles_n);
+        const double m_fast = w_bytes * frac(run / tiles_m + 1.0, tiles_n) + a_bytes * frac(run, tiles_m);
+        p.m_fast = (g_pbe_mfast && batch == 1 && m_fast < 0.9 * n_fast) ? 1 : 0;
+    }
+    p.tdiv = p.m_fast ? tiles_m : tiles_n; p.mg_tdiv = mg_of((unsigned)p.tdiv);
+    const int units = mode == 2 ? (p.C1 + p.C2) >> 6 : (p.K + 63) >> 6;            // what split-K slices: channel blocks of a halo tile, else k-tiles
+    p.split_per = p.splits > 1 ? (units + p.splits - 1) / p.splits : units;
+    p.sv_ns = (p.rowvec && p.group_rows < bm) ? bm / p.group_rows : 1;
+    p.sv_gdiv = p.group_rows > bm ? p.group_rows / bm : 1; p.mg_sv_gdiv = mg_of((unsigned)p.sv_gdiv);
+    if (mode != 0) {
+        const int kb = p.cb >> 6;
+        p.hw = p.Ho * p.Wo; p.mg_hw = mg_of((unsigned)p.hw); p.mg_wo = mg_of((unsigned)p.Wo);
+        p.per_blk = (p.phase ? 4 : 9) * kb; p.mg_per_blk = mg_of((unsigned)p.per_blk); p.mg_kb = mg_of((unsigned)kb);
+    }
+    if (mode == 2) {                                                             // halo geometry (igemm_kernel MODE 2; halo_rows admitted the map)
+        const int W = p.Wd, th = bm / W < p.H ? bm / W : p.H, img_px = th * W;
+        p.th = th;
+        p.h_hw2 = W + 1; p.h_hps = (th + 2) * (W + 1) + 1;
+        p.h_nsub = bm / img_px; p.h_rows = p.h_nsub * p.h_hps;
+        p.h_tpi = p.H / th; p.mg_h_tpi = mg_of((unsigned)p.h_tpi);
+        p.mh_hps = mh_of((unsigned)p.h_hps); p.mh_hw2 = mh_of((unsigned)p.h_hw2);
+        p.h_lgw = __builtin_ctz((unsigned)W); p.h_lgimg = __builtin_ctz((unsigned)img_px);
+    }
+}
+
 template <int BM, int BN, int NWM, int NWN, int S, int MODE, int HPA = 0, bool PP = false, bool F8 = false, int EX = 0>
 static void launch_cfg(IGemmP p, int batch, hipStream_t s) {
     // (ping-pong only where a wave's MFMA phase - (BM/NWM/16) x (BN/NWN/16) x 2 MFMAs - is as long as its read phase: measured
@@ -1615,15 +1684,7 @@ static void launch_cfg(IGemmP p, int batch, hipStream_t s) {
     pbe_raise_dynamic_lds(attr_done, reinterpret_cast<const void*>(&igemm_kernel<BM, BN, NWM, NWN, MODE, S, HPA, PP, F8, EX>), (int)lds);
     const int tiles_m = cdiv(p.M, BM), tiles_n = cdiv(p.N, BN);
     dim3 grid((unsigned)(tiles_m * tiles_n), batch, p.splits > 1 ? p.splits : 1);
-    {   // bytes the 8 L2s fetch under either tile order (an XCD owns a contiguous run of tiles_m * tiles_n / 8 tiles)
-        const double a_bytes = MODE != 0 ? 2.0 * (double)(p.M / (p.Ho * p.Wo)) * p.H * p.Wd * (p.C1 + p.C2) : 2.0 * p.M * (double)p.K;
-        const double w_bytes = 2.0 * p.N * (double)p.K;
-        const double run = tiles_m * (double)tiles_n / 8.0;
-        auto frac = [](double blocks_touched, int blocks) { const double f = blocks_touched / blocks; return f < 1.0 ? f : 1.0; };
-        const double n_fast = a_bytes * frac(run / tiles_n + 1.0, tiles_m) + w_bytes * frac(run, tiles_n);
-        const double m_fast = w_bytes * frac(run / tiles_m + 1.0, tiles_n) + a_bytes * frac(run, tiles_m);
-        p.m_fast = (g_pbe_mfast && batch == 1 && m_fast < 0.9 * n_fast) ? 1 : 0;
-    }
+    igemm_prologue(p, batch, BM, BN, MODE);
     {   // GroupNorm statistics from the copy-out: only where the kernel's GS_OK holds and a tile is a whole number of groups inside one sample
         constexpr int NTH = NWM * NWN * 64;
         constexpr bool one_pass = (size_t)BM * (BN + 8) * 2 <= (size_t)S * (BM + BN) * 128;
@@ -1634,9 +1695,8 @@ static void launch_cfg(IGemmP p, int batch, hipStream_t s) {
         if (p.gs_report) *p.gs_report = p.gstat ? p.gs_hw / BM : 0;
     }
     // profiling brackets exactly ONE kernel each, so the event averages agree with rocprofv3's per-kernel averages
-    if (MODE == 2) p.th = BM / p.Wd < p.H ? BM / p.Wd : p.H;
     pbe_prof_begin(MODE != 0 ? PBE_K_CONV3 : PBE_K_GEMM, s);
-    hipLaunchKernelGGL((igemm_kernel<BM, BN, NWM, NWN, MODE, S, HPA, PP, F8, EX>), grid, dim3(NWM * NWN * 64), lds, s, p, tiles_n);
+    hipLaunchKernelGGL((igemm_kernel<BM, BN, NWM, NWN, MODE, S, HPA, PP, F8, EX>), grid, dim3(NWM * NWN * 64), lds, s, p);
     {   // algorithmic bytes: every operand once (fp16): activations, weights, output, fused residual
         const double nout = p.act == PBE_ACT_GEGLU ? p.N * 0.5 : (double)p.N;
         const double a_el = MODE != 0 ? (double)(p.M / (p.Ho * p.Wo)) * p.H * p.Wd * (p.C1 + p.C2) : (double)p.M * p.K * batch;

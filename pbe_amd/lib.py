@@ -72,6 +72,8 @@ SYMBOLS = {
     "pbe_sizeof_attn_mx8_desc": (c_sz, []),
     "pbe_sizeof_mx8_out_desc": (c_sz, []),
     "pbe_sizeof_ctx_attn_desc": (c_sz, []),
+    "pbe_sizeof_igemm_params": (c_sz, []),
+    "pbe_sizeof_igemm_head": (c_sz, []),
     "pbe_ctx_attention_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp]),
     "pbe_ctx_attention_w_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp, c_i64, c_vp]),
     "pbe_ctx_attention_rw_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp, c_i64, c_i64, c_vp]),
@@ -81,6 +83,7 @@ SYMBOLS = {
     "pbe_conv3x3_f16": (c_i32, [C.POINTER(Conv3x3Desc), c_vp]),
     "pbe_gemm_plan": (c_i32, [C.POINTER(GemmDesc), C.POINTER(c_i32), C.POINTER(c_sz)]),
     "pbe_conv3x3_plan": (c_i32, [C.POINTER(Conv3x3Desc), C.POINTER(c_i32), C.POINTER(c_sz)]),
+    "pbe_conv3x3_prologue": (c_i32, [C.POINTER(Conv3x3Desc), C.POINTER(c_i32)]),
     "pbe_im2col3x3_f16": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "pbe_groupnorm_workspace_bytes": (c_sz, [c_i32, c_i32]),
     "pbe_groupnorm_f16": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_sz, c_vp]),

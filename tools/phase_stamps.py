@@ -4,7 +4,8 @@
 Builds / loads tools/_dbg/libpbe_hip_stamps.so (python -m pbe_amd.build --stamps: the shipped sources with -DPBE_STAMPS), runs one
 GEMM / conv shape of the path and prints, over all workgroups, the median / p10 / p90 cycles of each phase:
 
-    setup      kernel entry -> loader state, tap table (conv), epilogue vectors staged
+    setup      kernel entry -> loader state, tap table (conv), epilogue vectors staged; also split at the tile origin, the first value
+               that needs a kernel argument (the entry stamp itself waits for one scalar load: the stamp buffer's address)
     prime      issue of the first D k-tiles' LDS-DMAs
     first      until the first k-tile has been consumed (prologue latency: first DMA landing)
     mainloop   remaining k-tiles
@@ -68,6 +69,10 @@ def report(spec, s, plan, us, fl, out=sys.stdout):
     for i, n in enumerate(NAMES):
         print(f"   {n:9s} median {np.median(d[:, i]):9.0f}  p10 {np.percentile(d[:, i], 10):9.0f}  p90 {np.percentile(d[:, i], 90):9.0f}  "
               f"({100 * np.median(d[:, i]) / np.median(tot):5.1f} % of a workgroup)", file=out)
+    if (s[:, 14] != 0).all():                          # setup, split at the first value that needs a kernarg (the tile origin)
+        ka, ar = (s[:, 14] - s[:, 0]).astype(np.float64), (s[:, 1] - s[:, 14]).astype(np.float64)
+        print(f"   setup = entry -> tile origin known: median {np.median(ka):7.0f} (p10 {np.percentile(ka, 10):.0f}, p90 {np.percentile(ka, 90):.0f})"
+              f"  +  loader state: median {np.median(ar):7.0f} (p10 {np.percentile(ar, 10):.0f}, p90 {np.percentile(ar, 90):.0f})", file=out)
     loop = np.maximum(s[:, 4] - s[:, 2], 1).astype(np.float64)        # prime end -> main loop issued
     for j, n in ((9, "counted vmcnt waits"), (10, "barrier after the fragment reads (ping-pong)"), (11, "barrier closing a k-tile"),
                  (12, "DMA issue + fragment reads (to lgkmcnt 0 in the ping-pong loop, to issue in the plain loop)"), (13, "MFMA block")):
@@ -106,9 +111,10 @@ def pipeline(keys):
                 h.pbe_debug_set_stamps(None)
                 plan = ops._PLANS[n0]
                 key = plan[0] + ("|r" if k.get("resid") is not None else "") + ("|geglu" if k.get("act") == ops.ACT_GEGLU else "")
-                if key in keys and key not in got:
+                want = next((q for q in keys if q not in got and (key == q or key.startswith(q + ":") or key.startswith(q + "|"))), None)
+                if want is not None:                   # (a key may be given without its trailing fields: the first launch it prefixes)
                     torch.cuda.synchronize()
-                    got[key] = (buf.cpu().numpy().reshape(-1, 16).copy(), plan)
+                    got[want] = (buf.cpu().numpy().reshape(-1, 16).copy(), plan, key)
                 return out
             return w
         ops._PLANS = []
@@ -122,9 +128,9 @@ def pipeline(keys):
         if key not in got:
             print(f"== {key}: not launched by the U-Net forward")
             continue
-        s, plan = got[key]
+        s, plan, key = got[key]
         f = key.split("|")[0].split(":")
-        if f[0] == "g":
+        if f[0] in ("g", "gx", "g8"):
             fl = 2.0 * int(f[1]) * int(f[2]) * int(f[3])
         else:
             B, H, W, C1, C2, Co, st, pad, ups = (int(v) for v in f[1:10])
