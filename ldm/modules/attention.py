@@ -6,21 +6,24 @@ ldm/modules/attention.py in zhanwenchen/pbe (GEGLU :38-45, FeedForward :48-65, C
     rearranges per block are free),
   * to_q | to_k run as ONE GEMM, to_v as a second GEMM with swapped operands that emits V^T
     (what the fused attention kernel consumes), softmax(QK^T)V never touches HBM,
-  * the Paint-by-Example context is ONE token per sample, so attn2's softmax over a single key
-    is exactly 1 and ``attn2(x, ctx) = to_out(to_v(ctx))`` for every query (attention.py:207-230;
-    SURVEY.md K6): it is computed once per context as a [B, C] vector and added inside the
-    epilogue of attn1's output projection.  norm2 / attn2.to_q / attn2.to_k keep their
-    parameters (checkpoint compatibility) but are dead arithmetic on this path,
-  * a context of SEVERAL tokens (several exemplars) keeps that structure: everything that depends
-    on the context alone is folded once per context into two skinny operands, and
-    ``x + attn2(norm2(x), ctx)`` is ONE launch over the residual stream (pbe_ctx_attention_f16,
-    DESIGN.md section 4.11); contexts longer than that kernel takes run q / attention / to_out,
-  * exemplar tokens may carry a weight per sample (``context_weights``) and a map of where each applies (``context_regions``:
-    regional exemplars, a weight per query row - pbe_ctx_attention_rw_f16 on the same folded operands),
+  * a BasicTransformerBlock is ONE chain of three stages, whatever the context and the precision (BasicTransformerBlock._block):
+    attn1 ``x1 = x + to_out(attn1(norm1 x))``, attn2 ``x2 = x1 + attn2(norm2 x1, ctx)``, ff ``x2 + ff(norm3 x2)``.  Each stage is
+    written once and evaluates its LayerNorm in one of three modes (_mode): folded into the GEMM that reads it, a separate launch, or
+    emitted as fp8.  A guidance pair shares everything upstream of the first launch that depends on the context and parts there,
+  * the Paint-by-Example context is ONE token per sample, so attn2's softmax over a single key is exactly 1 and
+    ``attn2(x, ctx) = to_out(to_v(ctx))`` for every query (attention.py:207-230): it is computed once per context as a
+    [B, C] vector and rides in the epilogue of attn1's output projection - the attn2 stage launches nothing.  norm2 / attn2.to_q /
+    attn2.to_k keep their parameters (checkpoint compatibility) but are dead arithmetic with such a context,
+  * a context of SEVERAL tokens (several exemplars) keeps that structure: everything that depends on the context alone is folded once
+    per context into two skinny operands, and the attn2 stage is ONE launch over the residual stream (pbe_ctx_attention_f16, DESIGN.md
+    section 4.11); contexts longer than that kernel takes run q / attention / to_out,
+  * exemplar tokens may carry a weight per sample (``context_weights``) and a map of where each applies (``context_regions``: regional
+    exemplars, a weight per query row - pbe_ctx_attention_rw_f16 on the same folded operands),
   * the softmax weights of that launch can be collected as attribution maps (``ContextMaps``: which exemplar each position attended
     to - pbe_ctx_attention_map_f16, the same launch with a side output),
   * bias, residual and the row-broadcast adds are GEMM epilogues.
 """
+from contextlib import nullcontext
 from types import SimpleNamespace
 
 import torch
@@ -29,6 +32,8 @@ from torch import nn
 from pbe_amd import ops
 from pbe_amd.hipmodule import HipModule, f32, require_gpu
 from pbe_amd.lib import PbeError
+
+LOG2E = 1.4426950408889634      # the attention kernels run exp2: scale log2(e) goes onto q
 
 
 def exists(val):
@@ -139,7 +144,7 @@ class CrossAttention(HipModule):
         (wqk8, sqk), (wv8, sv) = p.f8
         inner = self.heads * self.dim_head
         if self._mx8_out(N):                     # both projections write the MX-fp8 operands directly (no fp16 q | k / V^T)
-            q8, k8, v8 = ops.qkv_mx8_f8(x8, sx, wqk8, sqk, wv8, sv, B=B, H=self.heads, N=N, D=self.dim_head, q_alpha=self.scale * 1.4426950408889634)
+            q8, k8, v8 = ops.qkv_mx8_f8(x8, sx, wqk8, sqk, wv8, sv, B=B, H=self.heads, N=N, D=self.dim_head, q_alpha=self.scale * LOG2E)
             return ops.attention_mx8(q8, k8, v8, 1.0).view(B * N, inner)
         qk = ops.gemm_f8(x8, sx, wqk8, sqk)
         npad = (N + 7) // 8 * 8
@@ -162,7 +167,7 @@ class CrossAttention(HipModule):
         with a power-of-two scale per 32 elements (scale log2(e) goes onto q there unless the projection already applied it)."""
         inner, H, D = self.heads * self.dim_head, self.heads, self.dim_head
         if self.attn_fp8:
-            c = self.scale * 1.4426950408889634
+            c = self.scale * LOG2E
             q8 = ops.quant_mx8(qk, B, H, N, D, rs=2 * inner, alpha=1.0 if q_prescaled else c)
             k8 = ops.quant_mx8(qk[:, inner:], B, H, N, D, rs=2 * inner)
             v8 = ops.quant_mx8(vt, B, H, N, D, rs=vt_rs, vt=True)
@@ -467,13 +472,11 @@ class BasicTransformerBlock(HipModule):
         ns = SimpleNamespace(g1=f32(n1.weight), b1=f32(n1.bias), g3=f32(n3.weight), b3=f32(n3.bias), eps1=n1.eps, eps3=n3.eps, wqkv=None)
         inner = a.heads * a.dim_head
         if a.to_q.weight.shape[1] == a.to_k.weight.shape[1] == a.to_v.weight.shape[1]:
-            ns.qscale = a.scale * 1.4426950408889634             # q leaves the projection as scale log2(e) q (fp32 epilogue)
+            ns.qscale = a.scale * LOG2E                           # q leaves the projection as scale log2(e) q (fp32 epilogue)
             ns.wqkv, ns.c2qkv, ns.c1qkv = ops.pack_linear_ln(torch.cat([a.to_q.weight, a.to_k.weight, a.to_v.weight], 0), None, n1.weight, n1.bias)
             ns.c2qkv[:inner] *= ns.qscale                         # (alpha multiplies the product, the bias is added after it)
-        w, b = self.ff.net[0].proj.weight.detach().float(), self.ff.net[0].proj.bias.detach().float()
-        F = w.shape[0] // 2
-        wi, bi = torch.stack([w[:F], w[F:]], 1).reshape(2 * F, -1), torch.stack([b[:F], b[F:]], 1).reshape(2 * F)   # (value, gate) rows interleaved
-        ns.wg, ns.c2g, ns.c1g = ops.pack_linear_ln(wi, bi, n3.weight, n3.bias)
+        proj = self.ff.net[0].proj                       # (value, gate) rows interleaved, in fp32: pack_linear_ln folds the gain before it rounds
+        ns.wg, ns.c2g, ns.c1g = ops.pack_linear_ln(*ops.interleave_geglu(proj.weight.detach().float(), proj.bias.detach().float()), n3.weight, n3.bias)
         ns.m2 = None                                     # the multi-token attn2 pack, built on first use (_pack_multi)
         return ns
 
@@ -490,7 +493,7 @@ class BasicTransformerBlock(HipModule):
             a2, n2 = self.attn2, self.norm2
             H, D, Cq = a2.heads, a2.dim_head, a2.to_q.weight.shape[1]
             m.g2, m.b2, m.eps2 = f32(n2.weight), f32(n2.bias), n2.eps
-            m.qscale2 = a2.scale * 1.4426950408889634
+            m.qscale2 = a2.scale * LOG2E
             m.wq2, m.c2q2, m.c1q2 = ops.pack_linear_ln(a2.to_q.weight, None, n2.weight, n2.bias)
             wq32 = a2.to_q.weight.detach().float()
             ext = torch.zeros((H, Cq + 8, D), dtype=torch.float32, device=wq32.device)
@@ -535,6 +538,11 @@ class BasicTransformerBlock(HipModule):
         if Cq % 64 or not 64 <= Cq <= ops.CTX_MAX_C:
             raise PbeError(f"BasicTransformerBlock: {what} need a width that is a multiple of 64 in 64..{ops.CTX_MAX_C}, got {Cq}")
 
+    def _refuse_multi_f8(self):
+        if self.linear_fp8:
+            raise PbeError("BasicTransformerBlock: a multi-token context is not available with linear_fp8 (the fp8 path folds attn2's "
+                           "constant into the out-projection epilogue; the multi-token kernels take fp16 operands only)")
+
     def context_operands(self, context, weights=None, regional=False, maps=False):
         """What run() needs of a context, computed once per context.  weights: exemplar weights [B, K] or a ContextWeights
         (prepare_context_weights: validated there), None = every token counts once; their log2 rides beside the operands (CtxOperands.log2w /
@@ -553,9 +561,7 @@ class BasicTransformerBlock(HipModule):
         cw = prepare_context_weights(c, weights)
         if K == 1:                                # (any positive weight on a single token is exact: the softmax over one key is 1)
             return self.attn2.single_token_context(c)
-        if self.linear_fp8:
-            raise PbeError("BasicTransformerBlock: a multi-token context is not available with linear_fp8 (the fp8 path folds attn2's "
-                           "constant into the out-projection epilogue; the multi-token kernels take fp16 operands only)")
+        self._refuse_multi_f8()
         a2, p2 = self.attn2, self.attn2.pk()
         inner = a2.heads * a2.dim_head
         if regional:
@@ -595,7 +601,7 @@ class BasicTransformerBlock(HipModule):
 
     def _attn2(self, x1, st2, ctx, B, N, folded, out=None, stats_out=None):
         """x2 = x1 + attn2(norm2(x1), ctx) for a multi-token context -> (x2, RowStats of x2 or None when not folded).  st2: RowStats of
-        x1 (None: computed here).  out / stats_out: targets inside shared buffers (run_paired)."""
+        x1 (None: computed here).  out / stats_out: targets inside shared buffers (a guidance pair)."""
         p, a2, p2 = self._pack_multi(), self.attn2, self.attn2.pk()
         want = False if not folded else (stats_out if stats_out is not None else True)
         if isinstance(ctx, ops.CtxOperands):
@@ -626,109 +632,83 @@ class BasicTransformerBlock(HipModule):
         r = ops.gemm(o.view(B * N, inner), p2.wo, p2.bo, resid=x1, out=out, row_stats=want)
         return r if folded else (r, None)
 
-    def _ff(self, x2, st3, folded):
+    def _mode(self, N):
+        """How the block's LayerNorms are evaluated at N tokens: "f8" (linear_fp8: emitted as e4m3 + a scale per token, BASELINE
+        configs[4]), "folded" (into the GEMMs that read them, _folded) or "plain" (separate launches)."""
+        return "f8" if self.linear_fp8 else "folded" if self._folded(self.pk(), N) else "plain"
+
+    def _attn1_core(self, x2d, B, N, stats, mode):
+        """attn1(norm1(x)) before to_out, [B*N, inner].  It does not depend on the context: a guidance pair runs it once."""
         p = self.pk()
-        if folded:
-            h = ops.gemm(x2, p.wg, p.c2g, act=ops.ACT_GEGLU, ln=(st3, p.c1g, p.eps3))
+        if mode == "folded":
+            return self.attn1.self_attention_fused(x2d, stats if stats is not None else ops.row_stats(x2d), p, B, N)
+        if mode == "f8":
+            return self.attn1.self_attention_f8(*ops.layernorm_f8(x2d, p.g1, p.b1, p.eps1), B, N)
+        return self.attn1.self_attention(ops.layernorm(x2d, p.g1, p.b1, p.eps1), B, N)
+
+    def _attn1_out(self, a, x2d, N, mode, rowvec=None, out=None, stats_out=None):
+        """x1 = x + to_out(a) (+ rowvec [B, C] on the rows of each sample: attn2's constant of a one-token context) -> (x1, RowStats of
+        x1 or None when not folded).  out / stats_out: targets inside shared buffers (a guidance pair)."""
+        a1 = self.attn1.pk()
+        want = False if mode != "folded" else (stats_out if stats_out is not None else True)
+        r = ops.gemm(a, a1.wo, a1.bo, rowvec=rowvec, group_rows=0 if rowvec is None else N, resid=x2d, out=out, row_stats=want)
+        return r if mode == "folded" else (r, None)
+
+    def _ff(self, x, st, mode):
+        """x + ff(norm3(x)); st: RowStats of x (folded)."""
+        p = self.pk()
+        if mode == "folded":
+            h = ops.gemm(x, p.wg, p.c2g, act=ops.ACT_GEGLU, ln=(st, p.c1g, p.eps3))
             fp = self.ff.pk()
-            return ops.gemm(h, fp.w2, fp.b2, resid=x2)
-        return self.ff.run(ops.layernorm(x2, p.g3, p.b3, p.eps3), resid=x2)
+            return ops.gemm(h, fp.w2, fp.b2, resid=x)
+        if mode == "f8":
+            return self.ff.run_f8(*ops.layernorm_f8(x, p.g3, p.b3, p.eps3), resid=x)
+        return self.ff.run(ops.layernorm(x, p.g3, p.b3, p.eps3), resid=x)
 
-    def _attn1(self, x2d, B, N, stats, folded):
-        """x1 = x + attn1(norm1(x)) with no attn2 term -> (x1, RowStats of x1 or None when not folded)."""
-        p, a1 = self.pk(), self.attn1.pk()
-        if folded:
-            a = self.attn1.self_attention_fused(x2d, stats if stats is not None else ops.row_stats(x2d), p, B, N)
-            return ops.gemm(a, a1.wo, a1.bo, resid=x2d, row_stats=True)
-        a = self.attn1.self_attention(ops.layernorm(x2d, p.g1, p.b1, p.eps1), B, N)
-        return ops.gemm(a, a1.wo, a1.bo, resid=x2d), None
-
-    def _run_multi(self, x2d, B, N, ctx, stats):
-        """run() for a multi-token context: attn1, x1 = to_out(a) + x (+ row statistics), x2 = x1 + attn2 (pbe_ctx_attention_f16, or
-        q / attention / to_out beyond its limits), GEGLU with norm3 folded on x2's statistics, ff out + x2: six launches folded."""
-        if self.linear_fp8:
-            raise PbeError("BasicTransformerBlock: a multi-token context is not available with linear_fp8 (fp16 operands only)")
-        folded = self._folded(self.pk(), N)
-        x1, st2 = self._attn1(x2d, B, N, stats, folded)
-        x2, st3 = self._attn2(x1, st2, ctx, B, N, folded)
-        return self._ff(x2, st3, folded)
-
-    def _run_paired_multi(self, x2d, B, N, ctx, stats):
-        """run_paired() for a multi-token context (ctx for 2B samples): x1 does not depend on the context, so attn1 AND its output
-        projection run once at batch B; the halves part at attn2, each writing its half of the 2B buffer and of the statistics."""
-        if self.linear_fp8:
-            raise PbeError("BasicTransformerBlock: a multi-token context is not available with linear_fp8 (fp16 operands only)")
-        folded = self._folded(self.pk(), N)
-        M = B * N
-        x2 = torch.empty((2 * M, x2d.shape[1]), dtype=torch.float16, device=x2d.device)
-        fused = isinstance(ctx, ops.CtxOperands)
-        maxp = 1 if fused else (x2d.shape[1] + 63) // 64
-        buf = torch.empty((maxp, 2 * M, 2), dtype=torch.float32, device=x2d.device) if folded else None
-        parts = 1
-        with ops.pinned_batch_scale(2):              # batch-B launches take the tile of the batch-2B layer: same bits
-            x1, st2 = self._attn1(x2d, B, N, stats, folded)
-            if st2 is None and fused:
-                st2 = ops.row_stats(x1)
-            for half in (0, 1):
-                tgt = ops.RowStats(buf, maxp, 2 * M, half * M) if folded else None
-                _, got = self._attn2(x1, st2, ctx.rows(half * B, (half + 1) * B), B, N, folded, out=x2[half * M:(half + 1) * M], stats_out=tgt)
-                parts = got.parts if got is not None else 1
-        return self._ff(x2, ops.RowStats(buf, parts, 2 * M) if folded else None, folded)
+    def _block(self, x2d, B, N, ctx, stats, paired):
+        """The stage chain of run (ctx for B samples) and run_paired (x2d serves both halves, ctx holds 2B samples).  What does not depend
+        on the context runs once; the halves of a pair part at the first launch that does - attn1's out-projection for a one-token
+        constant, attn2 for multi-token operands - each writing its half of one 2B buffer and of its row statistics."""
+        mode, one, fused = self._mode(N), isinstance(ctx, torch.Tensor), isinstance(ctx, ops.CtxOperands)
+        if not one:
+            self._refuse_multi_f8()
+        folded = mode == "folded"
+        M, Cc = x2d.shape
+        halves = [(ctx, None, None)]
+        if paired:
+            planes = 1 if fused else (Cc + 63) // 64             # (the fused cross-attention kernel writes one partial)
+            x = torch.empty((2 * M, Cc), dtype=torch.float16, device=x2d.device)
+            buf = torch.empty((planes, 2 * M, 2), dtype=torch.float32, device=x2d.device) if folded else None
+            halves = [(ctx[h * B:(h + 1) * B] if one else ctx.rows(h * B, (h + 1) * B), x[h * M:(h + 1) * M],
+                       ops.RowStats(buf, planes, 2 * M, h * M) if folded else None) for h in (0, 1)]
+        # a pair's batch-B launches take the tile, split-K factor and statistics partials of the batch-2B layer: same bits.  A single run
+        # enters no scale of its own: that would undo its caller's
+        with ops.pinned_batch_scale(2) if paired else nullcontext():
+            a = self._attn1_core(x2d, B, N, stats, mode)
+            if one:
+                for c, out, tgt in halves:
+                    y, st = self._attn1_out(a, x2d, N, mode, c, out, tgt)
+            else:
+                x1, st1 = self._attn1_out(a, x2d, N, mode)
+                if st1 is None and fused:
+                    st1 = ops.row_stats(x1)
+                for c, out, tgt in halves:
+                    y, st = self._attn2(x1, st1, c, B, N, folded, out, tgt)
+        if paired:                                               # the joined buffer, with the partial count the last launch reported
+            y, st = x, ops.RowStats(buf, st.parts, 2 * M) if folded else None
+        return self._ff(y, st, mode)
 
     def run(self, x2d, B, N, ctx_vec, stats=None):
-        """x2d [B*N, C] fp16 residual stream; ctx_vec = context_operands(context): [B, C] = attn2's constant for a one-token context
-        (single_token_context), or the multi-token operands (ops.CtxOperands / ContextKV); stats = ops.RowStats of x2d's rows when its
-        producer emitted them (SpatialTransformer's proj_in does), else they are computed here."""
-        if not isinstance(ctx_vec, torch.Tensor):
-            return self._run_multi(x2d, B, N, ctx_vec, stats)
-        p = self.pk()
-        a1 = self.attn1.pk()
-        if self.linear_fp8:                      # BASELINE configs[4]: LayerNorm emits e4m3 + a scale per token; q|k, V^T and the GEGLU projection read it
-            a = self.attn1.self_attention_f8(*ops.layernorm_f8(x2d, p.g1, p.b1, p.eps1), B, N)
-            x1 = ops.gemm(a, a1.wo, a1.bo, rowvec=ctx_vec, group_rows=N, resid=x2d)
-            return self.ff.run_f8(*ops.layernorm_f8(x1, p.g3, p.b3, p.eps3), resid=x1)
-        if self._folded(p, N):                   # 5 launches: q|k|v^T, attention, to_out (+ row statistics), GEGLU, ff out
-            a = self.attn1.self_attention_fused(x2d, stats if stats is not None else ops.row_stats(x2d), p, B, N)
-            x1, st3 = ops.gemm(a, a1.wo, a1.bo, rowvec=ctx_vec, group_rows=N, resid=x2d, row_stats=True)   # attn1 + x, + attn2 constant
-            h = ops.gemm(x1, p.wg, p.c2g, act=ops.ACT_GEGLU, ln=(st3, p.c1g, p.eps3))
-            fp = self.ff.pk()
-            return ops.gemm(h, fp.w2, fp.b2, resid=x1)
-        a = self.attn1.self_attention(ops.layernorm(x2d, p.g1, p.b1, p.eps1), B, N)
-        x1 = ops.gemm(a, a1.wo, a1.bo, rowvec=ctx_vec, group_rows=N, resid=x2d)          # attn1 + x, + attn2 constant
-        return self.ff.run(ops.layernorm(x1, p.g3, p.b3, p.eps3), resid=x1)
+        """x2d [B*N, C] fp16 residual stream -> the block's output, same shape.  ctx_vec = context_operands(context) for the B samples:
+        [B, C] = attn2's constant for a one-token context, or the multi-token operands (ops.CtxOperands / ContextKV); stats =
+        ops.RowStats of x2d's rows when its producer emitted them (SpatialTransformer's proj_in does), else the folded chain computes
+        them.  Stages and modes: _block."""
+        return self._block(x2d, B, N, ctx_vec, stats, False)
 
     def run_paired(self, x2d, B, N, ctx_vec, stats=None):
-        """Guidance pair with a SHARED input (x2d [B*N, C] serves both halves, ctx_vec [2B, C] differs): LayerNorm, q/k/v
-        and the attention core do not depend on the context, so they run once at batch B; the two halves part where
-        attn2's constant is added (the out-projection epilogue).  Returns [2B*N, C].  With multi-token operands (for 2B samples) the
-        shared part also covers the out-projection: the halves part at attn2 itself (_run_paired_multi)."""
-        if not isinstance(ctx_vec, torch.Tensor):
-            return self._run_paired_multi(x2d, B, N, ctx_vec, stats)
-        p = self.pk()
-        x1 = torch.empty((2 * B * N, x2d.shape[1]), dtype=torch.float16, device=x2d.device)
-        if self._folded(p, N):
-            a1 = self.attn1.pk()
-            maxp = (x2d.shape[1] + 63) // 64
-            st3 = ops.RowStats(torch.empty((maxp, 2 * B * N, 2), dtype=torch.float32, device=x2d.device), maxp, 2 * B * N)
-            with ops.pinned_batch_scale(2):          # batch-B launches take the tile (= statistics partials) of the batch-2B layer: same bits
-                a = self.attn1.self_attention_fused(x2d, stats if stats is not None else ops.row_stats(x2d), p, B, N)
-                for half in (0, 1):
-                    _, got = ops.gemm(a, a1.wo, a1.bo, rowvec=ctx_vec[half * B:(half + 1) * B], group_rows=N, resid=x2d, out=x1[half * B * N:(half + 1) * B * N],
-                                      row_stats=ops.RowStats(st3.buf, maxp, st3.ld, half * B * N))
-            h = ops.gemm(x1, p.wg, p.c2g, act=ops.ACT_GEGLU, ln=(ops.RowStats(st3.buf, got.parts, st3.ld), p.c1g, p.eps3))
-            fp = self.ff.pk()
-            return ops.gemm(h, fp.w2, fp.b2, resid=x1)
-        with ops.pinned_batch_scale(2):              # batch-B launches take the split-K factor of the batch-2B layer: same bits
-            if self.linear_fp8:                      # (fp8 GEMMs never split K: nothing to pin for them)
-                a = self.attn1.self_attention_f8(*ops.layernorm_f8(x2d, p.g1, p.b1, p.eps1), B, N)
-            else:
-                a = self.attn1.self_attention(ops.layernorm(x2d, p.g1, p.b1, p.eps1), B, N)
-            a1 = self.attn1.pk()
-            for half in (0, 1):
-                ops.gemm(a, a1.wo, a1.bo, rowvec=ctx_vec[half * B:(half + 1) * B], group_rows=N, resid=x2d, out=x1[half * B * N:(half + 1) * B * N])
-        if self.linear_fp8:
-            return self.ff.run_f8(*ops.layernorm_f8(x1, p.g3, p.b3, p.eps3), resid=x1)
-        return self.ff.run(ops.layernorm(x1, p.g3, p.b3, p.eps3), resid=x1)
+        """Guidance pair with a SHARED input: x2d [B*N, C] serves both halves, ctx_vec holds the 2B contexts -> [2B*N, C], the bits of
+        run on the duplicated input.  Everything upstream of the first launch that depends on the context runs once at batch B (_block)."""
+        return self._block(x2d, B, N, ctx_vec, stats, True)
 
     def forward(self, x, context=None, context_weights=None, context_row_weights=None, attn_map=None):
         """x [B, N, C], context [B, K, Dc] with K >= 1 tokens per sample (context_weights [B, K] or None) -> [B, N, C].
@@ -843,10 +823,7 @@ class SpatialTransformer(HipModule):
         require_gpu(x, "SpatialTransformer")
         if context is None:
             raise PbeError("SpatialTransformer: context is required on the Paint-by-Example path")
-        if context_maps is not None:
-            if context_maps.B is None:
-                context_maps.bind(context.shape[0], context.shape[1], x.device)
-            y = self.run(ops.nchw_to_nhwc(x.float()), self.context_vectors(context, context_weights, context_regions, maps=True), context_maps)
-            return ops.nhwc_to_nchw(y).to(x.dtype)
-        y = self.run(ops.nchw_to_nhwc(x.float()), self.context_vectors(context, context_weights, context_regions))
-        return ops.nhwc_to_nchw(y).to(x.dtype)
+        if context_maps is not None and context_maps.B is None:
+            context_maps.bind(context.shape[0], context.shape[1], x.device)
+        vecs = self.context_vectors(context, context_weights, context_regions, maps=context_maps is not None)
+        return ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(x.float()), vecs, context_maps)).to(x.dtype)

@@ -368,8 +368,6 @@ class UNetModel(HipModule):
             raise PbeError("UNetModel.forward needs timesteps and context")
         p = self.pk()
         x16 = ops.nchw_to_nhwc(x.float(), p.cin_pad)
-        if context_maps is not None:          # (an attention.ContextMaps: see forward_nhwc)
-            out = self.forward_nhwc(x16, timesteps, context, context_weights=context_weights, context_regions=context_regions, context_maps=context_maps)
-            return ops.nhwc_to_nchw(out).to(torch.float16)
-        out = self.forward_nhwc(x16, timesteps, context, context_weights=context_weights, context_regions=context_regions)
+        out = self.forward_nhwc(x16, timesteps, context, context_weights=context_weights, context_regions=context_regions,
+                                context_maps=context_maps)          # (an attention.ContextMaps or None: see forward_nhwc)
         return ops.nhwc_to_nchw(out).to(torch.float16)

@@ -1321,12 +1321,16 @@ def pack_linear_ln(w: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.T
     return wg, c2.float().contiguous(), wg.double().sum(1).float().contiguous()
 
 
-def pack_geglu(w: torch.Tensor, b: torch.Tensor):
+def interleave_geglu(w: torch.Tensor, b: torch.Tensor):
     """GEGLU projection [2F, K] (rows 0..F-1 = value, F..2F-1 = gate, attention.py:41-45) -> rows interleaved
-    (x_0, g_0, x_1, g_1, ...) so the GEMM epilogue sees each (value, gate) pair in one accumulator quad."""
+    (x_0, g_0, x_1, g_1, ...) so the GEMM epilogue sees each (value, gate) pair in one accumulator quad.  Dtypes are kept."""
     F = w.shape[0] // 2
-    wi = torch.stack([w[:F], w[F:]], 1).reshape(2 * F, -1)
-    bi = torch.stack([b[:F], b[F:]], 1).reshape(2 * F)
+    return torch.stack([w[:F], w[F:]], 1).reshape(2 * F, -1), torch.stack([b[:F], b[F:]], 1).reshape(2 * F)
+
+
+def pack_geglu(w: torch.Tensor, b: torch.Tensor):
+    """interleave_geglu as the GEMM takes it: fp16 weights, fp32 bias."""
+    wi, bi = interleave_geglu(w, b)
     return wi.to(torch.float16).contiguous(), bi.detach().float().contiguous()
 
 
