@@ -52,7 +52,7 @@ class DDIMSampler(PLMSSampler):
         if self.require_gpu and device.type != "cuda":
             raise PbeError("DDIMSampler: the model must live on an MI355X; there is no CPU path")
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        img = (torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)).contiguous()
         if "rest" in kwargs and "test_model_kwargs" not in kwargs:       # ddim.py:201-202: rest = cat(z_inpaint, mask)
             rest = kwargs["rest"]
             z_inp, msk = rest[:, :4], rest[:, 4:5]

@@ -209,7 +209,7 @@ class PLMSSampler(object):
         if self.require_gpu and device.type != "cuda":
             raise PbeError("PLMSSampler: the model must live on an MI355X (model.to('cuda')); there is no CPU path")
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        img = (torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)).contiguous()
         z_inp, msk = inpaint_kwargs(kwargs)
         z_inp = z_inp.to(device=device, dtype=torch.float32).contiguous()
         msk = msk.to(device=device, dtype=torch.float32).contiguous()

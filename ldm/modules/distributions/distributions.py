@@ -26,7 +26,7 @@ class DiagonalGaussianDistribution(object):
             return scale * self.mean
         if noise is None:
             noise = torch.randn((B, self.z, h, w))
-        noise = noise.to(device=self.parameters.device, dtype=torch.float32)
+        noise = noise.to(device=self.parameters.device, dtype=torch.float32).contiguous()
         return ops.posterior_sample(self.parameters, noise, scale)
 
     def mode(self):

@@ -277,6 +277,10 @@ extern "C" int pbe_qsample_blend_f32(const float* x0, const float* noise, const 
 }
 
 // ---- VAE posterior sample / latent un-scale / image post ---------------------------------------
+// exp in fp64, rounded once to fp32: under -ffp-contract=fast the backend fuses inside the inline expansion of expf as well - its
+// difference ph - rint(ph) (ph = x log2e rounded) becomes fma(x, log2e, -rint(ph)), which holds the rounding error of ph that the low word
+// then adds a second time - and expf is off by up to |x| 2^-24 relative (7 ulp at logvar = -30) instead of under 2 ulp.  One call per latent
+// element per image: the cost does not show.
 __global__ void posterior_kernel(const h16* mom, int ld, const float* eps, float* z, int HW, float scale, long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;     // over B*4*HW
     if (i >= total) return;
@@ -285,7 +289,7 @@ __global__ void posterior_kernel(const h16* mom, int ld, const float* eps, float
     const h16* m = mom + (b * HW + px) * ld;
     const float mean = (float)m[c];
     const float logvar = fminf(fmaxf((float)m[4 + c], -30.f), 20.f);
-    z[i] = scale * (mean + expf(0.5f * logvar) * eps[i]);
+    z[i] = scale * (mean + (float)exp(0.5 * (double)logvar) * eps[i]);
 }
 extern "C" int pbe_posterior_sample(const void* moments, int32_t ld, const float* eps, float* z, int32_t B, int32_t HW, float scale,
                                     pbe_stream_t stream) {

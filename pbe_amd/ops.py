@@ -986,10 +986,12 @@ def nchw_to_nhwc(x: torch.Tensor, cp: Optional[int] = None) -> torch.Tensor:
 def nhwc_to_nchw(x: torch.Tensor, c: Optional[int] = None) -> torch.Tensor:
     """fp16 NHWC [B,H,W,ld] -> fp32 NCHW of the first c channels."""
     _h(x, "nhwc_to_nchw x")
-    if not x.is_contiguous():
-        raise _l.PbeError("nhwc_to_nchw: x must be contiguous")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise _l.PbeError(f"nhwc_to_nchw: x must be contiguous fp16 NHWC [B, H, W, ld], got {tuple(x.shape)}")
     B, H, W, ld = x.shape
-    c = ld if c is None else c
+    c = ld if c is None else int(c)
+    if not 1 <= c <= ld:
+        raise _l.PbeError(f"nhwc_to_nchw: c = {c} channels of a tensor with {ld}")
     y = torch.empty((B, c, H, W), dtype=torch.float32, device=x.device)
     _l.check(_l.load().pbe_nhwc_f16_to_nchw_f32(_p(x), _p(y), B, c, H * W, ld, _stream()), "pbe_nhwc_f16_to_nchw_f32")
     return y
@@ -1010,14 +1012,23 @@ def plms_update(eps_out: torch.Tensor, dup: int, cfg_scale: float, x: torch.Tens
                 want_pred: bool = True):
     """Fused CFG combine + multistep weights + x_prev / pred_x0 (plms.py:188-189, 202-219, 230-244)."""
     _h(eps_out, "plms eps_out"); _f(x, "plms x")
+    if dup not in (1, 2) or len(coef8) != 8 or len(hist) > 3:
+        raise _l.PbeError(f"plms_update: dup must be 1 or 2, coef8 eight floats and hist at most 3 tensors, got dup={dup}, {len(coef8)} coefficients, "
+                          f"{len(hist)} history tensors")
+    if x.dim() != 4 or x.shape[1] != 4 or not x.is_contiguous():
+        raise _l.PbeError(f"plms_update: x must be contiguous fp32 NCHW [B, 4, H, W], got {tuple(x.shape)}")
     B, _, H, W = x.shape
-    ld = eps_out.shape[-1]
+    if eps_out.dim() != 4 or tuple(eps_out.shape[:3]) != (dup * B, H, W) or eps_out.shape[3] < 4 or not eps_out.is_contiguous() or eps_out.device != x.device:
+        raise _l.PbeError(f"plms_update: eps_out must be contiguous fp16 NHWC [{dup * B}, {H}, {W}, ld >= 4] on x's device, got {tuple(eps_out.shape)}")
+    ld = eps_out.shape[3]
+    h = [None, None, None]
+    for i, t in enumerate(hist):
+        h[i] = _f(t, "plms history")
+        if t.shape != x.shape or not t.is_contiguous() or t.device != x.device:
+            raise _l.PbeError(f"plms_update: history tensor {i} must match x ({tuple(x.shape)}, contiguous, same device), got {tuple(t.shape)}")
     e_t = torch.empty_like(x) if want_e_t else None
     pred = torch.empty_like(x) if want_pred else None
     x_prev = torch.empty_like(x)
-    h = [None, None, None]
-    for i, t in enumerate(hist[:3]):
-        h[i] = _f(t, "plms history")
     arr = (C.c_float * 8)(*[float(v) for v in coef8])
     _l.check(_l.load().pbe_plms_update(_p(eps_out), ld, dup, float(cfg_scale), _p(x), _p(h[0]), _p(h[1]), _p(h[2]), arr, _p(e_t),
                                        _p(x_prev), _p(pred), B, H * W, _stream()), "pbe_plms_update")
@@ -1075,10 +1086,16 @@ def qsample_blend(x0: torch.Tensor, noise: torch.Tensor, mask: torch.Tensor, img
 
 
 def posterior_sample(moments: torch.Tensor, eps: torch.Tensor, scale: float) -> torch.Tensor:
+    """z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps): moments fp16 NHWC [B, H, W, ld >= 8] (mean in channels 0 .. 3, logvar in
+    4 .. 7), eps fp32 NCHW [B, 4, H, W] -> fp32 NCHW [B, 4, H, W]."""
     _h(moments, "posterior moments"); _f(eps, "posterior eps")
+    if moments.dim() != 4 or moments.shape[3] < 8 or not moments.is_contiguous():
+        raise _l.PbeError(f"posterior_sample: moments must be contiguous fp16 NHWC [B, H, W, ld >= 8], got {tuple(moments.shape)}")
     B, H, W, ld = moments.shape
+    if tuple(eps.shape) != (B, 4, H, W) or not eps.is_contiguous() or eps.device != moments.device:
+        raise _l.PbeError(f"posterior_sample: eps must be contiguous fp32 NCHW [{B}, 4, {H}, {W}] on the moments' device, got {tuple(eps.shape)}")
     z = torch.empty((B, 4, H, W), dtype=torch.float32, device=moments.device)
-    _l.check(_l.load().pbe_posterior_sample(_p(moments), ld, _p(eps.contiguous()), _p(z), B, H * W, float(scale), _stream()), "pbe_posterior_sample")
+    _l.check(_l.load().pbe_posterior_sample(_p(moments), ld, _p(eps), _p(z), B, H * W, float(scale), _stream()), "pbe_posterior_sample")
     return z
 
 
@@ -1092,7 +1109,10 @@ def scale_latent(z: torch.Tensor, inv_scale: float) -> torch.Tensor:
 
 
 def image_post(x: torch.Tensor) -> torch.Tensor:
+    """clamp((x + 1) / 2, 0, 1) of the first 3 channels: fp16 NHWC [B, H, W, ld >= 3] -> fp32 NCHW [B, 3, H, W]."""
     _h(x, "image_post x")
+    if x.dim() != 4 or x.shape[3] < 3 or not x.is_contiguous():
+        raise _l.PbeError(f"image_post: x must be contiguous fp16 NHWC [B, H, W, ld >= 3], got {tuple(x.shape)}")
     B, H, W, ld = x.shape
     y = torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
     _l.check(_l.load().pbe_image_post_f32(_p(x), _p(y), B, H * W, ld, _stream()), "pbe_image_post_f32")
