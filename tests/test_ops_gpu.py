@@ -73,6 +73,12 @@ def test_gemm_epilogue(dev, act):
     ref = fn(pre).half().float() + res.float()
     got = ops.gemm(a.to(dev), w.to(dev), bias.to(dev), rowvec=rv.to(dev), group_rows=G, resid=res.to(dev), act=act, alpha=0.5)
     _close(got, ref, what=f"gemm epilogue act={act}")
+    # and per element against fp64 (tests/tilecheck.py expect: accumulation, epilogue, activation arm, the two fp16 stores)
+    import tilecheck
+    A, W = a.double(), w.double()
+    want, bound = tilecheck.expect(A @ W.t(), A.abs() @ W.abs().t(), K, alpha=torch.full((N,), 0.5, dtype=torch.float64), bias=bias.double(),
+                                   rowvec=rv.double().repeat_interleave(G, 0), act=act, resid=res.double())
+    tilecheck.check(got.cpu(), want, tilecheck.clamp_to_close(want, bound, (2e-3, 1e-3)), f"gemm epilogue act={act}")
 
 
 @pytest.mark.parametrize("M,N,K", [(512, 1280, 5120), (256, 640, 2048), (130, 320, 4096)])
@@ -414,6 +420,12 @@ def test_gemm_layernorm_fold(dev, M, N, K, act):
     for st in (ops.row_stats(xd),):
         got = ops.gemm(xd, wg.to(dev), c2.to(dev), act=act, ln=(st, c1.to(dev), 1e-5))
         _close(got, ref, rtol=3e-3, atol=3e-3, what=f"LayerNorm-folded GEMM {M}x{N}x{K} act={act}")
+        # and per element against fp64 on the first and last row tile and 64 seeded rows (tests/actref.py ln_fold_expect)
+        import actref
+        import tilecheck
+        rows = tilecheck.gemm_rows(M, 128, N + K + act, 64)
+        want, bound = actref.ln_fold_expect(x[rows], wg, c2, c1, act)
+        tilecheck.check(got[rows].cpu(), want, tilecheck.clamp_to_close(want, bound, (3e-3, 3e-3)), f"LayerNorm-folded GEMM {M}x{N}x{K} act={act}", rows)
     old = ops.gemm(ops.layernorm(xd, gamma.to(dev), beta.to(dev), 1e-5), wi.half().to(dev), bi.to(dev), act=act)
     e_new, e_old = (got.float().cpu() - ref).norm() / ref.norm(), (old.float().cpu() - ref).norm() / ref.norm()
     assert e_new <= 1.5 * e_old + 1e-4, (e_new, e_old)                      # no worse than the separate-LayerNorm path it replaces

@@ -28,6 +28,7 @@ Per-element bound (rounding model; u32 = 2^-24, u16 = 2^-11, S = (|A| @ |W|^T) o
   LayerNorm fold    rstd * (acc term + 4 u32 (|acc| + |mean colsum|) + d_mean |colsum|) + |pre| * eps_r, with the one-pass fp32 row
                     statistics' errors d_mean = ACC_C u32 sqrt(K) E|x| and eps_r = ACC_C u32 sqrt(K) E[x^2] / (var + eps) (relative, rstd)
   GEGLU             |gelu(g)| d_v + 1.13 |v| d_g + 7.1e-7 |v| (the kernel's GELU fit)
+  act 1 / 2 / 3     max |act'| (1.1 SiLU and quick-GELU, 1.13 GELU) times the pre-activation's error + the arm's own rounding (actref.py)
   fp16 stores       u16 |value| + 2^-25 for the stored value, and again after the residual add
 and never looser than the limit of the existing _close test of the same op (rtol * max|ref| + atol over the sampled elements).
 """
@@ -79,6 +80,7 @@ class Case:
         self.bias, self.resid, self.rowvec, self.act = True, False, False, 0
         self.ln = self.vt = self.row_stats = False
         self.group_stats, self.alpha, self.alpha_cols, self.tokens, self.offset = 0, 1.0, 0, 0, False
+        self.wscale = 1.0                        # weights are drawn at wscale / sqrt(K): the pre-activation's std (actref.py raises it to 3)
         if self.form == "c":
             self.B, self.H, self.W, self.C1, self.C2, self.Cout, self.stride, self.pad, self.ups = f
             hv, wv = (2 * self.H, 2 * self.W) if self.ups else (self.H, self.W)
@@ -168,7 +170,7 @@ def descriptor(case: Case, tile_cfg=None):
         d.B, d.H, d.W, d.C1, d.C2, d.Cout = case.B, case.H, case.W, case.C1, case.C2, case.Cout
         d.stride, d.pad, d.upsample = case.stride, case.pad, case.ups
         d.ldv = case.Cout if case.rowvec else 0
-        d.act, d.workspace, d.workspace_bytes, d.tile_cfg, d.kblock = 0, _FAKE, ops.SPLITK_WS_BYTES, cfg, 64
+        d.act, d.workspace, d.workspace_bytes, d.tile_cfg, d.kblock = case.act, _FAKE, ops.SPLITK_WS_BYTES, cfg, 64
         if case.group_stats:
             case._gs_blocks = ctypes.c_int32(0)
             d.group_stats_out, d.group_stats_groups = _FAKE, case.group_stats
@@ -273,7 +275,11 @@ def expect(acc, S, K, *, alpha=None, bias=None, rowvec=None, ln=None, act=0, res
         if v is not None:
             dpre = dpre + 2 * U32 * (pre.abs() + v.abs())
             pre = pre + v
-    if act == 4:                                 # interleaved (value, gate) columns
+    if act in (1, 2, 3):                         # SiLU / erf-GELU / quick-GELU: the slope times |d pre|, and the arm's own rounding (actref.py)
+        import actref
+        y = actref.act64(pre, act)
+        dy = actref.ACT_DMAX[act] * dpre + actref.act_term(pre, act)
+    elif act == 4:                               # interleaved (value, gate) columns
         v, gt, dv, dg = pre[:, 0::2], pre[:, 1::2], dpre[:, 0::2], dpre[:, 1::2]
         gel = gt * 0.5 * (1 + torch.erf(gt / math.sqrt(2.0)))
         y = v * gel
@@ -368,7 +374,7 @@ def run_gemm(case: Case, dev, *, mutate=False):
     if case.offset:
         a = a.clone()
         a[::97] += LN_OFFSET
-    w = _randn((N, K), gen, dev, 1.0 / math.sqrt(K))
+    w = _randn((N, K), gen, dev, case.wscale / math.sqrt(K))
     bias = torch.randn(N, generator=gen, device=dev) * 0.5
     t["A"], t["bias"] = a, bias
     kw = {}
@@ -448,10 +454,10 @@ def run_conv(case: Case, dev, *, mutate=False):
     gen = torch.Generator(device=dev).manual_seed(seed_of(case.key))
     B, H, W, C1, C2, Co = case.B, case.H, case.W, case.C1, case.C2, case.Cout
     t = {"x1": _randn((B, H, W, C1), gen, dev), "x2": _randn((B, H, W, C2), gen, dev) if C2 else None}
-    w = torch.randn(Co, C1 + C2, 3, 3, generator=gen, device=dev) / math.sqrt(9 * (C1 + C2))
+    w = torch.randn(Co, C1 + C2, 3, 3, generator=gen, device=dev) * (case.wscale / math.sqrt(9 * (C1 + C2)))
     bias = torch.randn(Co, generator=gen, device=dev) * 0.5
     t["bias"] = bias
-    kw = {}
+    kw = {"act": case.act} if case.act else {}
     if case.ups == 2:
         wp = ops.pack_conv3x3_up_phases(w)                               # [4, Co, 4 * C1], the fp16 weights sent
         t["wp"] = wp
@@ -540,7 +546,7 @@ def reference_conv(case: Case, t, sel):
     acc = acc.permute(0, 2, 1).reshape(-1, Co)
     S = S.permute(0, 2, 1).reshape(-1, Co)
     bidx = torch.tensor([b for b, _ in sel for _ in range(Wo)])
-    kw = dict(bias=t["bias"].double().cpu())
+    kw = dict(bias=t["bias"].double().cpu(), act=case.act)
     if t.get("rowvec") is not None:
         kw["rowvec"] = t["rowvec"].double().cpu()[bidx]
     if t.get("resid") is not None:
