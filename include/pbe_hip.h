@@ -218,8 +218,9 @@ int pbe_layernorm_f16(const void* X, const float* gamma, const float* beta, void
 int pbe_row_stats_f16(const void* X, float* out, int64_t rows, int32_t C, int64_t ldx, pbe_stream_t stream);
 
 /* pbe_layernorm_f8 — the same LayerNorm emitting OCP e4m3 bytes and one fp32 scale per row (BASELINE configs[4]):
- * Y[r, :] = e4m3(LN(X[r, :]) / row_scale[r]), row_scale[r] = max|LN(X[r, :])| / 448; ldy in bytes (multiple of 16).  Feeds the fp8
- * operand form of pbe_gemm_f16 (A = Y, a_scale = row_scale). */
+ * Y[r, :] = e4m3(LN(X[r, :]) / row_scale[r]), row_scale[r] = max|LN(X[r, :])| / 448, floored at 2^-100 (1 for an all-zero row): always
+ * finite, normal and positive; round to nearest even, saturating; ldy in bytes (multiple of 16).  Feeds the fp8 operand form of
+ * pbe_gemm_f16 (A = Y, a_scale = row_scale). */
 int pbe_layernorm_f8(const void* X, const float* gamma, const float* beta, void* Y, float* row_scale, int64_t rows,
                      int32_t C, int64_t ldx, int64_t ldy, float eps, pbe_stream_t stream);
 

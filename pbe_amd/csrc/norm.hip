@@ -436,7 +436,8 @@ __global__ void __launch_bounds__(256) layernorm_f8_kernel(const h16* X, const f
         }
     }
     amax = wave_max(amax);
-    const float scale = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+    // floored at 2^-100: below 448 * 2^-128 the scale is subnormal and 1 / scale overflows (a row of NaN bytes); no other row changes
+    const float scale = amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), 0x1p-100f) : 1.0f;
     const float inv = 1.0f / scale;
     if (lane == 0) S[row] = scale;
 #pragma unroll

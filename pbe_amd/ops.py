@@ -580,10 +580,11 @@ def gemm_f8(a8: torch.Tensor, a_scale: torch.Tensor, w8: torch.Tensor, w_scale: 
 
 def pack_linear_f8(w: torch.Tensor):
     """[N, K] fp32 weight -> (OCP e4m3 bytes uint8 [N, K], fp32 scale [N]) with one scale per output channel: w ~ w8 * scale[:, None].
-    One-off, at pack time (BASELINE configs[4])."""
+    One-off, at pack time (BASELINE configs[4]).  A non-zero row's scale is floored at 2^-100 (pbe_layernorm_f8 has the same floor): below
+    448 * 2^-128 the quotient 1 / scale overflows, and the row's bytes would come out NaN."""
     w2 = w.detach().reshape(w.shape[0], -1).float()
     amax = w2.abs().amax(1)
-    scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    scale = torch.where(amax > 0, (amax / 448.0).clamp(min=2.0 ** -100), torch.ones_like(amax))
     w8 = (w2 / scale[:, None]).to(torch.float8_e4m3fn).view(torch.uint8).contiguous()
     return w8, scale.contiguous()
 

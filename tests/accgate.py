@@ -385,8 +385,8 @@ def gn_emulate(x, gamma, beta, eps, silu, rows_per_block, groups=32, stats_rows=
 
 
 # ---- LayerNorm ---------------------------------------------------------------------------------------------------------------------
-def ln_reference(x, gamma, beta, eps):
-    """(want, bound) fp64 of LayerNorm over the last dim of x [rows, C]."""
+def ln_terms(x, gamma, beta, eps):
+    """(y, dy) fp64 of LayerNorm over the last dim of x [rows, C]: the value and the error of the kernel's fp32 result before any store."""
     C = x.shape[-1]
     xd, gm, bt = x.double(), gamma.double(), beta.double()
     mean = xd.mean(-1, keepdim=True)
@@ -398,6 +398,12 @@ def ln_reference(x, gamma, beta, eps):
     pre = (xd - mean) * rstd * gm
     y = pre + bt
     dy = gm.abs() * rstd * ((xd - mean).abs() * eps_r + d_mean) + 4 * U32 * (pre.abs() + bt.abs())
+    return y, dy
+
+
+def ln_reference(x, gamma, beta, eps):
+    """(want, bound) fp64 of LayerNorm over the last dim of x [rows, C], fp16 store included."""
+    y, dy = ln_terms(x, gamma, beta, eps)
     bound = dy * (1 + U16) + U16 * y.abs() + 2.0 ** -25
     return y, clamp_to_close(y, bound, CLOSE["norm"])
 
