@@ -530,6 +530,32 @@ int pbe_feather_alpha_f32(const void* mask, float* alpha, int32_t Hs, int32_t Ws
 int pbe_paste_window_u8(const float* result, const float* alpha, void* picture, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh,
                         int32_t ww, int32_t H, int32_t W, pbe_stream_t stream);
 
+/* Holes of a mask (pbe_amd/csrc/holes.hip; not in the reference): connected components of the hole, for one window per hole
+ * (pbe_amd.window.plan_holes, pipeline.inpaint_holes).  mask: u8 [Hs, Ws] contiguous, a byte >= 128 is a hole pixel; labels: i32 [Hs, Ws]
+ * contiguous.  Edges up to 16384, so a linear index y * Ws + x fits an int32.  Integers only: every output is unique and compared by
+ * equality.  Caller-owned buffers, an explicit stream, no synchronisation and no host read-back; no workgroup waits for another.
+ * pbe_mask_components_u8_i32 labels[y, x] = -1 on a non-hole pixel, else the SMALLEST linear index of any pixel of its connected component;
+ *                            connectivity 8 (diagonal neighbours join) or 4, anything else is an error.  Every element of labels is written,
+ *                            no byte outside mask is read.  Union-find on the label plane itself: 64 x 16 tiles in LDS, atomicMin links
+ *                            across the tile borders in global memory, a flattening pass (three launches).  `workspace`: at least
+ *                            pbe_mask_components_workspace_bytes(Hs, Ws) bytes of device scratch.
+ * pbe_component_boxes_i32    labels as written above -> *count = the number of components (device int32; the true number even above
+ *                            `capacity`) and, if count <= capacity, rows 0 .. count - 1 of table (i32 [capacity, 6]) = (label, ya, yb, xa,
+ *                            xb, area) of the distinct components, bounds inclusive, area in pixels, in unspecified order; rows from count
+ *                            on are not written.  If count > capacity the table's content is unspecified (nothing outside it is written).
+ *                            1 <= capacity <= 2^20.  A wave sums the pixels that share a label over 16 rows of 64 columns before its atomics.  `workspace`: at
+ *                            least pbe_component_boxes_workspace_bytes(Hs, Ws, capacity) bytes.
+ * pbe_select_components_u8   out_mask[y, x] = 255 if labels[y, x] is in `wanted` (device i32 [n_wanted], ASCENDING, 0 <= n_wanted <= 4096),
+ *                            else 0; u8 [Hs, Ws], every byte written. */
+size_t pbe_mask_components_workspace_bytes(int32_t Hs, int32_t Ws);
+int pbe_mask_components_u8_i32(const void* mask, int32_t* labels, int32_t Hs, int32_t Ws, int32_t connectivity, void* workspace,
+                               size_t workspace_bytes, pbe_stream_t stream);
+size_t pbe_component_boxes_workspace_bytes(int32_t Hs, int32_t Ws, int32_t capacity);
+int pbe_component_boxes_i32(const int32_t* labels, int32_t* table, int32_t* count, int32_t Hs, int32_t Ws, int32_t capacity, void* workspace,
+                            size_t workspace_bytes, pbe_stream_t stream);
+int pbe_select_components_u8(const int32_t* labels, const int32_t* wanted, int32_t n_wanted, void* out_mask, int32_t Hs, int32_t Ws,
+                             pbe_stream_t stream);
+
 /* pbe_tune— developer knobs for A/B runs in one process (never needed for correctness):
  * key 1: force an implicit-GEMM tile config index (-1 = heuristic); key 2: allow split-K (0/1);
  * key 3: attention queries-per-wave factor (0 = heuristic, 1, 2); key 4: ping-pong main loop of the halo-resident conv tiles (0/1);

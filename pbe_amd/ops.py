@@ -1264,6 +1264,84 @@ def paste_window(result: torch.Tensor, alpha: torch.Tensor, picture: torch.Tenso
     return picture
 
 
+# ---- holes of a mask (csrc/holes.hip): connected components, their boxes, the mask of some of them -----------------------------------
+def _plane_args(what: str, plane: torch.Tensor, dtype) -> Tuple[int, int]:
+    """(Hs, Ws) of a contiguous [Hs, Ws] tensor of `dtype` on the GPU with edges up to 16384."""
+    _req(plane, dtype, what)
+    if plane.dim() != 2 or not plane.is_contiguous() or plane.numel() == 0 or max(plane.shape) > 16384:
+        raise _l.PbeError(f"{what}: expected a contiguous {dtype} [Hs, Ws] tensor with edges in 1 .. 16384, got {tuple(plane.shape)} with strides "
+                          f"{tuple(plane.stride())}")
+    return int(plane.shape[0]), int(plane.shape[1])
+
+
+def _plane_out(what: str, out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _req(out, dtype, f"{what} out")
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise _l.PbeError(f"{what}: out must be a contiguous {dtype} {tuple(shape)} tensor on {device}, got {tuple(out.shape)}")
+    return out
+
+
+def _holes_ws(device, need: int) -> torch.Tensor:
+    key = (device.index, "holes")
+    ws = _ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=device)
+        _ws[key] = ws
+    return ws
+
+
+def mask_components(mask: torch.Tensor, connectivity: int = 8, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [Hs, Ws] mask (a byte >= 128 is a hole pixel) -> labels int32 [Hs, Ws]: -1 off the hole, else the smallest linear index
+    y * Ws + x of the pixel's connected component (connectivity 8: diagonal neighbours join; or 4).  Unique, whatever the order of the
+    kernel's atomics."""
+    Hs, Ws = _plane_args("mask_components mask", mask, torch.uint8)
+    if connectivity not in (4, 8):
+        raise _l.PbeError(f"mask_components: connectivity must be 8 or 4, got {connectivity!r}")
+    y = _plane_out("mask_components", out, (Hs, Ws), torch.int32, mask.device)
+    lib = _l.load()
+    ws = _holes_ws(mask.device, lib.pbe_mask_components_workspace_bytes(Hs, Ws))
+    _l.check(lib.pbe_mask_components_u8_i32(_p(mask), _p(y), Hs, Ws, int(connectivity), _p(ws), ws.numel(), _stream()), "pbe_mask_components_u8_i32")
+    return y
+
+
+def component_boxes(labels: torch.Tensor, capacity: int = 4096):
+    """labels int32 [Hs, Ws] of mask_components -> (count, table): table an int64 numpy [count, 6] array of (label, ya, yb, xa, xb, area)
+    per component, bounds inclusive, SORTED BY LABEL (the raster order of each component's first pixel).  The one read-back of the
+    per-hole path: 4 + 24 capacity bytes, not the mask.  More than `capacity` components raise PbeError."""
+    import numpy as np
+    Hs, Ws = _plane_args("component_boxes labels", labels, torch.int32)
+    cap = int(capacity)
+    if cap != capacity or cap < 1 or cap > (1 << 20):
+        raise _l.PbeError(f"component_boxes: capacity must be an integer in 1 .. {1 << 20}, got {capacity!r}")
+    lib = _l.load()
+    ws = _holes_ws(labels.device, lib.pbe_component_boxes_workspace_bytes(Hs, Ws, cap))
+    buf = torch.empty(6 * cap + 1, dtype=torch.int32, device=labels.device)                 # the table, then the count
+    _l.check(lib.pbe_component_boxes_i32(_p(labels), _p(buf), buf.data_ptr() + 24 * cap, Hs, Ws, cap, _p(ws), ws.numel(), _stream()),
+             "pbe_component_boxes_i32")
+    count = int(buf[6 * cap:].cpu()[0])
+    if count > cap:
+        raise _l.PbeError(f"component_boxes: the mask has {count} components, more than capacity = {cap}: raise the `capacity` argument")
+    table = buf[:6 * count].cpu().numpy().astype(np.int64).reshape(count, 6)
+    return count, table[np.argsort(table[:, 0], kind="stable")]
+
+
+def select_components(labels: torch.Tensor, wanted, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """labels int32 [Hs, Ws], wanted: up to 4096 labels (any order, on the host or the device) -> uint8 [Hs, Ws]: 255 where the pixel's
+    label is one of them, else 0 - the mask of those holes alone."""
+    Hs, Ws = _plane_args("select_components labels", labels, torch.int32)
+    w = torch.as_tensor(wanted).reshape(-1)
+    if w.numel() and (w.is_floating_point() or w.dtype == torch.bool):
+        raise _l.PbeError(f"select_components: wanted must hold integer labels, got {w.dtype}")
+    if w.numel() > 4096:
+        raise _l.PbeError(f"select_components: {w.numel()} labels wanted, at most 4096 allowed")
+    w = torch.sort(w.to(torch.int32)).values.to(labels.device).contiguous()
+    y = _plane_out("select_components", out, (Hs, Ws), torch.uint8, labels.device)
+    _l.check(_l.load().pbe_select_components_u8(_p(labels), _p(w) if w.numel() else None, w.numel(), _p(y), Hs, Ws, _stream()), "pbe_select_components_u8")
+    return y
+
+
 def bcast_row(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, B: int, y_bs: int) -> None:
     """out[bi * y_bs + c] = a[c] + b[c] for bi < B."""
     _h(a, "bcast_row a"); _h(b, "bcast_row b"); _h(out, "bcast_row out")

@@ -169,6 +169,73 @@ def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torc
     return out
 
 
+PER_WINDOW_KWARGS = ("x_T", "post_eps", "ref_weights", "ref_regions")       # the arguments of inpaint with a leading batch dimension
+
+
+@torch.no_grad()
+def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], ref: torch.Tensor, *, size=(512, 512), context=0.5,
+                  feather: int = 8, connectivity: int = 8, max_holes: int = 16, batch: Optional[int] = None, **inpaint_kwargs) -> Dict[str, object]:
+    """Inpaint every hole of a picture in a window of its own and paste them all back into one picture.  pictures / masks: as in
+    inpaint_window (B samples).  Per sample the mask is labelled on the device (ops.mask_components at `connectivity`), the component
+    boxes come back in one small read (ops.component_boxes) and pbe_amd.window.plan_holes groups the components whose blend zones could
+    touch and plans one window per group: N windows over the B samples, ordered by sample, then by the raster order of each group's
+    first pixel.  More than `max_holes` groups in a sample, or a mask without a hole, raise PbeError.
+
+    DECISION: window g is built from g's OWN mask, ops.select_components of g's labels - both what the model sees (ops.window_mask) and
+    the blend (ops.feather_alpha).  Another group's hole that falls into g's window shows its original pixels there and is not blended
+    by g: each hole is edited as if it were the only one.  Groups lie farther apart than 4 feather + 2, so their alpha supports are
+    disjoint and the order of pasting does not matter.
+
+    ref: [B, ...] (each sample's exemplars serve all its holes) or [N, ...] (one per window); where B == N that is the same thing.  The
+    per-window arguments of inpaint (x_T, post_eps, ref_weights, ref_regions) have leading size N.  The windows go through the unchanged
+    `inpaint` in chunks of at most `batch` (default: all N at once); everything else in **inpaint_kwargs passes as it is.
+    Returns inpaint's tensors concatenated over the chunks, plus 'pictures' (per sample a uint8 [Hs, Ws, 3] clone with every hole pasted),
+    'holes' (per window a dict: 'sample', 'labels', 'box' (ya, yb, xa, xb), 'window' (y0, x0, wh, ww), 'area' in pixels), 'alphas' (per
+    window fp32 [wh, ww]) and 'inputs' (window_inputs over the N windows)."""
+    from . import window as _w
+    B = len(pictures)
+    if B == 0 or len(masks) != B:
+        raise PbeError(f"inpaint_holes: {B} pictures, {len(masks)} masks")
+    for i, (p, m) in enumerate(zip(pictures, masks)):
+        if not isinstance(p, torch.Tensor) or not isinstance(m, torch.Tensor) or p.dim() != 3 or m.dim() != 2 or tuple(p.shape[:2]) != tuple(m.shape):
+            raise PbeError(f"inpaint_holes: sample {i} needs a uint8 [Hs, Ws, 3] picture and a uint8 [Hs, Ws] mask of one size")
+    holes, own_masks = [], []
+    for i in range(B):
+        labels = ops.mask_components(masks[i], connectivity)
+        _, table = ops.component_boxes(labels)
+        area = {int(row[0]): int(row[5]) for row in table}
+        for ls, box, win in _w.plan_holes(table, masks[i].shape, size, context, feather, max_holes):
+            holes.append({"sample": i, "labels": ls, "box": box, "window": win, "area": sum(area[l] for l in ls)})
+            own_masks.append(ops.select_components(labels, ls))
+    N = len(holes)
+    lead = int(ref.shape[0])
+    if lead == B:
+        ref = ref if N == B and all(h["sample"] == k for k, h in enumerate(holes)) else ref[[h["sample"] for h in holes]]
+    elif lead != N:
+        raise PbeError(f"inpaint_holes: ref has leading size {lead}; expected {B} (one per sample) or {N} (one per hole)")
+    for k in PER_WINDOW_KWARGS:
+        v = inpaint_kwargs.get(k)
+        if v is not None and len(v) != N:
+            raise PbeError(f"inpaint_holes: {k} has leading size {len(v)}, expected {N} (one per hole)")
+    step = N if batch is None else int(batch)
+    if step < 1:
+        raise PbeError(f"inpaint_holes: batch {batch!r} must be a positive integer")
+    wins = [h["window"] for h in holes]
+    inputs = window_inputs([pictures[h["sample"]] for h in holes], own_masks, wins, size)
+    chunks = []
+    for a in range(0, N, step):
+        kw = {k: (v[a:a + step] if k in PER_WINDOW_KWARGS and v is not None else v) for k, v in inpaint_kwargs.items()}
+        chunks.append(inpaint(model, inputs["image"][a:a + step], inputs["mask"][a:a + step], ref[a:a + step], **kw))
+    out: Dict[str, object] = {k: (torch.cat([c[k] for c in chunks]) if len(chunks) > 1 else chunks[0][k]) for k in chunks[0]}
+    alphas = [ops.feather_alpha(own_masks[n], wins[n], feather) for n in range(N)]
+    result = out["image"].float().contiguous()
+    pasted = [p.clone() for p in pictures]
+    for n, h in enumerate(holes):
+        ops.paste_window(result[n], alphas[n], pasted[h["sample"]], wins[n])
+    out["pictures"], out["holes"], out["alphas"], out["inputs"] = pasted, holes, alphas, inputs
+    return out
+
+
 def ref_maps_u8(ref_maps: torch.Tensor, size, antialias: bool = True) -> torch.Tensor:
     """Attribution maps fp32 [B, K, h, w] in [0, 1] -> uint8 [B, K, H, W] at the picture size `size` = (H, W): resized on the device
     (pbe_resize_bilinear_f32, as the mask is) and quantised as round(255 * map).  What --save_reference_maps writes, one PNG per plane."""

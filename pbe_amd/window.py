@@ -1,6 +1,7 @@
 """Window planning for inpainting a region of a picture of any size (pipeline.inpaint_window): which rectangle of the picture goes
 through the model.  Host side, integers only - the pixels are handled by the kernels of csrc/window.hip (ops.window_image,
-ops.window_mask, ops.feather_alpha, ops.paste_window)."""
+ops.window_mask, ops.feather_alpha, ops.paste_window).  For one window per hole (pipeline.inpaint_holes) the planner below turns the
+component table of ops.component_boxes (csrc/holes.hip) into groups with disjoint blend zones and one window per group."""
 from __future__ import annotations
 
 from fractions import Fraction
@@ -75,7 +76,20 @@ def plan_window(mask_u8, working: Sequence[int], context=0.5, feather: int = 8, 
     r = int(feather)
     if H < 1 or W < 1 or r != feather or r < 0 or not (context >= 0) or context == float("inf"):
         raise PbeError(f"plan_window: working size {tuple(working)!r} must be positive, feather {feather!r} an integer >= 0, context {context!r} finite and >= 0")
-    ya, yb, xa, xb = hole_box(m8)
+    return plan_window_box(hole_box(m8), (Hs, Ws), working, context, feather)
+
+
+def plan_window_box(box: Sequence[int], picture_hw: Sequence[int], working: Sequence[int], context=0.5, feather: int = 8) -> Window:
+    """plan_window's arithmetic from the hole's bounding box (ya, yb, xa, xb), inclusive, in a picture of picture_hw = (Hs, Ws): what
+    plan_window returns for a mask with that box.  plan_holes calls it once per group of holes."""
+    Hs, Ws = int(picture_hw[0]), int(picture_hw[1])
+    H, W = int(working[0]), int(working[1])
+    r = int(feather)
+    if H < 1 or W < 1 or r != feather or r < 0 or not (context >= 0) or context == float("inf"):
+        raise PbeError(f"plan_window: working size {tuple(working)!r} must be positive, feather {feather!r} an integer >= 0, context {context!r} finite and >= 0")
+    ya, yb, xa, xb = (int(v) for v in box)
+    if not (0 <= ya <= yb < Hs and 0 <= xa <= xb < Ws):
+        raise PbeError(f"plan_window: box (ya, yb, xa, xb) = {tuple(box)!r} is not inside the {Hs} x {Ws} picture")
     bh, bw, m, ctx = yb - ya + 1, xb - xa + 1, 2 * r + 1, Fraction(context)
     need_h = bh + 2 * max(m, int(-((-ctx * bh) // 1)))
     need_w = bw + 2 * max(m, int(-((-ctx * bw) // 1)))
@@ -87,3 +101,57 @@ def plan_window(mask_u8, working: Sequence[int], context=0.5, feather: int = 8, 
     y0 = min(max((ya + yb + 1 - wh) // 2, 0), Hs - wh)
     x0 = min(max((xa + xb + 1 - ww) // 2, 0), Ws - ww)
     return y0, x0, wh, ww
+
+
+# ---- one window per hole (pipeline.inpaint_holes): the component table of ops.component_boxes -> groups -> windows ----------------------
+def _box_gap(a, b) -> int:
+    """Chebyshev distance of two inclusive boxes (ya, yb, xa, xb): per axis the index gap where they do not overlap, the larger of the two."""
+    return max(a[0] - b[1], b[0] - a[1], a[2] - b[3], b[2] - a[3], 0)
+
+
+def group_components(table, feather: int = 8):
+    """Components whose blend zones could touch, grouped.  table: rows (label, ya, yb, xa, xb, area) of ops.component_boxes, any order.
+    With r = feather and m = 2r + 1: one group per component, then any two groups whose bounding boxes have Chebyshev distance <= 2m are
+    merged (box = the union), to the fixed point.  Merging only ever grows boxes, so a pair that may merge stays mergeable and every order
+    of merges ends in the same partition: the finest one whose boxes lie pairwise farther apart than 2m.
+    Why 2m: ops.feather_alpha is positive only within Chebyshev distance 2r of its hole.  Pixels of two groups are at least as far apart
+    as their boxes, > 4r + 2, so no pixel lies within 2r of both: the alpha supports are disjoint, pasting is independent of order and no
+    pixel is blended twice.
+    Returns a list of (labels, box, area): labels a sorted tuple, box (ya, yb, xa, xb), ordered by the smallest label (the raster order of
+    each group's first pixel)."""
+    r = int(feather)
+    if r != feather or r < 0:
+        raise PbeError(f"group_components: feather {feather!r} must be an integer >= 0")
+    rows = np.asarray(table, dtype=np.int64).reshape(-1, 6)
+    if len(set(rows[:, 0].tolist())) != rows.shape[0]:
+        raise PbeError("group_components: the table names a label twice")
+    limit = 2 * (2 * r + 1)
+    groups = [([int(l)], (int(ya), int(yb), int(xa), int(xb)), int(a)) for l, ya, yb, xa, xb, a in sorted(rows.tolist())]
+    merged = True
+    while merged:
+        merged = False
+        for i in range(len(groups)):
+            j = i + 1
+            while j < len(groups):
+                (la, ba, aa), (lb, bb, ab) = groups[i], groups[j]
+                if _box_gap(ba, bb) <= limit:
+                    groups[i] = (la + lb, (min(ba[0], bb[0]), max(ba[1], bb[1]), min(ba[2], bb[2]), max(ba[3], bb[3])), aa + ab)
+                    del groups[j]
+                    merged, j = True, i + 1                # the grown box may now reach groups it passed
+                else:
+                    j += 1
+    out = [(tuple(sorted(ls)), box, area) for ls, box, area in groups]
+    return sorted(out, key=lambda g: g[0][0])
+
+
+def plan_holes(table, picture_hw: Sequence[int], working: Sequence[int], context=0.5, feather: int = 8, max_holes: int = 16):
+    """One window per group of holes: [(labels, box, window)] in group_components' order, window = plan_window_box(box, ...).  No component
+    is dropped: more than `max_holes` groups raise PbeError, and so does an empty table (the error of hole_box)."""
+    rows = np.asarray(table, dtype=np.int64).reshape(-1, 6)
+    if rows.shape[0] == 0:
+        raise PbeError("plan_window: the mask has no hole (no byte >= 128): nothing to inpaint")
+    groups = group_components(rows, feather)
+    if len(groups) > int(max_holes):
+        raise PbeError(f"plan_holes: the mask has {len(groups)} separate holes, more than max_holes = {int(max_holes)}: raise max_holes, or use "
+                       "inpaint_window, which treats them as one hole")
+    return [(labels, box, plan_window_box(box, picture_hw, working, context, feather)) for labels, box, _ in groups]

@@ -24,6 +24,12 @@ hole's box plus `--context` of its size and the feather's width on each side, at
 and `grid/` show that window as before, and `pasted/<stem>_<seed>.png` is the whole picture with the result blended in under a mask
 feathered over `--feather` pixels (default 8): every pixel farther than 2 x feather from the hole keeps its bytes.  `--reference_region`
 images are then picture-sized and cropped to the window; the attribution maps stay on the window.
+`--per_hole` (with `--paste_back`; not in the reference) gives every hole of the mask a window of its own (pipeline.inpaint_holes: the
+mask's connected components, grouped where their blend zones could touch; each window sees its own hole alone) and
+`pasted/<stem>_<seed>.png` holds all of them; `source/`, `results/` and `grid/` get one set of files per hole, named
+`<stem>_hole<i>_<seed>...`, holes in raster order of their first pixel.  With `--reference_per_hole` the i-th `--reference_path` is the
+exemplar of the i-th hole (as many paths as holes); without it every hole gets all of them.  The start code (with `--fixed_code`) and the
+posterior noise of the windows come from generators seeded with `--seed`, so a run is reproducible from its arguments.
 
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
@@ -78,6 +84,11 @@ def parse(argv=None):
                    "window around the hole at --H x --W and write the whole picture, the result blended in, to <outdir>/pasted/")
     p.add_argument("--context", type=float, default=0.5, help="with --paste_back: the window holds the hole's box plus this fraction of its size on each side")
     p.add_argument("--feather", type=int, default=8, help="with --paste_back: the blend mask falls off over 2 x this many picture pixels around the hole")
+    p.add_argument("--per_hole", action="store_true", help="with --paste_back: every hole of the mask (connected components, grouped where their "
+                   "blend zones could touch) gets a window of its own; pasted/ holds all of them")
+    p.add_argument("--reference_per_hole", action="store_true", help="with --per_hole: the i-th --reference_path is the exemplar of the i-th hole, "
+                   "holes in raster order of their first pixel")
+    p.add_argument("--max_holes", type=int, default=16, help="with --per_hole: more separate holes than this is an error")
     p.add_argument("--random_weights", action="store_true", help="name-seeded random weights instead of --ckpt")
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
@@ -94,6 +105,19 @@ def parse(argv=None):
             p.error("--reference_weight: weights must be finite and >= 0 with a positive sum")
     if not (opt.context >= 0.0) or opt.context == float("inf") or opt.feather < 0 or opt.feather > 2047:
         p.error("--context must be finite and >= 0, --feather an integer in 0 .. 2047")
+    if opt.per_hole:
+        if not opt.paste_back:
+            raise SystemExit("--per_hole needs --paste_back: the holes are pasted back into the one picture")
+        if opt.n_samples != 1:
+            raise SystemExit(f"--per_hole runs one sample per hole: --n_samples {opt.n_samples} is not 1")
+        if opt.dump_tensors:
+            raise SystemExit("--per_hole does not write --dump_tensors (the dump describes one window)")
+        if opt.reference_region is not None or opt.save_reference_maps or opt.ddim_eta != 0.0:
+            raise SystemExit("--per_hole is not built for --reference_region, --save_reference_maps or a --ddim_eta other than 0")
+        if opt.reference_per_hole and opt.reference_weight is not None:
+            raise SystemExit("--reference_per_hole gives each hole one exemplar: --reference_weight has nothing to weigh")
+    elif opt.reference_per_hole:
+        raise SystemExit("--reference_per_hole needs --per_hole")
     if opt.reference_region is not None:
         refs = opt.reference_path if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
         if len(opt.reference_region) != len(refs):
@@ -138,6 +162,48 @@ def save_reference_maps(outdir, stem, seed, ref_maps, H, W):
     return paths
 
 
+def run_per_hole(opt, model, device, refs):
+    """--paste_back --per_hole: pipeline.inpaint_holes on the picture, one set of source / results / grid files per hole and the picture
+    with every hole pasted.  Returns the windows' results [N, 3, H, W] on the host."""
+    from PIL import Image
+    from pbe_amd import ops, pipeline, preprocess
+    from pbe_amd import window as pbe_window
+    u8 = preprocess.load_triple_u8(opt.image_path, opt.mask_path, refs[0])
+    if u8["image"].shape[:2] != u8["mask"].shape:
+        raise SystemExit(f"--paste_back: the image is {u8['image'].shape[:2]}, the mask {u8['mask'].shape}")
+    picture, picture_mask = torch.from_numpy(u8["image"]).to(device), torch.from_numpy(u8["mask"]).to(device)
+    size = (opt.H, opt.W)
+    _, table = ops.component_boxes(ops.mask_components(picture_mask))
+    N = len(pbe_window.plan_holes(table, picture_mask.shape, size, opt.context, opt.feather, opt.max_holes))
+    if opt.reference_per_hole and len(refs) != N:
+        raise SystemExit(f"--reference_per_hole: {len(refs)} --reference_path images for {N} holes")
+    planes = [preprocess.load_triple_device(opt.image_path, opt.mask_path, r, device)["ref"][0] for r in refs]        # each [3, 224, 224]
+    kw = {}
+    if opt.reference_per_hole:
+        ref = torch.stack(planes)                                                      # [N, 3, 224, 224]: exemplar i for hole i
+    else:
+        ref = torch.stack(planes)[None] if len(planes) > 1 else planes[0][None]        # the sample's exemplars, for every hole
+        if opt.reference_weight is not None:
+            kw["ref_weights"] = torch.tensor([opt.reference_weight], dtype=torch.float64).expand(N, -1).contiguous()
+    shape = (N, opt.C, opt.H // opt.f, opt.W // opt.f)
+    if opt.fixed_code:
+        kw["x_T"] = torch.randn(shape, device=device, generator=torch.Generator(device=device).manual_seed(opt.seed))
+    kw["post_eps"] = torch.randn(shape, generator=torch.Generator().manual_seed(opt.seed)).to(device)
+    out = pipeline.inpaint_holes(model, [picture], [picture_mask], ref, size=size, context=opt.context, feather=opt.feather, max_holes=opt.max_holes,
+                                 steps=opt.ddim_steps, scale=opt.scale, sampler="dpm" if opt.dpm_solver else ("plms" if opt.plms else "ddim"), **kw)
+    stem = os.path.basename(opt.image_path)[:-4]
+    if not opt.skip_save:
+        for i in range(N):
+            t = {k: out["inputs"][k][i:i + 1] for k in ("image", "mask", "inpaint")}
+            t["ref"] = (ref[i] if opt.reference_per_hole else planes[0])[None]
+            preprocess.save_outputs_device(opt.outdir, f"{stem}_hole{i}", opt.seed, t, out["image"][i], opt.H, opt.W)
+    os.makedirs(os.path.join(opt.outdir, "pasted"), exist_ok=True)
+    Image.fromarray(out["pictures"][0].cpu().numpy()).save(os.path.join(opt.outdir, "pasted", f"{stem}_{opt.seed}.png"))
+    for i, h in enumerate(out["holes"]):
+        print(f"hole {i}: {h['area']} pixels in rows {h['box'][0]} .. {h['box'][1]}, columns {h['box'][2]} .. {h['box'][3]}; window {h['window']}")
+    return out["image"].cpu()
+
+
 def seed_everything(seed):
     import random
     import numpy as np
@@ -180,6 +246,10 @@ def main(argv=None):
 
     with torch.no_grad(), model.ema_scope():
         refs = list(opt.reference_path) if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
+        if opt.per_hole:                                                               # one window per hole: its own path, the rest is unchanged
+            x = run_per_hole(opt, model, device, refs)
+            print(f"Your samples are ready and waiting for you here: \n{opt.outdir} \n \nEnjoy.")
+            return x
         win = None
         if opt.paste_back:                                                             # a picture of any size: one window of it at H x W
             from pbe_amd import window as pbe_window
