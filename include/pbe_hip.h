@@ -556,6 +556,29 @@ int pbe_component_boxes_i32(const int32_t* labels, int32_t* table, int32_t* coun
 int pbe_select_components_u8(const int32_t* labels, const int32_t* wanted, int32_t n_wanted, void* out_mask, int32_t Hs, int32_t Ws,
                              pbe_stream_t stream);
 
+/* The shape of a mask (pbe_amd/csrc/maskshape.hip; not in the reference): the exact squared Euclidean distance map of a mask and what
+ * grows, shrinks, closes, opens and boxes a hole with it (pbe_amd.ops.mask_grow ..., pbe_amd.window.shape_mask).  mask: u8 [Hs, Ws]
+ * contiguous, a byte >= 128 is a hole pixel; edges up to 16384.  Integers only, no atomics: every output is unique and compared by
+ * equality.  Caller-owned buffers, an explicit stream.
+ * pbe_mask_dist2_u8_i32      d2[y, x] = min(min over (y', x') in S of (y - y')^2 + (x - x')^2, rmax^2 + 1), i32 [Hs, Ws]; S = the hole pixels
+ *                            (to_hole = 1) or the non-hole pixels (to_hole = 0) INSIDE the picture - the outside is neither, so a hole that
+ *                            touches the border is not eroded from that side; an empty S gives rmax^2 + 1 everywhere.  0 <= rmax <= 2047.
+ *                            The true Euclidean minimum at any size, no chamfer: a column pass (rows since the last pixel of S, down and up,
+ *                            saturated at rmax + 1, 16 bits per pixel in `workspace`) and a row pass (per pixel the taps dx = 0, +-1, ...
+ *                            of dx^2 + g^2 from LDS until dx^2 >= the best so far).  `workspace`: 2-byte aligned, at least
+ *                            pbe_mask_dist2_workspace_bytes(Hs, Ws) bytes (0 for edges out of range).  No synchronisation.
+ * pbe_mask_from_dist2_u8     out_mask[y, x] = 255 where d2 <= t2 (above = 0) or where d2 > t2 (above = 1), else 0; t2 >= 0; every byte written.
+ *                            Growing a hole by a disc of radius r is d2(to_hole = 1) <= floor(r^2), shrinking it d2(to_hole = 0) > floor(r^2).
+ * pbe_fill_boxes_u8          boxes: device i32 [n, 4], rows (ya, yb, xa, xb) inclusive, 0 <= n <= 4096 -> out_mask = 255 inside any box, else
+ *                            0; every byte written, n = 0 gives zeros.  A row that is not a box inside the picture (ya > yb, xa > xb, a
+ *                            bound outside) is refused before anything is launched: for that the rows are read back on `stream` (at most
+ *                            64 KiB), so THIS entry point waits for the stream and cannot be captured into a graph. */
+size_t pbe_mask_dist2_workspace_bytes(int32_t Hs, int32_t Ws);
+int pbe_mask_dist2_u8_i32(const void* mask, int32_t* d2, int32_t Hs, int32_t Ws, int32_t to_hole, int32_t rmax, void* workspace,
+                          size_t workspace_bytes, pbe_stream_t stream);
+int pbe_mask_from_dist2_u8(const int32_t* d2, void* out_mask, int32_t Hs, int32_t Ws, int32_t t2, int32_t above, pbe_stream_t stream);
+int pbe_fill_boxes_u8(const int32_t* boxes, int32_t n, void* out_mask, int32_t Hs, int32_t Ws, pbe_stream_t stream);
+
 /* pbe_tune— developer knobs for A/B runs in one process (never needed for correctness):
  * key 1: force an implicit-GEMM tile config index (-1 = heuristic); key 2: allow split-K (0/1);
  * key 3: attention queries-per-wave factor (0 = heuristic, 1, 2); key 4: ping-pong main loop of the halo-resident conv tiles (0/1);

@@ -126,6 +126,10 @@ SYMBOLS = {
     "pbe_component_boxes_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "pbe_component_boxes_i32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "pbe_select_components_u8": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp]),
+    "pbe_mask_dist2_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "pbe_mask_dist2_u8_i32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "pbe_mask_from_dist2_u8": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "pbe_fill_boxes_u8": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp]),
     "pbe_tune": (c_i32, [c_i32, c_i32]),
     "pbe_prof_enable": (c_i32, [c_i32]),
     "pbe_prof_reset": (c_i32, []),
@@ -137,7 +141,7 @@ _lib = None
 _lock = threading.Lock()
 
 SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_astat.hip", "attention.hip", "attention_mx8.hip", "ctx_attention.hip", "norm.hip",
-           "elementwise.hip", "window.hip", "holes.hip"]
+           "elementwise.hip", "window.hip", "holes.hip", "maskshape.hip"]
 HASHED = [os.path.join("csrc", f) for f in SOURCES] + [os.path.join("csrc", "common.h"), os.path.join("csrc", "igemm_kernel.h"), os.path.join("..", "include", "pbe_hip.h"), "build.py"]
 
 

@@ -1342,6 +1342,127 @@ def select_components(labels: torch.Tensor, wanted, out: Optional[torch.Tensor] 
     return y
 
 
+# ---- the shape of a mask (csrc/maskshape.hip): the exact squared Euclidean distance map, grow / shrink / close / open by a disc, boxes ----
+MASK_RMAX = 2047
+
+
+def _maskshape_ws(device, need: int, what: str = "maskshape") -> torch.Tensor:
+    key = (device.index, what)
+    ws = _ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=device)
+        _ws[key] = ws
+    return ws
+
+
+def _radius(what: str, r, signed: bool):
+    """r as an exact rational, or PbeError unless it is a finite real in -2047 .. 2047 (signed) or 0 .. 2047."""
+    import numbers
+    from fractions import Fraction
+    lo = -MASK_RMAX if signed else 0
+    try:
+        if isinstance(r, bool) or not isinstance(r, numbers.Real):
+            raise TypeError(type(r))
+        # the exact value of a float (numpy's scalars go through Python's); nan and inf raise
+        f = r if isinstance(r, Fraction) else Fraction(int(r) if isinstance(r, numbers.Integral) else float(r))
+    except (TypeError, ValueError, OverflowError) as e:
+        raise _l.PbeError(f"{what} must be a real number in {lo} .. {MASK_RMAX}, got {r!r}") from e
+    if f < lo or f > MASK_RMAX:
+        raise _l.PbeError(f"{what} must be a real number in {lo} .. {MASK_RMAX}, got {r!r}")
+    return f
+
+
+def mask_dist2(mask: torch.Tensor, to_hole: bool = True, rmax: int = MASK_RMAX, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [Hs, Ws] mask (a byte >= 128 is a hole pixel) -> int32 [Hs, Ws]: the squared Euclidean distance to the nearest hole pixel
+    (to_hole) or the nearest non-hole pixel (not to_hole) of the picture, exact, saturated at rmax^2 + 1 (0 <= rmax <= 2047).  The
+    outside of the picture belongs to neither set; an empty set gives rmax^2 + 1 everywhere.  A pixel farther than rmax from the set
+    costs 2 rmax + 1 taps: give the rmax you need."""
+    Hs, Ws = _plane_args("mask_dist2 mask", mask, torch.uint8)
+    f = _radius("mask_dist2: rmax", rmax, False)
+    if f.denominator != 1:
+        raise _l.PbeError(f"mask_dist2: rmax must be an integer in 0 .. {MASK_RMAX}, got {rmax!r}")
+    rm = int(f)
+    y = _plane_out("mask_dist2", out, (Hs, Ws), torch.int32, mask.device)
+    lib = _l.load()
+    ws = _maskshape_ws(mask.device, lib.pbe_mask_dist2_workspace_bytes(Hs, Ws))
+    _l.check(lib.pbe_mask_dist2_u8_i32(_p(mask), _p(y), Hs, Ws, 1 if to_hole else 0, rm, _p(ws), ws.numel(), _stream()), "pbe_mask_dist2_u8_i32")
+    return y
+
+
+def mask_grow(mask: torch.Tensor, r, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [Hs, Ws] mask, r a real in -2047 .. 2047 -> uint8 [Hs, Ws] in {0, 255}: the hole grown by the disc of radius r, i.e. every
+    pixel whose squared distance to a hole pixel is <= floor(r^2) (r = 1: the 4-neighbour cross, 1.5: the 3 x 3 square, 2: the 13-pixel
+    disc); r < 0 shrinks it: the pixels whose squared distance to a non-hole pixel of the picture is > floor(r^2) - the picture's border
+    does not erode.  r = 0 is the mask binarised.  The distance map is taken with rmax = ceil(|r|)."""
+    Hs, Ws = _plane_args("mask_grow mask", mask, torch.uint8)
+    f = _radius("mask_grow: r", r, True)
+    y = _plane_out("mask_grow", out, (Hs, Ws), torch.uint8, mask.device)
+    t2, rm = int(f * f // 1), int(-((-abs(f)) // 1))                                 # floor(r^2), ceil(|r|): exact, r is a rational
+    d2 = _maskshape_ws(mask.device, 4 * Hs * Ws, "maskshape d2")[:4 * Hs * Ws].view(torch.int32).view(Hs, Ws)      # kept per device, not allocated per call
+    mask_dist2(mask, f >= 0, rm, out=d2)
+    _l.check(_l.load().pbe_mask_from_dist2_u8(_p(d2), _p(y), Hs, Ws, t2, 0 if f >= 0 else 1, _stream()), "pbe_mask_from_dist2_u8")
+    return y
+
+
+def mask_close(mask: torch.Tensor, r, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mask_grow(mask_grow(mask, r), -r), r in 0 .. 2047: gaps and pits narrower than the disc are filled, nothing is removed."""
+    f = _radius("mask_close: r", r, False)
+    Hs, Ws = _plane_args("mask_close mask", mask, torch.uint8)
+    if out is not None:
+        _plane_out("mask_close", out, (Hs, Ws), torch.uint8, mask.device)          # refused before the first stage runs
+    return mask_grow(mask_grow(mask, f), -f, out=out)
+
+
+def mask_open(mask: torch.Tensor, r, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mask_grow(mask_grow(mask, -r), r), r in 0 .. 2047: specks and spurs narrower than the disc are removed, nothing is added."""
+    f = _radius("mask_open: r", r, False)
+    Hs, Ws = _plane_args("mask_open mask", mask, torch.uint8)
+    if out is not None:
+        _plane_out("mask_open", out, (Hs, Ws), torch.uint8, mask.device)          # refused before the first stage runs
+    return mask_grow(mask_grow(mask, -f), f, out=out)
+
+
+def fill_boxes(boxes, shape, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """boxes: anything torch.as_tensor takes, integers [n, 4] with rows (ya, yb, xa, xb), bounds inclusive (component_boxes' columns
+    1 .. 4), 0 <= n <= 4096, on the host or the device; shape = (Hs, Ws) -> uint8 [Hs, Ws]: 255 inside any box, else 0.  A row that is
+    not a box inside the picture raises: rows on the host are checked here, rows on the device by the entry point alone.  BLOCKS: the
+    entry point reads the rows back to refuse a bad one before it launches, so this call waits for the current stream (once).  The
+    result lives on `out`'s device, else `device`, else the boxes' GPU, else the current one."""
+    try:
+        Hs, Ws = (int(v) for v in shape)
+        exact = len(tuple(shape)) == 2 and all(int(v) == v for v in shape)
+    except (TypeError, ValueError) as e:
+        raise _l.PbeError(f"fill_boxes: shape must be two integers (Hs, Ws), got {shape!r}") from e
+    if not exact or Hs < 1 or Ws < 1 or max(Hs, Ws) > 16384:
+        raise _l.PbeError(f"fill_boxes: shape (Hs, Ws) = {tuple(shape)!r} must have edges in 1 .. 16384")
+    b = torch.as_tensor(boxes)
+    if b.numel() and (b.is_floating_point() or b.is_complex() or b.dtype == torch.bool):
+        raise _l.PbeError(f"fill_boxes: boxes must hold integers, got {b.dtype}")
+    if (b.dim() != 2 or b.shape[1] != 4) and b.numel():
+        raise _l.PbeError(f"fill_boxes: boxes must be [n, 4] rows (ya, yb, xa, xb), got {tuple(b.shape)}")
+    n = b.numel() // 4
+    if n > 4096:
+        raise _l.PbeError(f"fill_boxes: {n} boxes, at most 4096 allowed")
+    if not b.is_cuda:                                                                # (rows on the device: the entry point's read-back is the one check)
+        host = b.detach().to(torch.int64).reshape(n, 4)
+        bad = (host[:, 0] < 0) | (host[:, 0] > host[:, 1]) | (host[:, 1] >= Hs) | (host[:, 2] < 0) | (host[:, 2] > host[:, 3]) | (host[:, 3] >= Ws)
+        if bool(bad.any()):
+            i = int(torch.nonzero(bad)[0])
+            raise _l.PbeError(f"fill_boxes: box {i} (ya, yb, xa, xb) = {tuple(host[i].tolist())} is not a box inside the {Hs} x {Ws} picture")
+    if out is not None:
+        dev = out.device
+    elif device is not None:
+        dev = torch.device(device)
+    else:
+        dev = b.device if b.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise _l.PbeError(f"fill_boxes: the result must live on a GPU, got {dev}")
+    y = _plane_out("fill_boxes", out, (Hs, Ws), torch.uint8, dev)
+    d = b.detach().reshape(n, 4).to(device=dev, dtype=torch.int64).clamp(-1, 1 << 20).to(torch.int32).contiguous()        # (the clamp: no wrap into range; both ends are refused)
+    _l.check(_l.load().pbe_fill_boxes_u8(_p(d) if n else None, n, _p(y), Hs, Ws, _stream()), "pbe_fill_boxes_u8")
+    return y
+
+
 def bcast_row(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, B: int, y_bs: int) -> None:
     """out[bi * y_bs + c] = a[c] + b[c] for bi < B."""
     _h(a, "bcast_row a"); _h(b, "bcast_row b"); _h(out, "bcast_row out")

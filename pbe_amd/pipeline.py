@@ -138,7 +138,7 @@ def window_inputs(pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor
 
 @torch.no_grad()
 def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], ref: torch.Tensor, *, size=(512, 512), context=0.5,
-                   feather: int = 8, windows: Optional[Sequence] = None, **inpaint_kwargs) -> Dict[str, object]:
+                   feather: int = 8, windows: Optional[Sequence] = None, mask_shape: Optional[dict] = None, **inpaint_kwargs) -> Dict[str, object]:
     """Inpaint a region of pictures of any size and paste it back in place.  pictures: per sample a uint8 [Hs, Ws, 3] tensor, masks: a
     uint8 [Hs, Ws] tensor of the same Hs x Ws (a byte >= 128 is the hole), both contiguous and on the model's GPU; the sizes may differ
     from sample to sample.  Per sample ONE window is planned around the hole (pbe_amd.window.plan_window with `size`, `context`,
@@ -151,14 +151,20 @@ def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torc
     Returns inpaint's dict ('image', 'latent', ... at the working size) plus 'pictures' (list of uint8 [Hs, Ws, 3]), 'windows' (list of
     (y0, x0, wh, ww)), 'alphas' (list of fp32 [wh, ww]) and 'inputs' (window_inputs: what the model saw).  ref_regions and 'ref_maps' stay
     on the WINDOW's grid: a region map describes the window at the working size, not the picture, and the attribution maps come back on
-    the window's latent grid."""
+    the window's latent grid.
+    mask_shape: a dict of pbe_amd.window.shape_mask's keywords (open, close, grow, box, connectivity).  Each mask is then shaped once, on
+    the device, and the shaped mask is THE mask from there on - planning, what the model sees, the blend - and the result gains 'masks',
+    the list of shaped uint8 masks.  None (the default) takes the masks as they are."""
     from . import window as _w
     B = len(pictures)
+    shape = None if mask_shape is None else _w.shape_args(mask_shape)
     if B == 0 or len(masks) != B or (windows is not None and len(windows) != B):
         raise PbeError(f"inpaint_window: {B} pictures, {len(masks)} masks" + ("" if windows is None else f", {len(windows)} windows"))
     for i, (p, m) in enumerate(zip(pictures, masks)):
         if not isinstance(p, torch.Tensor) or not isinstance(m, torch.Tensor) or p.dim() != 3 or m.dim() != 2 or tuple(p.shape[:2]) != tuple(m.shape):
             raise PbeError(f"inpaint_window: sample {i} needs a uint8 [Hs, Ws, 3] picture and a uint8 [Hs, Ws] mask of one size")
+    if shape is not None:
+        masks = [_w.shape_mask(m, **shape) for m in masks]
     wins = [_w.plan_window(masks[i], size, context, feather, None if windows is None else windows[i]) for i in range(B)]
     inputs = window_inputs(pictures, masks, wins, size)
     out: Dict[str, object] = dict(inpaint(model, inputs["image"], inputs["mask"], ref, **inpaint_kwargs))
@@ -166,6 +172,8 @@ def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torc
     result = out["image"].float().contiguous()
     out["pictures"] = [ops.paste_window(result[i], alphas[i], pictures[i].clone(), wins[i]) for i in range(B)]
     out["windows"], out["alphas"], out["inputs"] = wins, alphas, inputs
+    if shape is not None:
+        out["masks"] = list(masks)
     return out
 
 
@@ -174,7 +182,8 @@ PER_WINDOW_KWARGS = ("x_T", "post_eps", "ref_weights", "ref_regions")       # th
 
 @torch.no_grad()
 def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], ref: torch.Tensor, *, size=(512, 512), context=0.5,
-                  feather: int = 8, connectivity: int = 8, max_holes: int = 16, batch: Optional[int] = None, **inpaint_kwargs) -> Dict[str, object]:
+                  feather: int = 8, connectivity: int = 8, max_holes: int = 16, batch: Optional[int] = None, mask_shape: Optional[dict] = None,
+                  **inpaint_kwargs) -> Dict[str, object]:
     """Inpaint every hole of a picture in a window of its own and paste them all back into one picture.  pictures / masks: as in
     inpaint_window (B samples).  Per sample the mask is labelled on the device (ops.mask_components at `connectivity`), the component
     boxes come back in one small read (ops.component_boxes) and pbe_amd.window.plan_holes groups the components whose blend zones could
@@ -191,14 +200,19 @@ def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch
     `inpaint` in chunks of at most `batch` (default: all N at once); everything else in **inpaint_kwargs passes as it is.
     Returns inpaint's tensors concatenated over the chunks, plus 'pictures' (per sample a uint8 [Hs, Ws, 3] clone with every hole pasted),
     'holes' (per window a dict: 'sample', 'labels', 'box' (ya, yb, xa, xb), 'window' (y0, x0, wh, ww), 'area' in pixels), 'alphas' (per
-    window fp32 [wh, ww]) and 'inputs' (window_inputs over the N windows)."""
+    window fp32 [wh, ww]) and 'inputs' (window_inputs over the N windows).
+    mask_shape: as in inpaint_window - each mask is shaped once (pbe_amd.window.shape_mask) before it is labelled, the holes are those
+    of the shaped mask, and the result gains 'masks'.  `connectivity` here is the labelling's; the box stage has its own key."""
     from . import window as _w
     B = len(pictures)
+    shape = None if mask_shape is None else _w.shape_args(mask_shape)
     if B == 0 or len(masks) != B:
         raise PbeError(f"inpaint_holes: {B} pictures, {len(masks)} masks")
     for i, (p, m) in enumerate(zip(pictures, masks)):
         if not isinstance(p, torch.Tensor) or not isinstance(m, torch.Tensor) or p.dim() != 3 or m.dim() != 2 or tuple(p.shape[:2]) != tuple(m.shape):
             raise PbeError(f"inpaint_holes: sample {i} needs a uint8 [Hs, Ws, 3] picture and a uint8 [Hs, Ws] mask of one size")
+    if shape is not None:
+        masks = [_w.shape_mask(m, **shape) for m in masks]
     holes, own_masks = [], []
     for i in range(B):
         labels = ops.mask_components(masks[i], connectivity)
@@ -233,6 +247,8 @@ def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch
     for n, h in enumerate(holes):
         ops.paste_window(result[n], alphas[n], pasted[h["sample"]], wins[n])
     out["pictures"], out["holes"], out["alphas"], out["inputs"] = pasted, holes, alphas, inputs
+    if shape is not None:
+        out["masks"] = list(masks)
     return out
 
 

@@ -43,12 +43,17 @@ def load_triple_u8(image_path: str, mask_path: str, reference_path: str) -> Dict
             "ref": np.array(Image.open(reference_path).convert("RGB").resize((224, 224)), dtype=np.uint8)}
 
 
-def load_triple_device(image_path: str, mask_path: str, reference_path: str, device) -> Dict[str, torch.Tensor]:
+def load_triple_device(image_path: str, mask_path: str, reference_path: str, device, mask_shape=None) -> Dict[str, torch.Tensor]:
     """load_triple with the arithmetic of scripts/inference.py:306-319 on the GPU (pbe_u8_to_planes_f32 / pbe_mul_planes_f32):
-    the triple travels as uint8; the returned fp32 tensors live on `device` and equal load_triple()'s bit for bit."""
+    the triple travels as uint8; the returned fp32 tensors live on `device` and equal load_triple()'s bit for bit.
+    mask_shape: a dict of pbe_amd.window.shape_mask's keywords - the uint8 mask is then shaped on the device before it becomes the keep
+    plane (the same byte >= 128 rule); None takes it as it is."""
     from . import ops
     u8 = load_triple_u8(image_path, mask_path, reference_path)
     dev = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device)[None] for k, v in u8.items()}
+    if mask_shape is not None:
+        from .window import shape_args, shape_mask
+        dev["mask"] = shape_mask(dev["mask"][0], **shape_args(mask_shape))[None]
     img = ops.u8_to_planes(dev["image"], (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))
     ref = ops.u8_to_planes(dev["ref"], CLIP_MEAN, CLIP_STD)
     mask = ops.u8_to_planes(dev["mask"], mask_mode=1)

@@ -1,7 +1,8 @@
 """Window planning for inpainting a region of a picture of any size (pipeline.inpaint_window): which rectangle of the picture goes
 through the model.  Host side, integers only - the pixels are handled by the kernels of csrc/window.hip (ops.window_image,
 ops.window_mask, ops.feather_alpha, ops.paste_window).  For one window per hole (pipeline.inpaint_holes) the planner below turns the
-component table of ops.component_boxes (csrc/holes.hip) into groups with disjoint blend zones and one window per group."""
+component table of ops.component_boxes (csrc/holes.hip) into groups with disjoint blend zones and one window per group.  shape_mask
+brings a mask into the shape the model wants before anything is planned from it (csrc/maskshape.hip)."""
 from __future__ import annotations
 
 from fractions import Fraction
@@ -101,6 +102,63 @@ def plan_window_box(box: Sequence[int], picture_hw: Sequence[int], working: Sequ
     y0 = min(max((ya + yb + 1 - wh) // 2, 0), Hs - wh)
     x0 = min(max((xa + xb + 1 - ww) // 2, 0), Ws - ww)
     return y0, x0, wh, ww
+
+
+# ---- the shape of the hole (csrc/maskshape.hip): what a mask goes through before anything is planned from it ----------------------------
+SHAPE_KEYS = ("open", "close", "grow", "box", "connectivity")
+
+
+def shape_args(shape) -> dict:
+    """The keywords of shape_mask, checked and with the defaults filled in: `shape` is a dict of some of open (>= 0), close (>= 0), grow
+    (negative shrinks; all three reals up to 2047), box (a bool) and connectivity (8 or 4).  Anything else raises PbeError."""
+    import numbers
+    try:
+        kw = dict(shape)
+    except (TypeError, ValueError) as e:
+        raise PbeError(f"shape_mask: expected a dict of {SHAPE_KEYS}, got {shape!r}") from e
+    unknown = sorted(str(k) for k in kw if k not in SHAPE_KEYS)
+    if unknown:
+        raise PbeError(f"shape_mask: unknown key(s) {unknown}: the keys are {SHAPE_KEYS}")
+    out = {"open": kw.get("open", 0), "close": kw.get("close", 0), "grow": kw.get("grow", 0), "box": kw.get("box", False),
+           "connectivity": kw.get("connectivity", 8)}
+    for k in ("open", "close", "grow"):
+        v = out[k]
+        lo = -2047 if k == "grow" else 0
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not (lo <= v <= 2047):
+            raise PbeError(f"shape_mask: {k} must be a real number in {lo} .. 2047, got {v!r}")
+    if not isinstance(out["box"], (bool, np.bool_)):
+        raise PbeError(f"shape_mask: box must be True or False, got {out['box']!r}")
+    if out["connectivity"] not in (4, 8):
+        raise PbeError(f"shape_mask: connectivity must be 8 or 4, got {out['connectivity']!r}")
+    return out
+
+
+def shape_mask(mask, *, open=0, close=0, grow=0, box=False, connectivity=8):                       # noqa: A002 (the morphological names)
+    """The mask in the shape the model wants: uint8 [Hs, Ws] on the GPU (a byte >= 128 is the hole) -> a NEW uint8 [Hs, Ws] in {0, 255},
+    after, in this order and each only when it is not at its default,
+      open   ops.mask_open(., open):   specks and spurs narrower than the disc of that radius go
+      close  ops.mask_close(., close): gaps and pits narrower than the disc are filled (two fragments of one object become one hole)
+      grow   ops.mask_grow(., grow):   the hole grown by the disc of that radius, a negative one shrinks it
+      box    every component (ops.mask_components at `connectivity`, ops.component_boxes) replaced by its bounding box
+             (ops.fill_boxes); boxes that overlap simply unite, and whoever labels afterwards sees them as one hole.
+    All of it is exact integer arithmetic in Euclidean distance; the outside of the picture is neither hole nor background, so a hole
+    at the border is not eroded from there.  With every stage at its default the result is the mask binarised.  The input is never
+    modified; a result without a hole is not an error here (the planners raise for it)."""
+    from . import ops
+    a = shape_args({"open": open, "close": close, "grow": grow, "box": box, "connectivity": connectivity})
+    m, staged = mask, False
+    for stage, fn in (("open", "mask_open"), ("close", "mask_close"), ("grow", "mask_grow")):
+        if a[stage] != 0:
+            m, staged = getattr(ops, fn)(m, a[stage]), True
+    if a["box"]:
+        labels = ops.mask_components(m, a["connectivity"])
+        try:
+            _, table = ops.component_boxes(labels, capacity=4096)                                # what ops.fill_boxes takes
+        except PbeError as e:
+            raise PbeError(f"shape_mask: the box stage found more than 4096 components, more boxes than ops.fill_boxes takes ({e}): "
+                           "remove the specks first (open=...), or close the gaps (close=...)") from e
+        return ops.fill_boxes(np.asarray(table, dtype=np.int64).reshape(-1, 6)[:, 1:5], tuple(m.shape), device=m.device)
+    return m if staged else ops.mask_grow(m, 0)
 
 
 # ---- one window per hole (pipeline.inpaint_holes): the component table of ops.component_boxes -> groups -> windows ----------------------

@@ -30,6 +30,10 @@ mask's connected components, grouped where their blend zones could touch; each w
 `<stem>_hole<i>_<seed>...`, holes in raster order of their first pixel.  With `--reference_per_hole` the i-th `--reference_path` is the
 exemplar of the i-th hole (as many paths as holes); without it every hole gets all of them.  The start code (with `--fixed_code`) and the
 posterior noise of the windows come from generators seeded with `--seed`, so a run is reproducible from its arguments.
+`--mask_open PX`, `--mask_close PX`, `--mask_grow PX` and `--mask_box` (not in the reference) shape the mask on the device before anything
+else sees it (pbe_amd.window.shape_mask, in that order): open removes specks narrower than a disc of radius PX, close fills gaps narrower
+than it, grow grows the hole by that disc (a negative PX shrinks it), box replaces every hole by its bounding box.  They work with and
+without `--paste_back` / `--per_hole`; `source/<stem>_<seed>_mask.png` then shows the shaped mask.
 
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
@@ -89,6 +93,12 @@ def parse(argv=None):
     p.add_argument("--reference_per_hole", action="store_true", help="with --per_hole: the i-th --reference_path is the exemplar of the i-th hole, "
                    "holes in raster order of their first pixel")
     p.add_argument("--max_holes", type=int, default=16, help="with --per_hole: more separate holes than this is an error")
+    p.add_argument("--mask_grow", type=float, default=0.0, metavar="PX", help="(not in the reference) grow the hole by a disc of this radius in "
+                   "mask pixels before anything else sees the mask; negative shrinks it")
+    p.add_argument("--mask_close", type=float, default=0.0, metavar="PX", help="(not in the reference) fill gaps of the hole narrower than a disc of this radius")
+    p.add_argument("--mask_open", type=float, default=0.0, metavar="PX", help="(not in the reference) remove specks of the hole narrower than a disc of this radius")
+    p.add_argument("--mask_box", action="store_true", help="(not in the reference) replace every hole by its bounding box; applied after "
+                   "--mask_open, --mask_close and --mask_grow, in that order")
     p.add_argument("--random_weights", action="store_true", help="name-seeded random weights instead of --ckpt")
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
@@ -105,6 +115,8 @@ def parse(argv=None):
             p.error("--reference_weight: weights must be finite and >= 0 with a positive sum")
     if not (opt.context >= 0.0) or opt.context == float("inf") or opt.feather < 0 or opt.feather > 2047:
         p.error("--context must be finite and >= 0, --feather an integer in 0 .. 2047")
+    if not (-2047.0 <= opt.mask_grow <= 2047.0) or not (0.0 <= opt.mask_close <= 2047.0) or not (0.0 <= opt.mask_open <= 2047.0):
+        p.error("--mask_grow must lie in -2047 .. 2047, --mask_close and --mask_open in 0 .. 2047")
     if opt.per_hole:
         if not opt.paste_back:
             raise SystemExit("--per_hole needs --paste_back: the holes are pasted back into the one picture")
@@ -123,6 +135,13 @@ def parse(argv=None):
         if len(opt.reference_region) != len(refs):
             p.error(f"--reference_region: {len(opt.reference_region)} region images for {len(refs)} --reference_path images")
     return opt
+
+
+def mask_shape_of(opt):
+    """The --mask_* flags as the keywords of pbe_amd.window.shape_mask, or None when none of them is given."""
+    if opt.mask_open == 0.0 and opt.mask_close == 0.0 and opt.mask_grow == 0.0 and not opt.mask_box:
+        return None
+    return {"open": opt.mask_open, "close": opt.mask_close, "grow": opt.mask_grow, "box": bool(opt.mask_box)}
 
 
 def load_regions(paths, size, device, window=None):
@@ -172,6 +191,8 @@ def run_per_hole(opt, model, device, refs):
     if u8["image"].shape[:2] != u8["mask"].shape:
         raise SystemExit(f"--paste_back: the image is {u8['image'].shape[:2]}, the mask {u8['mask'].shape}")
     picture, picture_mask = torch.from_numpy(u8["image"]).to(device), torch.from_numpy(u8["mask"]).to(device)
+    if mask_shape_of(opt) is not None:                                                 # shaped once, here: inpaint_holes gets the shaped mask
+        picture_mask = pbe_window.shape_mask(picture_mask, **mask_shape_of(opt))
     size = (opt.H, opt.W)
     _, table = ops.component_boxes(ops.mask_components(picture_mask))
     N = len(pbe_window.plan_holes(table, picture_mask.shape, size, opt.context, opt.feather, opt.max_holes))
@@ -250,18 +271,20 @@ def main(argv=None):
             x = run_per_hole(opt, model, device, refs)
             print(f"Your samples are ready and waiting for you here: \n{opt.outdir} \n \nEnjoy.")
             return x
-        win = None
+        win, mask_shape = None, mask_shape_of(opt)
         if opt.paste_back:                                                             # a picture of any size: one window of it at H x W
             from pbe_amd import window as pbe_window
             u8 = preprocess.load_triple_u8(opt.image_path, opt.mask_path, refs[0])
             if u8["image"].shape[:2] != u8["mask"].shape:
                 raise SystemExit(f"--paste_back: the image is {u8['image'].shape[:2]}, the mask {u8['mask'].shape}")
             picture, picture_mask = torch.from_numpy(u8["image"]).to(device), torch.from_numpy(u8["mask"]).to(device)
-            win = pbe_window.plan_window(u8["mask"], (opt.H, opt.W), opt.context, opt.feather)
+            if mask_shape is not None:
+                picture_mask = pbe_window.shape_mask(picture_mask, **mask_shape)
+            win = pbe_window.plan_window(u8["mask"] if mask_shape is None else picture_mask, (opt.H, opt.W), opt.context, opt.feather)
             t = pipeline.window_inputs([picture], [picture_mask], [win], (opt.H, opt.W))
             t["ref"] = ops.u8_to_planes(torch.from_numpy(u8["ref"]).to(device)[None], preprocess.CLIP_MEAN, preprocess.CLIP_STD)
         else:
-            t = preprocess.load_triple_device(opt.image_path, opt.mask_path, refs[0], device)  # uint8 up, arithmetic on the GPU
+            t = preprocess.load_triple_device(opt.image_path, opt.mask_path, refs[0], device, mask_shape=mask_shape)   # uint8 up, arithmetic on the GPU
         filename = os.path.basename(opt.image_path)
         test_model_kwargs = {"inpaint_mask": t["mask"], "inpaint_image": t["inpaint"]}
         ref = t["ref"]
