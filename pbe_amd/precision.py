@@ -17,6 +17,10 @@ set_attention_precision switches the self-attention CORE (softmax(q k^T) v of ev
         stored), so no fp16 q|k / V^T is written and no quantiser runs; the bytes are those of the quantiser path, which stays for
         other shapes (N % 64 != 0), the unfolded projection and CrossAttention.mx8_from_projection = False (A/B runs).
         Tolerances: tests/test_attention_mx8_gpu.py.  Timing: tools/attn_mx8_ab.py.
+
+Both switches, alone and together, are also held to a quantisation-aware fp64 reference (tests/q8ref.py: the same chain in exact
+arithmetic with only the operand quantisations) - per block through q8ref.verdict, one full-size forward against
+tests/golden/full_q8.npz (Q8_FWD_MEASURED) and the 50-step trajectory (Q8_TRAJ_MEASURED): tests/test_q8gate_gpu.py, DESIGN.md section 4.5.
 """
 from __future__ import annotations
 
