@@ -519,7 +519,10 @@ int pbe_planes_to_u8_canvas(const float* src, void* canvas, int32_t H, int32_t W
  *                            through `workspace`, at least pbe_feather_alpha_workspace_bytes(wh, ww, r) bytes of device scratch.
  * pbe_paste_window_u8        for every window pixel with alpha > 0 and each channel: res = AA(result, (H, W) -> (wh, ww)), o = byte / 255,
  *                            v = fmaf(alpha, res, (1 - alpha) * o), byte = rint(255 * clamp(v, 0, 1)) (half to even); result fp32 [3, H, W].
- *                            Pixels with alpha == 0 and everything outside the window are not written. */
+ *                            Pixels with alpha == 0 and everything outside the window are not written.
+ * pbe_paste_window_tone_u8   pbe_paste_window_u8 with res = fmaf(gain3[c], res, offset3[c]) per channel between the filter and the blend
+ *                            (gain3 / offset3: three floats each on the HOST, passed by value into the launch): the tone map of
+ *                            pbe_tone_stats_i64 below.  Gain 1 and offset 0 give pbe_paste_window_u8's bytes. */
 int pbe_window_image_u8_f32(const void* picture, float* dst, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
                             int32_t H, int32_t W, const float* mean3, const float* std3, pbe_stream_t stream);
 int pbe_window_mask_u8_f32(const void* mask, float* dst, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
@@ -529,6 +532,24 @@ int pbe_feather_alpha_f32(const void* mask, float* alpha, int32_t Hs, int32_t Ws
                           void* workspace, size_t workspace_bytes, pbe_stream_t stream);
 int pbe_paste_window_u8(const float* result, const float* alpha, void* picture, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh,
                         int32_t ww, int32_t H, int32_t W, pbe_stream_t stream);
+int pbe_paste_window_tone_u8(const float* result, const float* alpha, void* picture, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0,
+                             int32_t wh, int32_t ww, int32_t H, int32_t W, const float* gain3, const float* offset3, pbe_stream_t stream);
+
+/* Tone of a pasted window (pbe_amd/csrc/tone.hip; not in the reference): the sums from which pbe_amd.window.fit_tone fits one affine map
+ * per window and channel that brings the result's known pixels back onto the original's.
+ * pbe_tone_stats_i64         image fp32 [B, 3, H, W] model-normalised in [-1, 1] (pbe_window_image_u8_f32 at mean = std = 0.5), result fp32
+ *                            [B, 3, H, W] in [0, 1] (pbe_image_post_f32), sel fp32 [B, 1, H, W] -> stats int64 [B, 3, 6].  Per pixel and
+ *                            channel o = (int)rintf(255 c01(0.5 x + 0.5)) and q = (int)rintf(255 c01(r)), c01(v) = fminf(fmaxf(v, 0), 1)
+ *                            (a NaN counts as 0; half to even); a pixel counts iff sel >= 0.5f (a NaN selects nothing).  Row [b, c] is
+ *                            n, sum o, sum q, sum o^2, sum q^2, sum o q over the counted pixels of sample b; n is the same in a sample's
+ *                            three rows.  EVERY element is written (no counted pixel: six zeros): neither stats nor the workspace need
+ *                            clearing.  Integer sums only, no atomics: per-thread 32-bit accumulators, a wave and a block reduction,
+ *                            64-bit block partials in `workspace` (at least pbe_tone_stats_workspace_bytes(B, H, W) bytes of device
+ *                            scratch, 8-byte aligned) and a finalise kernel - the table does not depend on the order the blocks ran in.
+ *                            H, W <= 16384, B <= 65535. */
+size_t pbe_tone_stats_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pbe_tone_stats_i64(const float* image, const float* result, const float* sel, int64_t* stats, int32_t B, int32_t H, int32_t W,
+                       void* workspace, size_t workspace_bytes, pbe_stream_t stream);
 
 /* Holes of a mask (pbe_amd/csrc/holes.hip; not in the reference): connected components of the hole, for one window per hole
  * (pbe_amd.window.plan_holes, pipeline.inpaint_holes).  mask: u8 [Hs, Ws] contiguous, a byte >= 128 is a hole pixel; labels: i32 [Hs, Ws]

@@ -3,6 +3,7 @@
 //   pbe_window_mask_u8_f32    window of the mask    -> keep plane in {0, 1} at the working size (integer footprint rule, no filter)
 //   pbe_feather_alpha_f32     mask + window + r     -> alpha = box_r(dilate_r(hole)) / (2r+1)^2 on the window (separable integer passes)
 //   pbe_paste_window_u8       result + alpha        -> the picture's bytes, in place, where alpha > 0
+//   pbe_paste_window_tone_u8  the same with res = gain * res + offset per channel before the blend (the tone map of csrc/tone.hip's statistics)
 // One thread per output pixel (all three channels), 256 threads per block.  No per-thread arrays: filter weights are recomputed per
 // tap from integers, so any scale goes (pbe_resize_bilinear_f32 keeps 64 weights in registers and stops at scale 31).  Every fused
 // multiply-add is written as fmaf and no other product feeds a sum, so the arithmetic does not depend on -ffp-contract and
@@ -238,9 +239,13 @@ extern "C" int pbe_feather_alpha_f32(const void* mask, float* alpha, int32_t Hs,
     EW_END(s, 2.0 * n1 + 2.0 * n2 + 4.0 * n3 + 4.0 * n4, "pbe_feather_alpha_f32");
 }
 
-// ---- pbe_paste_window_u8 ---------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) paste_window_kernel(const float* result, const float* alpha, unsigned char* pic, int Ws, int y0, int x0, int wh, int ww,
-                                                           int H, int W) {
+// ---- pbe_paste_window_u8, pbe_paste_window_tone_u8 -------------------------------------------------------------------------------------
+// One body for both: with TONE the resampled result goes through res = fmaf(gain, res, offset) per channel (the affine map of
+// pbe_amd.window.fit_tone) before the blend, and nothing else differs; fmaf(1, res, 0) = res, so tone (1, 0) gives the plain paste's bytes.
+// paste_window_kernel keeps its name and its arguments: it compiles to what it compiled to before the tone entry existed.
+template <bool TONE>
+__device__ __forceinline__ void paste_window_body(const float* result, const float* alpha, unsigned char* pic, int Ws, int y0, int x0, int wh, int ww, int H, int W,
+                                                  const float (&gain)[3], const float (&offset)[3]) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;           // over wh * ww window pixels
     if (i >= (long)wh * ww) return;
     const float a = alpha[i];
@@ -249,6 +254,10 @@ __global__ void __launch_bounds__(256) paste_window_kernel(const float* result, 
     const SrcF32Planes src = {result, W, (long)H * W};
     float res[3];
     aa_resample3(src, oy, ox, H, W, wh, ww, res);
+    if (TONE) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) res[c] = fmaf(gain[c], res[c], offset[c]);
+    }
     unsigned char* d = pic + ((long)(y0 + oy) * Ws + (x0 + ox)) * 3;
     const float keep = 1.f - a;
 #pragma unroll
@@ -258,6 +267,16 @@ __global__ void __launch_bounds__(256) paste_window_kernel(const float* result, 
         v = fminf(fmaxf(v, 0.f), 1.f);
         d[c] = (unsigned char)rintf(255.0f * v);                   // round half to even
     }
+}
+__global__ void __launch_bounds__(256) paste_window_kernel(const float* result, const float* alpha, unsigned char* pic, int Ws, int y0, int x0, int wh, int ww,
+                                                           int H, int W) {
+    const float none[3] = {0.f, 0.f, 0.f};
+    paste_window_body<false>(result, alpha, pic, Ws, y0, x0, wh, ww, H, W, none, none);
+}
+__global__ void __launch_bounds__(256) paste_window_tone_kernel(const float* result, const float* alpha, unsigned char* pic, int Ws, int y0, int x0, int wh, int ww,
+                                                                int H, int W, float g0, float g1, float g2, float b0, float b1, float b2) {
+    const float gain[3] = {g0, g1, g2}, offset[3] = {b0, b1, b2};
+    paste_window_body<true>(result, alpha, pic, Ws, y0, x0, wh, ww, H, W, gain, offset);
 }
 extern "C" int pbe_paste_window_u8(const float* result, const float* alpha, void* picture, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh,
                                    int32_t ww, int32_t H, int32_t W, pbe_stream_t stream) {
@@ -270,4 +289,17 @@ extern "C" int pbe_paste_window_u8(const float* result, const float* alpha, void
     EW_BEGIN(s);
     hipLaunchKernelGGL(paste_window_kernel, EW_GRID(total), dim3(256), 0, s, result, alpha, (unsigned char*)picture, Ws, y0, x0, wh, ww, H, W);
     EW_END(s, 12.0 * (double)H * W + 10.0 * (double)total, "pbe_paste_window_u8");
+}
+extern "C" int pbe_paste_window_tone_u8(const float* result, const float* alpha, void* picture, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh,
+                                        int32_t ww, int32_t H, int32_t W, const float* gain3, const float* offset3, pbe_stream_t stream) {
+    PBE_REQUIRE(result && alpha && picture && gain3 && offset3 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "pbe_paste_window_tone_u8: bad arguments");
+    PBE_REQUIRE(Hs <= WIN_MAX_DIM && Ws <= WIN_MAX_DIM && H <= WIN_MAX_DIM && W <= WIN_MAX_DIM, "pbe_paste_window_tone_u8: an edge above %d", WIN_MAX_DIM);
+    PBE_REQUIRE(y0 >= 0 && x0 >= 0 && wh > 0 && ww > 0 && wh <= Hs - y0 && ww <= Ws - x0,
+                "pbe_paste_window_tone_u8: window (%d, %d, %d, %d) outside the %d x %d picture", y0, x0, wh, ww, Hs, Ws);
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)wh * ww;
+    EW_BEGIN(s);
+    hipLaunchKernelGGL(paste_window_tone_kernel, EW_GRID(total), dim3(256), 0, s, result, alpha, (unsigned char*)picture, Ws, y0, x0, wh, ww, H, W,
+                       gain3[0], gain3[1], gain3[2], offset3[0], offset3[1], offset3[2]);
+    EW_END(s, 12.0 * (double)H * W + 10.0 * (double)total, "pbe_paste_window_tone_u8");
 }

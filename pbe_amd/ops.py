@@ -1249,19 +1249,67 @@ def feather_alpha(mask: torch.Tensor, window, feather: int, out: Optional[torch.
     return y
 
 
-def paste_window(result: torch.Tensor, alpha: torch.Tensor, picture: torch.Tensor, window) -> torch.Tensor:
+def _tone_pair(tone):
+    """tone = (gain, offset), two sequences of three finite floats -> two (c_float * 3) arrays, or PbeError."""
+    import math
+    try:
+        gain, offset = tone
+        g, b = [float(v) for v in gain], [float(v) for v in offset]
+    except (TypeError, ValueError) as e:
+        raise _l.PbeError(f"paste_window: tone must be (gain, offset), two sequences of three floats, got {tone!r}") from e
+    if len(g) != 3 or len(b) != 3 or not all(math.isfinite(v) for v in g + b):
+        raise _l.PbeError(f"paste_window: tone must be (gain, offset), two sequences of three finite floats, got {tone!r}")
+    return (C.c_float * 3)(*g), (C.c_float * 3)(*b)
+
+
+def paste_window(result: torch.Tensor, alpha: torch.Tensor, picture: torch.Tensor, window, tone=None) -> torch.Tensor:
     """result fp32 [3, H, W] in [0, 1] (one image of image_post), alpha fp32 [wh, ww], window -> `picture` (uint8 [Hs, Ws, 3]) changed IN
     PLACE and returned: where alpha > 0, byte = rint(255 clamp(fma(alpha, res, (1 - alpha) byte / 255), 0, 1)) with res the antialiased
-    filter of result to (wh, ww).  Where alpha == 0 and outside the window no byte is written."""
+    filter of result to (wh, ww).  Where alpha == 0 and outside the window no byte is written.
+    tone = (gain, offset), three floats each (pbe_amd.window.fit_tone's): res = fma(gain[c], res, offset[c]) per channel before the blend
+    (pbe_paste_window_tone_u8); ((1, 1, 1), (0, 0, 0)) gives the bytes of tone=None, which launches the plain kernel as it always did."""
     Hs, Ws, y0, x0, wh, ww = _window_args("paste_window picture", picture, 3, window)
     _f(result, "paste_window result"); _f(alpha, "paste_window alpha")
     if result.dim() != 3 or result.shape[0] != 3 or not result.is_contiguous() or result.device != picture.device:
         raise _l.PbeError(f"paste_window: result must be a contiguous fp32 [3, H, W] tensor on the picture's device, got {tuple(result.shape)}")
     if tuple(alpha.shape) != (wh, ww) or not alpha.is_contiguous() or alpha.device != picture.device:
         raise _l.PbeError(f"paste_window: alpha must be a contiguous fp32 [{wh}, {ww}] tensor on the picture's device, got {tuple(alpha.shape)}")
+    if tone is not None:
+        g, b = _tone_pair(tone)
+        _l.check(_l.load().pbe_paste_window_tone_u8(_p(result), _p(alpha), _p(picture), Hs, Ws, y0, x0, wh, ww, int(result.shape[1]), int(result.shape[2]),
+                                                    g, b, _stream()), "pbe_paste_window_tone_u8")
+        return picture
     _l.check(_l.load().pbe_paste_window_u8(_p(result), _p(alpha), _p(picture), Hs, Ws, y0, x0, wh, ww, int(result.shape[1]), int(result.shape[2]),
                                            _stream()), "pbe_paste_window_u8")
     return picture
+
+
+# ---- the tone of a pasted window (csrc/tone.hip): the sums pbe_amd.window.fit_tone fits its affine map from ---------------------------
+def tone_stats(image: torch.Tensor, result: torch.Tensor, sel: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """image fp32 [B, 3, H, W] model-normalised in [-1, 1] (window_image), result fp32 [B, 3, H, W] in [0, 1] (image_post), sel fp32
+    [B, 1, H, W] -> int64 [B, 3, 6] on the device: per sample and channel n, sum o, sum q, sum o^2, sum q^2, sum o q over the pixels with
+    sel >= 0.5, o = rint(255 clamp(0.5 x + 0.5, 0, 1)) and q = rint(255 clamp(r, 0, 1)) the two pictures as bytes (a NaN value counts as
+    0, a NaN in sel selects nothing).  Integer sums: the table is exact and the same from run to run.  Every element is written."""
+    _f(image, "tone_stats image"); _f(result, "tone_stats result"); _f(sel, "tone_stats sel")
+    if image.dim() != 4 or image.shape[1] != 3 or image.numel() == 0 or max(image.shape[2:]) > 16384 or image.shape[0] > 65535:
+        raise _l.PbeError(f"tone_stats: image must be fp32 [B, 3, H, W] with B in 1 .. 65535 and edges in 1 .. 16384, got {tuple(image.shape)}")
+    B, _, H, W = (int(v) for v in image.shape)
+    if tuple(result.shape) != (B, 3, H, W) or tuple(sel.shape) != (B, 1, H, W):
+        raise _l.PbeError(f"tone_stats: result must be [{B}, 3, {H}, {W}] and sel [{B}, 1, {H}, {W}], got {tuple(result.shape)} and {tuple(sel.shape)}")
+    if not (image.is_contiguous() and result.is_contiguous() and sel.is_contiguous()):
+        raise _l.PbeError("tone_stats: image, result and sel must be contiguous")
+    if result.device != image.device or sel.device != image.device:
+        raise _l.PbeError(f"tone_stats: image, result and sel must be on one device, got {image.device}, {result.device}, {sel.device}")
+    y = _plane_out("tone_stats", out, (B, 3, 6), torch.int64, image.device)
+    lib = _l.load()
+    need = lib.pbe_tone_stats_workspace_bytes(B, H, W)
+    key = (image.device.index, "tone")
+    ws = _ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=image.device)
+        _ws[key] = ws
+    _l.check(lib.pbe_tone_stats_i64(_p(image), _p(result), _p(sel), _p(y), B, H, W, _p(ws), ws.numel(), _stream()), "pbe_tone_stats_i64")
+    return y
 
 
 # ---- holes of a mask (csrc/holes.hip): connected components, their boxes, the mask of some of them -----------------------------------

@@ -138,7 +138,8 @@ def window_inputs(pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor
 
 @torch.no_grad()
 def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], ref: torch.Tensor, *, size=(512, 512), context=0.5,
-                   feather: int = 8, windows: Optional[Sequence] = None, mask_shape: Optional[dict] = None, **inpaint_kwargs) -> Dict[str, object]:
+                   feather: int = 8, windows: Optional[Sequence] = None, mask_shape: Optional[dict] = None, tone: Optional[str] = None, tone_margin: int = 8,
+                   tone_gain_limit: float = 1.25, **inpaint_kwargs) -> Dict[str, object]:
     """Inpaint a region of pictures of any size and paste it back in place.  pictures: per sample a uint8 [Hs, Ws, 3] tensor, masks: a
     uint8 [Hs, Ws] tensor of the same Hs x Ws (a byte >= 128 is the hole), both contiguous and on the model's GPU; the sizes may differ
     from sample to sample.  Per sample ONE window is planned around the hole (pbe_amd.window.plan_window with `size`, `context`,
@@ -154,10 +155,14 @@ def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torc
     the window's latent grid.
     mask_shape: a dict of pbe_amd.window.shape_mask's keywords (open, close, grow, box, connectivity).  Each mask is then shaped once, on
     the device, and the shaped mask is THE mask from there on - planning, what the model sees, the blend - and the result gains 'masks',
-    the list of shaped uint8 masks.  None (the default) takes the masks as they are."""
+    the list of shaped uint8 masks.  None (the default) takes the masks as they are.
+    tone: "mean" or "affine" matches the pasted window's tone to the picture around the hole (match_tone below): each window is pasted
+    through its own per-channel map gain * res + offset, and the result gains 'tone' (pbe_amd.window.fit_tone's list) and 'tone_stats'
+    (the int64 [B, 3, 6] table).  'image' stays the uncorrected working-size result.  None (the default) adds no key and no launch."""
     from . import window as _w
     B = len(pictures)
     shape = None if mask_shape is None else _w.shape_args(mask_shape)
+    _check_tone("inpaint_window", tone)
     if B == 0 or len(masks) != B or (windows is not None and len(windows) != B):
         raise PbeError(f"inpaint_window: {B} pictures, {len(masks)} masks" + ("" if windows is None else f", {len(windows)} windows"))
     for i, (p, m) in enumerate(zip(pictures, masks)):
@@ -170,11 +175,40 @@ def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torc
     out: Dict[str, object] = dict(inpaint(model, inputs["image"], inputs["mask"], ref, **inpaint_kwargs))
     alphas = [ops.feather_alpha(masks[i], wins[i], feather) for i in range(B)]
     result = out["image"].float().contiguous()
-    out["pictures"] = [ops.paste_window(result[i], alphas[i], pictures[i].clone(), wins[i]) for i in range(B)]
+    maps = [{}] * B                                       # tone=None: the call it always was
+    if tone is not None:
+        out["tone"], out["tone_stats"] = match_tone(inputs["image"], result, masks, wins, size, tone, tone_margin, tone_gain_limit)
+        maps = [{"tone": (f["gain"], f["offset"])} for f in out["tone"]]
+    out["pictures"] = [ops.paste_window(result[i], alphas[i], pictures[i].clone(), wins[i], **maps[i]) for i in range(B)]
     out["windows"], out["alphas"], out["inputs"] = wins, alphas, inputs
     if shape is not None:
         out["masks"] = list(masks)
     return out
+
+
+TONE_MODES = ("mean", "affine")
+
+
+def _check_tone(what: str, tone) -> None:
+    if tone is not None and tone not in TONE_MODES:
+        raise PbeError(f"{what}: tone must be None or one of {TONE_MODES}, got {tone!r}")
+
+
+def match_tone(image: torch.Tensor, result: torch.Tensor, masks: Sequence[torch.Tensor], windows: Sequence, size, mode: str = "affine",
+               margin: int = 8, gain_limit: float = 1.25):
+    """The tone maps of a batch of windows: (pbe_amd.window.fit_tone's list, the int64 [B, 3, 6] table on the device).  image [B, 3, H, W]
+    is what the model saw (window_inputs' 'image'), result [B, 3, H, W] what it returned (inpaint's 'image'), masks[i] / windows[i] the
+    uint8 mask and the window of sample i.  sel = pbe_amd.window.tone_selection per window, stacked; ONE ops.tone_stats over the batch,
+    one host read of the table, the fit on the host.  Known pixels come back from the autoencoder with a brightness and contrast of their
+    own per channel; the map brings them back onto the original's, and the paste applies it to the whole window, hole included."""
+    from . import window as _w
+    _check_tone("match_tone", mode)
+    B, (H, W) = len(windows), (int(size[0]), int(size[1]))
+    sel = torch.empty((B, 1, H, W), dtype=torch.float32, device=image.device)
+    for i in range(B):
+        _w.tone_selection(masks[i], windows[i], (H, W), margin, out=sel[i])
+    stats = ops.tone_stats(image.contiguous(), result.contiguous(), sel)
+    return _w.fit_tone(stats.cpu(), mode, gain_limit), stats
 
 
 PER_WINDOW_KWARGS = ("x_T", "post_eps", "ref_weights", "ref_regions")       # the arguments of inpaint with a leading batch dimension
@@ -183,7 +217,7 @@ PER_WINDOW_KWARGS = ("x_T", "post_eps", "ref_weights", "ref_regions")       # th
 @torch.no_grad()
 def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], ref: torch.Tensor, *, size=(512, 512), context=0.5,
                   feather: int = 8, connectivity: int = 8, max_holes: int = 16, batch: Optional[int] = None, mask_shape: Optional[dict] = None,
-                  **inpaint_kwargs) -> Dict[str, object]:
+                  tone: Optional[str] = None, tone_margin: int = 8, tone_gain_limit: float = 1.25, **inpaint_kwargs) -> Dict[str, object]:
     """Inpaint every hole of a picture in a window of its own and paste them all back into one picture.  pictures / masks: as in
     inpaint_window (B samples).  Per sample the mask is labelled on the device (ops.mask_components at `connectivity`), the component
     boxes come back in one small read (ops.component_boxes) and pbe_amd.window.plan_holes groups the components whose blend zones could
@@ -202,10 +236,14 @@ def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch
     'holes' (per window a dict: 'sample', 'labels', 'box' (ya, yb, xa, xb), 'window' (y0, x0, wh, ww), 'area' in pixels), 'alphas' (per
     window fp32 [wh, ww]) and 'inputs' (window_inputs over the N windows).
     mask_shape: as in inpaint_window - each mask is shaped once (pbe_amd.window.shape_mask) before it is labelled, the holes are those
-    of the shaped mask, and the result gains 'masks'.  `connectivity` here is the labelling's; the box stage has its own key."""
+    of the shaped mask, and the result gains 'masks'.  `connectivity` here is the labelling's; the box stage has its own key.
+    tone: as in inpaint_window, one map per WINDOW ('tone' and 'tone_stats' have N entries / rows, concatenated over the chunks).  The
+    selection comes from each window's OWN mask, as alpha does: another group's hole inside the window was a known pixel for the model
+    and counts as one."""
     from . import window as _w
     B = len(pictures)
     shape = None if mask_shape is None else _w.shape_args(mask_shape)
+    _check_tone("inpaint_holes", tone)
     if B == 0 or len(masks) != B:
         raise PbeError(f"inpaint_holes: {B} pictures, {len(masks)} masks")
     for i, (p, m) in enumerate(zip(pictures, masks)):
@@ -244,8 +282,12 @@ def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch
     alphas = [ops.feather_alpha(own_masks[n], wins[n], feather) for n in range(N)]
     result = out["image"].float().contiguous()
     pasted = [p.clone() for p in pictures]
+    maps = [{}] * N                                       # tone=None: the call it always was
+    if tone is not None:
+        out["tone"], out["tone_stats"] = match_tone(inputs["image"], result, own_masks, wins, size, tone, tone_margin, tone_gain_limit)
+        maps = [{"tone": (f["gain"], f["offset"])} for f in out["tone"]]
     for n, h in enumerate(holes):
-        ops.paste_window(result[n], alphas[n], pasted[h["sample"]], wins[n])
+        ops.paste_window(result[n], alphas[n], pasted[h["sample"]], wins[n], **maps[n])
     out["pictures"], out["holes"], out["alphas"], out["inputs"] = pasted, holes, alphas, inputs
     if shape is not None:
         out["masks"] = list(masks)

@@ -213,3 +213,112 @@ def plan_holes(table, picture_hw: Sequence[int], working: Sequence[int], context
         raise PbeError(f"plan_holes: the mask has {len(groups)} separate holes, more than max_holes = {int(max_holes)}: raise max_holes, or use "
                        "inpaint_window, which treats them as one hole")
     return [(labels, box, plan_window_box(box, picture_hw, working, context, feather)) for labels, box, _ in groups]
+
+
+# ---- the tone of a pasted window (csrc/tone.hip): one affine map per window and channel, fitted on the known pixels ---------------------
+TONE_MODES = ("mean", "affine")
+
+
+def _f32(v) -> float:
+    return float(np.float32(v))
+
+
+def _tone_table(stats):
+    """stats as a nested list [B][3][6] of Python ints, or PbeError."""
+    if hasattr(stats, "detach"):
+        stats = stats.detach().cpu()
+    if hasattr(stats, "tolist"):
+        stats = stats.tolist()
+    try:
+        table = [[[v for v in row] for row in sample] for sample in stats]
+    except TypeError as e:
+        raise PbeError(f"fit_tone: stats must be a [B, 3, 6] table of integers, got {stats!r}") from e
+    for sample in table:
+        if len(sample) != 3 or any(len(row) != 6 for row in sample):
+            raise PbeError("fit_tone: stats must be a [B, 3, 6] table (per sample and channel n, So, Sq, Soo, Sqq, Soq)")
+        for row in sample:
+            if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in row):
+                raise PbeError(f"fit_tone: stats must hold integers, got {row!r}")
+        if len({int(row[0]) for row in sample}) != 1:
+            raise PbeError(f"fit_tone: the three rows of a sample count different numbers of pixels: {[int(row[0]) for row in sample]}")
+    return [[[int(v) for v in row] for row in sample] for sample in table]
+
+
+def fit_tone(stats, mode: str = "affine", gain_limit: float = 1.25, min_pixels: int = 64):
+    """One affine map per window and channel that brings the result's known pixels back onto the original's, from the table of
+    ops.tone_stats: stats [B, 3, 6] (a host tensor, an array or a nested list; taken as Python ints), row [b, c] = n, So, Sq, Soo, Sqq,
+    Soq, the sums over the counted pixels of o (the original's byte), q (the result's byte), their squares and their product.  Returns a
+    list, one dict per window: {"n", "gain": [3], "offset": [3], "clamped": [3], "rms_before": [3], "rms_after": [3], "identity"}.
+    Per channel, on exact integers:
+      mode "affine": g = (n Soq - So Sq) / (n Sqq - Sq^2), the least-squares slope of o on q (two integers, divided once), clamped to
+                     [1 / gain_limit, gain_limit] - `clamped` says whether that happened; a zero denominator (a flat result) gives g = 1;
+      mode "mean":   g = 1;
+      gain   = g rounded to fp32: the reported value is the applied one (ops.paste_window(tone=(gain, offset)));
+      offset = (So - gain Sq) / (255 n) rounded to fp32: the least-squares offset FOR THE GAIN APPLIED, in [0, 1] units;
+      rms_before = sqrt(sum (o - q)^2 / n), rms_after = sqrt(sum (o - gain q - 255 offset)^2 / n): grey levels over the counted pixels,
+                   both expanded from the six sums in exact rationals.
+    n < min_pixels (and n = 0 always) gives gain 1, offset 0: too little evidence changes nothing.  "identity" is True where the map
+    applied is the identity in all three channels.
+    DECISIONS (none of them is a measurement):
+      least squares on PAIRED pixels, not moment matching (gain = sd o / sd q): it minimises what the eye sees at the seam, and texture
+          noise in the result, which inflates sd q, does not inflate the gain;
+      gain_limit = 1.25 by default: an autoencoder's tone drift is a few per cent; a larger gain means that the known pixels were
+          redrawn, and that is not tone;
+      min_pixels = 64.
+    An unknown mode, gain_limit < 1 (or not finite), a table of another shape or rows of one sample with different n raise PbeError."""
+    import math
+    if mode not in TONE_MODES:
+        raise PbeError(f"fit_tone: mode must be one of {TONE_MODES}, got {mode!r}")
+    try:
+        limit = float(gain_limit)
+    except (TypeError, ValueError) as e:
+        raise PbeError(f"fit_tone: gain_limit must be a finite number >= 1, got {gain_limit!r}") from e
+    if not (limit >= 1.0) or limit == float("inf"):
+        raise PbeError(f"fit_tone: gain_limit must be a finite number >= 1, got {gain_limit!r}")
+    if isinstance(min_pixels, bool) or int(min_pixels) != min_pixels or min_pixels < 0:
+        raise PbeError(f"fit_tone: min_pixels must be an integer >= 0, got {min_pixels!r}")
+    out = []
+    for sample in _tone_table(stats):
+        n = sample[0][0]
+        fit = {"n": n, "gain": [], "offset": [], "clamped": [], "rms_before": [], "rms_after": []}
+        for _, So, Sq, Soo, Sqq, Soq in sample:
+            g, clamped = 1.0, False
+            if mode == "affine" and n > 0 and n >= min_pixels:
+                num, den = n * Soq - So * Sq, n * Sqq - Sq * Sq
+                if den != 0:
+                    g = num / den
+                    clamped = not (1.0 / limit <= g <= limit)
+                    g = min(max(g, 1.0 / limit), limit)
+            gain = _f32(g)
+            offset = 0.0
+            if n > 0 and n >= min_pixels:
+                gn, gd = gain.as_integer_ratio()
+                offset = _f32((So * gd - gn * Sq) / (255 * n * gd))
+            G, Bq = Fraction(gain), 255 * Fraction(offset)
+            before = Fraction(Soo - 2 * Soq + Sqq, max(n, 1))
+            after = (Soo + G * G * Sqq + Bq * Bq * n - 2 * G * Soq - 2 * Bq * So + 2 * G * Bq * Sq) / max(n, 1)
+            fit["gain"].append(gain); fit["offset"].append(offset); fit["clamped"].append(clamped)
+            fit["rms_before"].append(math.sqrt(before)); fit["rms_after"].append(math.sqrt(after))
+        fit["identity"] = all(g == 1.0 for g in fit["gain"]) and all(b == 0.0 for b in fit["offset"])
+        out.append(fit)
+    return out
+
+
+def tone_selection(mask, window, size, margin: int = 8, out=None):
+    """The pixels the tone is fitted on: fp32 [1, H, W] on the device, 1 on the known working pixels that lie farther from the hole than
+    `margin` WORKING pixels, else 0.  mask: uint8 [Hs, Ws] on the GPU (a byte >= 128 is the hole), window (y0, x0, wh, ww), size (H, W).
+    In picture pixels the margin is r = max(ceil(margin wh / H), ceil(margin ww / W)) (integers; r > 2047 raises PbeError), and
+      sel = ops.window_mask(ops.mask_grow(mask, r), window, size, out)     (the mask itself at r = 0): existing kernels only.
+    DECISION: the default margin is 8 working pixels, one latent cell: nearer to the hole the decoder mixes generated content into the
+    known pixels, and that is not tone."""
+    from . import ops
+    H, W = int(size[0]), int(size[1])
+    if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or margin < 0:
+        raise PbeError(f"tone_selection: margin must be an integer >= 0, got {margin!r}")
+    if H < 1 or W < 1:
+        raise PbeError(f"tone_selection: working size {tuple(size)!r} must be positive")
+    _, _, wh, ww = validate_window(window, mask.shape[:2])
+    r = max(_ceil_div(int(margin) * wh, H), _ceil_div(int(margin) * ww, W))
+    if r > 2047:
+        raise PbeError(f"tone_selection: a margin of {margin} working pixels is {r} picture pixels in window {tuple(window)}, more than 2047")
+    return ops.window_mask(ops.mask_grow(mask, r) if r > 0 else mask, window, size, out=out)

@@ -34,6 +34,12 @@ posterior noise of the windows come from generators seeded with `--seed`, so a r
 else sees it (pbe_amd.window.shape_mask, in that order): open removes specks narrower than a disc of radius PX, close fills gaps narrower
 than it, grow grows the hole by that disc (a negative PX shrinks it), box replaces every hole by its bounding box.  They work with and
 without `--paste_back` / `--per_hole`; `source/<stem>_<seed>_mask.png` then shows the shaped mask.
+`--match_tone {mean,affine}` (with `--paste_back`, with or without `--per_hole`; not in the reference) matches the pasted window's tone
+to the picture around the hole: per window and channel an offset (`mean`) or a gain and an offset (`affine`) is fitted on the known
+pixels farther than `--tone_margin PX` (default 8) working pixels from the hole, so that the result's known pixels fall back onto the
+original's, and the whole window is pasted through that map.  A line per window reports gains, offsets, the rms difference before and
+after in grey levels and the pixel count; `pasted/<stem>_<seed>.tone.json` holds the same (pbe_amd.window.fit_tone's list).  `results/`
+keeps the uncorrected window.
 
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
@@ -92,6 +98,11 @@ def parse(argv=None):
                    "blend zones could touch) gets a window of its own; pasted/ holds all of them")
     p.add_argument("--reference_per_hole", action="store_true", help="with --per_hole: the i-th --reference_path is the exemplar of the i-th hole, "
                    "holes in raster order of their first pixel")
+    p.add_argument("--match_tone", choices=("mean", "affine"), default=None, help="with --paste_back: match the pasted window's tone to the picture "
+                   "around the hole - per window and channel an offset (mean) or a gain and an offset (affine) fitted on the known pixels; "
+                   "pasted/<stem>_<seed>.tone.json holds the fit")
+    p.add_argument("--tone_margin", type=int, default=8, metavar="PX", help="with --match_tone: known pixels nearer to the hole than this many "
+                   "working pixels are left out of the fit")
     p.add_argument("--max_holes", type=int, default=16, help="with --per_hole: more separate holes than this is an error")
     p.add_argument("--mask_grow", type=float, default=0.0, metavar="PX", help="(not in the reference) grow the hole by a disc of this radius in "
                    "mask pixels before anything else sees the mask; negative shrinks it")
@@ -117,6 +128,10 @@ def parse(argv=None):
         p.error("--context must be finite and >= 0, --feather an integer in 0 .. 2047")
     if not (-2047.0 <= opt.mask_grow <= 2047.0) or not (0.0 <= opt.mask_close <= 2047.0) or not (0.0 <= opt.mask_open <= 2047.0):
         p.error("--mask_grow must lie in -2047 .. 2047, --mask_close and --mask_open in 0 .. 2047")
+    if (opt.match_tone is not None or opt.tone_margin != 8) and not opt.paste_back:
+        raise SystemExit("--match_tone / --tone_margin need --paste_back: the tone is matched where the window is pasted into the picture")
+    if opt.tone_margin < 0:
+        p.error("--tone_margin must be an integer >= 0")
     if opt.per_hole:
         if not opt.paste_back:
             raise SystemExit("--per_hole needs --paste_back: the holes are pasted back into the one picture")
@@ -181,6 +196,17 @@ def save_reference_maps(outdir, stem, seed, ref_maps, H, W):
     return paths
 
 
+def report_tone(outdir, stem, seed, fits):
+    """--match_tone: a line per window and pasted/<stem>_<seed>.tone.json with pbe_amd.window.fit_tone's list."""
+    import json
+    fmt = lambda v, spec: "(" + ", ".join(format(x, spec) for x in v) + ")"      # noqa: E731
+    for i, f in enumerate(fits):
+        print(f"tone of window {i}: gain {fmt(f['gain'], '.4f')}, offset {fmt(f['offset'], '+.4f')}, rms {fmt(f['rms_before'], '.2f')} -> "
+              f"{fmt(f['rms_after'], '.2f')} grey levels over n = {f['n']} pixels" + (" (identity)" if f["identity"] else ""))
+    with open(os.path.join(outdir, "pasted", f"{stem}_{seed}.tone.json"), "w") as fh:
+        json.dump(fits, fh, indent=1)
+
+
 def run_per_hole(opt, model, device, refs):
     """--paste_back --per_hole: pipeline.inpaint_holes on the picture, one set of source / results / grid files per hole and the picture
     with every hole pasted.  Returns the windows' results [N, 3, H, W] on the host."""
@@ -211,7 +237,8 @@ def run_per_hole(opt, model, device, refs):
         kw["x_T"] = torch.randn(shape, device=device, generator=torch.Generator(device=device).manual_seed(opt.seed))
     kw["post_eps"] = torch.randn(shape, generator=torch.Generator().manual_seed(opt.seed)).to(device)
     out = pipeline.inpaint_holes(model, [picture], [picture_mask], ref, size=size, context=opt.context, feather=opt.feather, max_holes=opt.max_holes,
-                                 steps=opt.ddim_steps, scale=opt.scale, sampler="dpm" if opt.dpm_solver else ("plms" if opt.plms else "ddim"), **kw)
+                                 steps=opt.ddim_steps, scale=opt.scale, sampler="dpm" if opt.dpm_solver else ("plms" if opt.plms else "ddim"),
+                                 **({} if opt.match_tone is None else {"tone": opt.match_tone, "tone_margin": opt.tone_margin}), **kw)
     stem = os.path.basename(opt.image_path)[:-4]
     if not opt.skip_save:
         for i in range(N):
@@ -220,6 +247,8 @@ def run_per_hole(opt, model, device, refs):
             preprocess.save_outputs_device(opt.outdir, f"{stem}_hole{i}", opt.seed, t, out["image"][i], opt.H, opt.W)
     os.makedirs(os.path.join(opt.outdir, "pasted"), exist_ok=True)
     Image.fromarray(out["pictures"][0].cpu().numpy()).save(os.path.join(opt.outdir, "pasted", f"{stem}_{opt.seed}.png"))
+    if opt.match_tone is not None:
+        report_tone(opt.outdir, stem, opt.seed, out["tone"])
     for i, h in enumerate(out["holes"]):
         print(f"hole {i}: {h['area']} pixels in rows {h['box'][0]} .. {h['box'][1]}, columns {h['box'][2]} .. {h['box'][3]}; window {h['window']}")
     return out["image"].cpu()
@@ -322,9 +351,17 @@ def main(argv=None):
             from PIL import Image
             os.makedirs(os.path.join(opt.outdir, "pasted"), exist_ok=True)
             alpha = ops.feather_alpha(picture_mask, win, opt.feather)
+            maps = [None] * xd.shape[0]
+            if opt.match_tone is not None:                                             # per saved sample against the one window the model saw
+                n = xd.shape[0]
+                fits, _ = pipeline.match_tone(t["image"].expand(n, -1, -1, -1), xd, [picture_mask] * n, [win] * n, (opt.H, opt.W), opt.match_tone,
+                                              opt.tone_margin)
+                maps = [(f["gain"], f["offset"]) for f in fits]
             for i in range(xd.shape[0]):
-                pasted = ops.paste_window(xd[i].contiguous(), alpha, picture.clone(), win)
+                pasted = ops.paste_window(xd[i].contiguous(), alpha, picture.clone(), win, tone=maps[i])
                 Image.fromarray(pasted.cpu().numpy()).save(os.path.join(opt.outdir, "pasted", f"{filename[:-4]}_{opt.seed}.png"))
+            if opt.match_tone is not None:
+                report_tone(opt.outdir, filename[:-4], opt.seed, fits)
         ref_maps = None
         if cm is not None:                                                             # (an explicit request: written with --skip_save too)
             ref_maps = cm.result(z_inpaint.shape[-2:])
