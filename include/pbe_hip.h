@@ -522,7 +522,13 @@ int pbe_planes_to_u8_canvas(const float* src, void* canvas, int32_t H, int32_t W
  *                            Pixels with alpha == 0 and everything outside the window are not written.
  * pbe_paste_window_tone_u8   pbe_paste_window_u8 with res = fmaf(gain3[c], res, offset3[c]) per channel between the filter and the blend
  *                            (gain3 / offset3: three floats each on the HOST, passed by value into the launch): the tone map of
- *                            pbe_tone_stats_i64 below.  Gain 1 and offset 0 give pbe_paste_window_u8's bytes. */
+ *                            pbe_tone_stats_i64 below.  Gain 1 and offset 0 give pbe_paste_window_u8's bytes.
+ * pbe_paste_window_field_u8  pbe_paste_window_u8 with res[c] += f_c between the filter and the blend, f_c the bilinear sample of `field`
+ *                            (fp32 [3, Hc, Wc] on the device, pbe_tone_field_f32's, Hc = ceil(H / cell), Wc = ceil(W / cell)) at the window
+ *                            pixel's centre: ty = fmaf(oy + 0.5f, sy, -0.5f) with sy = (float)((double)H / ((double)wh cell)) computed on
+ *                            the host, iy = floorf(ty), rows clamp(iy) and clamp(iy + 1) to 0 .. Hc - 1, fraction ty - iy, fmaf(t, b - a, a)
+ *                            along y and then along x (x alike).  A zero field gives pbe_paste_window_u8's bytes, a constant field b those
+ *                            of pbe_paste_window_tone_u8 at gain 1 and offset b. */
 int pbe_window_image_u8_f32(const void* picture, float* dst, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
                             int32_t H, int32_t W, const float* mean3, const float* std3, pbe_stream_t stream);
 int pbe_window_mask_u8_f32(const void* mask, float* dst, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh, int32_t ww,
@@ -547,8 +553,35 @@ int pbe_paste_window_tone_u8(const float* result, const float* alpha, void* pict
  *                            64-bit block partials in `workspace` (at least pbe_tone_stats_workspace_bytes(B, H, W) bytes of device
  *                            scratch, 8-byte aligned) and a finalise kernel - the table does not depend on the order the blocks ran in.
  *                            H, W <= 16384, B <= 65535. */
+int pbe_paste_window_field_u8(const float* result, const float* alpha, void* picture, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0,
+                              int32_t wh, int32_t ww, int32_t H, int32_t W, const float* field, int32_t Hc, int32_t Wc, int32_t cell,
+                              pbe_stream_t stream);
 size_t pbe_tone_stats_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int pbe_tone_stats_i64(const float* image, const float* result, const float* sel, int64_t* stats, int32_t B, int32_t H, int32_t W,
+                       void* workspace, size_t workspace_bytes, pbe_stream_t stream);
+
+/* A tone that varies across the window (pbe_amd/csrc/tone_field.hip; not in the reference): a low-frequency field of the difference o - q
+ * of the two bytes of pbe_tone_stats_i64, which pbe_paste_window_field_u8 adds to the pasted window.
+ * pbe_tone_cells_i32         image, result, sel as for pbe_tone_stats_i64; cell in {4, 8, 16, 32, 64} working pixels -> cells int32
+ *                            [B, 4, Hc, Wc], Hc = ceil(H / cell), Wc = ceil(W / cell): plane 0 the number n of pixels of the cell with
+ *                            sel >= 0.5f, planes 1 .. 3 sum (o - q) over them per channel; the cells of the last row and column may be
+ *                            ragged.  Integer sums (|sum| <= 255 cell^2 < 2^21), no atomics; every element is written exactly once, so
+ *                            `cells` needs no clearing.  4- / 2-wide loads where W is a multiple of 4 / 2 and the three tensors start on
+ *                            16 / 8 bytes, else scalar ones.  H, W <= 16384, B <= 65535.
+ * pbe_tone_field_f32         cells -> field fp32 [B, 3, Hc, Wc] in [0, 1] units by a pull-push fill.  PULL: level 0 is the table, level
+ *                            l + 1 has ceil(Hl / 2) x ceil(Wl / 2) cells, each the int64 sum of its up to four children, up to 1 x 1.
+ *                            MEAN at every level: m = clamp((float)((double)S / (255.0 (double)n)), -limit, +limit) where n > 0, else 0.
+ *                            PUSH: v_top = m_top; below it u = the parent field at the child's centre, separably: along y rows a = i >> 1
+ *                            and b = clamp(a + (i odd ? 1 : -1), 0, H(l+1) - 1), r = fmaf(0.25f, b - a, a), then the same along x;
+ *                            w = (float)min(n, cell^2) / (float)cell^2 and v = fmaf(w, m - u, u).  A sample whose whole-window n is 0 or
+ *                            below min_pixels gets a field of zeros.  One launch, one workgroup per sample; the pyramid lives in
+ *                            `workspace` (at least pbe_tone_field_workspace_bytes(B, Hc, Wc) bytes of device scratch, 8-byte aligned),
+ *                            which needs no clearing; every element of `field` is written.  limit finite and > 0, min_pixels >= 0,
+ *                            Hc Wc <= 2^20, B <= 65535. */
+int pbe_tone_cells_i32(const float* image, const float* result, const float* sel, int32_t* cells, int32_t B, int32_t H, int32_t W, int32_t cell,
+                       pbe_stream_t stream);
+size_t pbe_tone_field_workspace_bytes(int32_t B, int32_t Hc, int32_t Wc);
+int pbe_tone_field_f32(const int32_t* cells, float* field, int32_t B, int32_t Hc, int32_t Wc, int32_t cell, float limit, int32_t min_pixels,
                        void* workspace, size_t workspace_bytes, pbe_stream_t stream);
 
 /* Holes of a mask (pbe_amd/csrc/holes.hip; not in the reference): connected components of the hole, for one window per hole

@@ -5,6 +5,7 @@
 // Everything that is added is an integer, there are no atomics and no float sums: the table is the same whatever order the blocks ran
 // in, and tests/toneref.py restates it element for element.
 #include "common.h"
+#include "tone_bytes.h"          // tone_byte_image, tone_byte_result, ToneVec: shared with tone_field.hip
 #include "../../include/pbe_hip.h"
 
 #define EW_BEGIN(s) pbe_prof_begin(PBE_K_ELEM, s)
@@ -27,22 +28,11 @@
 //   sample, 64 bits:       the sum of q^2 reaches 2^28 * 65025 < 2^45
 static_assert(((long)WIN_MAX_DIM * WIN_MAX_DIM / ((long)TONE_MAX_BLOCKS * 256) + 3) * 65025L < (1L << 31), "a per-thread accumulator could overflow");
 
-__device__ __forceinline__ float tone_c01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }          // fmaxf(NaN, 0) = 0: a NaN counts as 0
-// the byte of a model-normalised value.  0.5f * x is exact (a power of two), so the sum is rounded once whether or not the compiler
-// contracts 0.5f * x + 0.5f into an fma: the two forms agree bit for bit, and tests/toneref.py takes the uncontracted one.
-__device__ __forceinline__ unsigned tone_byte_image(float x) { return (unsigned)(int)rintf(255.0f * tone_c01(0.5f * x + 0.5f)); }
-__device__ __forceinline__ unsigned tone_byte_result(float r) { return (unsigned)(int)rintf(255.0f * tone_c01(r)); }       // rintf: half to even
-
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, 64);
     return v;
 }
-
-template <int VEC> struct ToneVec;
-template <> struct ToneVec<1> { typedef float type; };
-template <> struct ToneVec<2> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct ToneVec<4> { typedef float type __attribute__((ext_vector_type(4))); };
 
 // grid (blocks per sample, B).  VEC pixels per load: 4 or 2 only where H * W is a multiple of it and the three tensors start on 16 / 8
 // bytes - then every plane base (b * 3 + c) * HW is aligned as well and there is no tail; any other H * W (an odd one leaves the planes

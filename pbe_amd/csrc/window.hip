@@ -4,6 +4,7 @@
 //   pbe_feather_alpha_f32     mask + window + r     -> alpha = box_r(dilate_r(hole)) / (2r+1)^2 on the window (separable integer passes)
 //   pbe_paste_window_u8       result + alpha        -> the picture's bytes, in place, where alpha > 0
 //   pbe_paste_window_tone_u8  the same with res = gain * res + offset per channel before the blend (the tone map of csrc/tone.hip's statistics)
+//   pbe_paste_window_field_u8 the same with res += the coarse difference field of csrc/tone_field.hip, sampled bilinearly
 // One thread per output pixel (all three channels), 256 threads per block.  No per-thread arrays: filter weights are recomputed per
 // tap from integers, so any scale goes (pbe_resize_bilinear_f32 keeps 64 weights in registers and stops at scale 31).  Every fused
 // multiply-add is written as fmaf and no other product feeds a sum, so the arithmetic does not depend on -ffp-contract and
@@ -239,13 +240,30 @@ extern "C" int pbe_feather_alpha_f32(const void* mask, float* alpha, int32_t Hs,
     EW_END(s, 2.0 * n1 + 2.0 * n2 + 4.0 * n3 + 4.0 * n4, "pbe_feather_alpha_f32");
 }
 
-// ---- pbe_paste_window_u8, pbe_paste_window_tone_u8 -------------------------------------------------------------------------------------
-// One body for both: with TONE the resampled result goes through res = fmaf(gain, res, offset) per channel (the affine map of
-// pbe_amd.window.fit_tone) before the blend, and nothing else differs; fmaf(1, res, 0) = res, so tone (1, 0) gives the plain paste's bytes.
-// paste_window_kernel keeps its name and its arguments: it compiles to what it compiled to before the tone entry existed.
-template <bool TONE>
+// ---- pbe_paste_window_u8, pbe_paste_window_tone_u8, pbe_paste_window_field_u8 ----------------------------------------------------------
+// One body for the three.  PASTE_TONE: the resampled result goes through res = fmaf(gain, res, offset) per channel (the affine map of
+// pbe_amd.window.fit_tone) before the blend; fmaf(1, res, 0) = res, so tone (1, 0) gives the plain paste's bytes.  PASTE_FIELD:
+// res += the coarse field of csrc/tone_field.hip, sampled bilinearly at the window pixel's centre; a zero field gives the plain paste's
+// bytes and a constant field b the bytes of tone (1, b), since fmaf(1, res, b) = res + b.  Nothing else differs.
+// paste_window_kernel and paste_window_tone_kernel keep their names and arguments: they compile to what they compiled to before.
+enum { PASTE_PLAIN = 0, PASTE_TONE = 1, PASTE_FIELD = 2 };
+struct FieldGrid {
+    const float* p;                // fp32 [3, Hc, Wc]
+    int Hc, Wc;
+    float sy, sx;                  // cells per window pixel: (float)((double)H / ((double)wh * cell)), the same in x
+};
+// one axis of the bilinear sample: the cell coordinate of window pixel o's centre, its two clamped cells and the fraction between them
+__device__ __forceinline__ void field_axis(int o, float s, int n, int& a, int& b, float& t) {
+    const float c = fmaf((float)o + 0.5f, s, -0.5f);
+    const float f = floorf(c);
+    const int i = (int)f;
+    a = min(max(i, 0), n - 1);
+    b = min(max(i + 1, 0), n - 1);
+    t = c - f;
+}
+template <int MODE>
 __device__ __forceinline__ void paste_window_body(const float* result, const float* alpha, unsigned char* pic, int Ws, int y0, int x0, int wh, int ww, int H, int W,
-                                                  const float (&gain)[3], const float (&offset)[3]) {
+                                                  const float (&gain)[3], const float (&offset)[3], const FieldGrid& fg) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;           // over wh * ww window pixels
     if (i >= (long)wh * ww) return;
     const float a = alpha[i];
@@ -254,9 +272,23 @@ __device__ __forceinline__ void paste_window_body(const float* result, const flo
     const SrcF32Planes src = {result, W, (long)H * W};
     float res[3];
     aa_resample3(src, oy, ox, H, W, wh, ww, res);
-    if (TONE) {
+    if (MODE == PASTE_TONE) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) res[c] = fmaf(gain[c], res[c], offset[c]);
+    }
+    if (MODE == PASTE_FIELD) {
+        int ya, yb, xa, xb;
+        float ty, tx;
+        field_axis(oy, fg.sy, fg.Hc, ya, yb, ty);
+        field_axis(ox, fg.sx, fg.Wc, xa, xb, tx);
+        const long plane = (long)fg.Hc * fg.Wc;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {                              // along y in the two columns, then along x
+            const float* f = fg.p + c * plane;
+            const float aa = f[(long)ya * fg.Wc + xa], ba = f[(long)yb * fg.Wc + xa], ab = f[(long)ya * fg.Wc + xb], bb = f[(long)yb * fg.Wc + xb];
+            const float ca = fmaf(ty, ba - aa, aa), cb = fmaf(ty, bb - ab, ab);
+            res[c] += fmaf(tx, cb - ca, ca);
+        }
     }
     unsigned char* d = pic + ((long)(y0 + oy) * Ws + (x0 + ox)) * 3;
     const float keep = 1.f - a;
@@ -271,12 +303,17 @@ __device__ __forceinline__ void paste_window_body(const float* result, const flo
 __global__ void __launch_bounds__(256) paste_window_kernel(const float* result, const float* alpha, unsigned char* pic, int Ws, int y0, int x0, int wh, int ww,
                                                            int H, int W) {
     const float none[3] = {0.f, 0.f, 0.f};
-    paste_window_body<false>(result, alpha, pic, Ws, y0, x0, wh, ww, H, W, none, none);
+    paste_window_body<PASTE_PLAIN>(result, alpha, pic, Ws, y0, x0, wh, ww, H, W, none, none, FieldGrid{nullptr, 0, 0, 0.f, 0.f});
 }
 __global__ void __launch_bounds__(256) paste_window_tone_kernel(const float* result, const float* alpha, unsigned char* pic, int Ws, int y0, int x0, int wh, int ww,
                                                                 int H, int W, float g0, float g1, float g2, float b0, float b1, float b2) {
     const float gain[3] = {g0, g1, g2}, offset[3] = {b0, b1, b2};
-    paste_window_body<true>(result, alpha, pic, Ws, y0, x0, wh, ww, H, W, gain, offset);
+    paste_window_body<PASTE_TONE>(result, alpha, pic, Ws, y0, x0, wh, ww, H, W, gain, offset, FieldGrid{nullptr, 0, 0, 0.f, 0.f});
+}
+__global__ void __launch_bounds__(256) paste_window_field_kernel(const float* result, const float* alpha, unsigned char* pic, int Ws, int y0, int x0, int wh, int ww,
+                                                                 int H, int W, FieldGrid fg) {
+    const float none[3] = {0.f, 0.f, 0.f};
+    paste_window_body<PASTE_FIELD>(result, alpha, pic, Ws, y0, x0, wh, ww, H, W, none, none, fg);
 }
 extern "C" int pbe_paste_window_u8(const float* result, const float* alpha, void* picture, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh,
                                    int32_t ww, int32_t H, int32_t W, pbe_stream_t stream) {
@@ -302,4 +339,20 @@ extern "C" int pbe_paste_window_tone_u8(const float* result, const float* alpha,
     hipLaunchKernelGGL(paste_window_tone_kernel, EW_GRID(total), dim3(256), 0, s, result, alpha, (unsigned char*)picture, Ws, y0, x0, wh, ww, H, W,
                        gain3[0], gain3[1], gain3[2], offset3[0], offset3[1], offset3[2]);
     EW_END(s, 12.0 * (double)H * W + 10.0 * (double)total, "pbe_paste_window_tone_u8");
+}
+extern "C" int pbe_paste_window_field_u8(const float* result, const float* alpha, void* picture, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t wh,
+                                         int32_t ww, int32_t H, int32_t W, const float* field, int32_t Hc, int32_t Wc, int32_t cell, pbe_stream_t stream) {
+    PBE_REQUIRE(result && alpha && picture && field && Hs > 0 && Ws > 0 && H > 0 && W > 0, "pbe_paste_window_field_u8: bad arguments");
+    PBE_REQUIRE(Hs <= WIN_MAX_DIM && Ws <= WIN_MAX_DIM && H <= WIN_MAX_DIM && W <= WIN_MAX_DIM, "pbe_paste_window_field_u8: an edge above %d", WIN_MAX_DIM);
+    PBE_REQUIRE(y0 >= 0 && x0 >= 0 && wh > 0 && ww > 0 && wh <= Hs - y0 && ww <= Ws - x0,
+                "pbe_paste_window_field_u8: window (%d, %d, %d, %d) outside the %d x %d picture", y0, x0, wh, ww, Hs, Ws);
+    PBE_REQUIRE(cell == 4 || cell == 8 || cell == 16 || cell == 32 || cell == 64, "pbe_paste_window_field_u8: cell %d is not one of 4, 8, 16, 32, 64", cell);
+    PBE_REQUIRE(Hc == (H + cell - 1) / cell && Wc == (W + cell - 1) / cell, "pbe_paste_window_field_u8: a field of %d x %d cells for a %d x %d result at cell %d", Hc, Wc,
+                H, W, cell);
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)wh * ww;
+    const FieldGrid fg = {field, Hc, Wc, (float)((double)H / ((double)wh * cell)), (float)((double)W / ((double)ww * cell))};
+    EW_BEGIN(s);
+    hipLaunchKernelGGL(paste_window_field_kernel, EW_GRID(total), dim3(256), 0, s, result, alpha, (unsigned char*)picture, Ws, y0, x0, wh, ww, H, W, fg);
+    EW_END(s, 12.0 * (double)H * W + 10.0 * (double)total + 12.0 * (double)Hc * Wc, "pbe_paste_window_field_u8");
 }

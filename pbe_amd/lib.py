@@ -124,6 +124,10 @@ SYMBOLS = {
     "pbe_paste_window_tone_u8": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_f32), C.POINTER(c_f32), c_vp]),
     "pbe_tone_stats_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "pbe_tone_stats_i64": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "pbe_paste_window_field_u8": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "pbe_tone_cells_i32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "pbe_tone_field_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "pbe_tone_field_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_sz, c_vp]),
     "pbe_mask_components_workspace_bytes": (c_sz, [c_i32, c_i32]),
     "pbe_mask_components_u8_i32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "pbe_component_boxes_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
@@ -144,8 +148,9 @@ _lib = None
 _lock = threading.Lock()
 
 SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_astat.hip", "attention.hip", "attention_mx8.hip", "ctx_attention.hip", "norm.hip",
-           "elementwise.hip", "window.hip", "holes.hip", "maskshape.hip", "tone.hip"]
-HASHED = [os.path.join("csrc", f) for f in SOURCES] + [os.path.join("csrc", "common.h"), os.path.join("csrc", "igemm_kernel.h"), os.path.join("..", "include", "pbe_hip.h"), "build.py"]
+           "elementwise.hip", "window.hip", "holes.hip", "maskshape.hip", "tone.hip", "tone_field.hip"]
+HASHED = [os.path.join("csrc", f) for f in SOURCES] + [os.path.join("csrc", "common.h"), os.path.join("csrc", "igemm_kernel.h"), os.path.join("csrc", "tone_bytes.h"),
+                                                         os.path.join("..", "include", "pbe_hip.h"), "build.py"]
 
 
 def source_hash() -> str:

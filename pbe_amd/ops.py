@@ -1262,18 +1262,35 @@ def _tone_pair(tone):
     return (C.c_float * 3)(*g), (C.c_float * 3)(*b)
 
 
-def paste_window(result: torch.Tensor, alpha: torch.Tensor, picture: torch.Tensor, window, tone=None) -> torch.Tensor:
+def paste_window(result: torch.Tensor, alpha: torch.Tensor, picture: torch.Tensor, window, tone=None, field: Optional[torch.Tensor] = None,
+                 cell: int = 8) -> torch.Tensor:
     """result fp32 [3, H, W] in [0, 1] (one image of image_post), alpha fp32 [wh, ww], window -> `picture` (uint8 [Hs, Ws, 3]) changed IN
     PLACE and returned: where alpha > 0, byte = rint(255 clamp(fma(alpha, res, (1 - alpha) byte / 255), 0, 1)) with res the antialiased
     filter of result to (wh, ww).  Where alpha == 0 and outside the window no byte is written.
     tone = (gain, offset), three floats each (pbe_amd.window.fit_tone's): res = fma(gain[c], res, offset[c]) per channel before the blend
-    (pbe_paste_window_tone_u8); ((1, 1, 1), (0, 0, 0)) gives the bytes of tone=None, which launches the plain kernel as it always did."""
+    (pbe_paste_window_tone_u8); ((1, 1, 1), (0, 0, 0)) gives the bytes of tone=None, which launches the plain kernel as it always did.
+    field = fp32 [3, Hc, Wc] (one window of tone_field's, at `cell` working pixels per cell: Hc = ceil(H / cell), Wc = ceil(W / cell)):
+    res += the field, sampled bilinearly at the window pixel's centre, before the blend (pbe_paste_window_field_u8).  A zero field gives
+    the bytes of the plain paste, a constant field b those of tone=((1, 1, 1), (b, b, b)).  field and tone together are refused."""
     Hs, Ws, y0, x0, wh, ww = _window_args("paste_window picture", picture, 3, window)
     _f(result, "paste_window result"); _f(alpha, "paste_window alpha")
     if result.dim() != 3 or result.shape[0] != 3 or not result.is_contiguous() or result.device != picture.device:
         raise _l.PbeError(f"paste_window: result must be a contiguous fp32 [3, H, W] tensor on the picture's device, got {tuple(result.shape)}")
     if tuple(alpha.shape) != (wh, ww) or not alpha.is_contiguous() or alpha.device != picture.device:
         raise _l.PbeError(f"paste_window: alpha must be a contiguous fp32 [{wh}, {ww}] tensor on the picture's device, got {tuple(alpha.shape)}")
+    if field is not None:
+        if tone is not None:
+            raise _l.PbeError("paste_window: field and tone together: the field is additive with gain 1, take one of the two")
+        _f(field, "paste_window field")
+        H, W = int(result.shape[1]), int(result.shape[2])
+        if isinstance(cell, bool) or cell not in TONE_CELLS:
+            raise _l.PbeError(f"paste_window: cell must be one of {TONE_CELLS}, got {cell!r}")
+        want = (3, -(-H // cell), -(-W // cell))
+        if tuple(field.shape) != want or not field.is_contiguous() or field.device != picture.device:
+            raise _l.PbeError(f"paste_window: field must be a contiguous fp32 {list(want)} tensor on the picture's device (cell {cell}), got {tuple(field.shape)}")
+        _l.check(_l.load().pbe_paste_window_field_u8(_p(result), _p(alpha), _p(picture), Hs, Ws, y0, x0, wh, ww, H, W, _p(field), want[1], want[2], int(cell),
+                                                     _stream()), "pbe_paste_window_field_u8")
+        return picture
     if tone is not None:
         g, b = _tone_pair(tone)
         _l.check(_l.load().pbe_paste_window_tone_u8(_p(result), _p(alpha), _p(picture), Hs, Ws, y0, x0, wh, ww, int(result.shape[1]), int(result.shape[2]),
@@ -1309,6 +1326,67 @@ def tone_stats(image: torch.Tensor, result: torch.Tensor, sel: torch.Tensor, out
         ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=image.device)
         _ws[key] = ws
     _l.check(lib.pbe_tone_stats_i64(_p(image), _p(result), _p(sel), _p(y), B, H, W, _p(ws), ws.numel(), _stream()), "pbe_tone_stats_i64")
+    return y
+
+
+# ---- a tone that varies across the window (csrc/tone_field.hip): cell sums of o - q, and the pull-push field made of them -------------
+TONE_CELLS = (4, 8, 16, 32, 64)
+
+
+def tone_cells(image: torch.Tensor, result: torch.Tensor, sel: torch.Tensor, cell: int = 8, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """image, result, sel as for tone_stats; cell in (4, 8, 16, 32, 64) working pixels (8: one latent cell) -> int32 [B, 4, Hc, Wc] on the
+    device, Hc = ceil(H / cell), Wc = ceil(W / cell): plane 0 the number of pixels of the cell with sel >= 0.5, planes 1 .. 3 the sum of
+    o - q over them per channel (o, q: tone_stats' two bytes).  The last cell row and column may be ragged.  Integer sums: the table is
+    exact and the same from run to run.  Every element is written exactly once."""
+    _f(image, "tone_cells image"); _f(result, "tone_cells result"); _f(sel, "tone_cells sel")
+    if image.dim() != 4 or image.shape[1] != 3 or image.numel() == 0 or max(image.shape[2:]) > 16384 or image.shape[0] > 65535:
+        raise _l.PbeError(f"tone_cells: image must be fp32 [B, 3, H, W] with B in 1 .. 65535 and edges in 1 .. 16384, got {tuple(image.shape)}")
+    B, _, H, W = (int(v) for v in image.shape)
+    if tuple(result.shape) != (B, 3, H, W) or tuple(sel.shape) != (B, 1, H, W):
+        raise _l.PbeError(f"tone_cells: result must be [{B}, 3, {H}, {W}] and sel [{B}, 1, {H}, {W}], got {tuple(result.shape)} and {tuple(sel.shape)}")
+    if not (image.is_contiguous() and result.is_contiguous() and sel.is_contiguous()):
+        raise _l.PbeError("tone_cells: image, result and sel must be contiguous")
+    if result.device != image.device or sel.device != image.device:
+        raise _l.PbeError(f"tone_cells: image, result and sel must be on one device, got {image.device}, {result.device}, {sel.device}")
+    if isinstance(cell, bool) or cell not in TONE_CELLS:
+        raise _l.PbeError(f"tone_cells: cell must be one of {TONE_CELLS}, got {cell!r}")
+    y = _plane_out("tone_cells", out, (B, 4, -(-H // cell), -(-W // cell)), torch.int32, image.device)
+    _l.check(_l.load().pbe_tone_cells_i32(_p(image), _p(result), _p(sel), _p(y), B, H, W, int(cell), _stream()), "pbe_tone_cells_i32")
+    return y
+
+
+def tone_field(cells: torch.Tensor, cell: int = 8, limit: float = 0.125, min_pixels: int = 64, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cells int32 [B, 4, Hc, Wc] (tone_cells at the same `cell`) -> fp32 [B, 3, Hc, Wc] on the device: the pull-push fill of
+    pbe_tone_field_f32 (include/pbe_hip.h), in [0, 1] units, every cell mean clamped to +-limit (a blended value may pass it by a rounding).  A sample with fewer than min_pixels selected
+    pixels (and with none, always) gets zeros.  One launch; every element is written; the same bits from run to run."""
+    import math
+    _req(cells, torch.int32, "tone_field cells")
+    if cells.dim() != 4 or cells.shape[1] != 4 or cells.numel() == 0 or cells.shape[0] > 65535 or not cells.is_contiguous():
+        raise _l.PbeError(f"tone_field: cells must be a contiguous int32 [B, 4, Hc, Wc] tensor with B in 1 .. 65535, got {tuple(cells.shape)}")
+    B, _, Hc, Wc = (int(v) for v in cells.shape)
+    if max(Hc, Wc) > 4096 or Hc * Wc > 1 << 20:
+        raise _l.PbeError(f"tone_field: a grid of {Hc} x {Wc} cells: edges up to 4096 and at most 2^20 cells (one workgroup walks a sample's pyramid); "
+                          "take a larger cell")
+    if isinstance(cell, bool) or cell not in TONE_CELLS:
+        raise _l.PbeError(f"tone_field: cell must be one of {TONE_CELLS}, got {cell!r}")
+    try:
+        lim = float(limit)
+    except (TypeError, ValueError) as e:
+        raise _l.PbeError(f"tone_field: limit must be a finite number > 0, got {limit!r}") from e
+    lim = C.c_float(lim).value if math.isfinite(lim) else lim                # the fp32 value the kernel receives
+    if not (lim > 0.0) or not math.isfinite(lim):
+        raise _l.PbeError(f"tone_field: limit must be a finite number > 0 (in fp32), got {limit!r}")
+    if isinstance(min_pixels, bool) or int(min_pixels) != min_pixels or not (0 <= min_pixels < 1 << 31):
+        raise _l.PbeError(f"tone_field: min_pixels must be an integer >= 0, got {min_pixels!r}")
+    y = _plane_out("tone_field", out, (B, 3, Hc, Wc), torch.float32, cells.device)
+    lib = _l.load()
+    need = lib.pbe_tone_field_workspace_bytes(B, Hc, Wc)
+    key = (cells.device.index, "tone_field")
+    ws = _ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=cells.device)
+        _ws[key] = ws
+    _l.check(lib.pbe_tone_field_f32(_p(cells), _p(y), B, Hc, Wc, int(cell), lim, int(min_pixels), _p(ws), ws.numel(), _stream()), "pbe_tone_field_f32")
     return y
 
 

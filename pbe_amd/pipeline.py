@@ -139,7 +139,7 @@ def window_inputs(pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor
 @torch.no_grad()
 def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], ref: torch.Tensor, *, size=(512, 512), context=0.5,
                    feather: int = 8, windows: Optional[Sequence] = None, mask_shape: Optional[dict] = None, tone: Optional[str] = None, tone_margin: int = 8,
-                   tone_gain_limit: float = 1.25, **inpaint_kwargs) -> Dict[str, object]:
+                   tone_gain_limit: float = 1.25, tone_cell: int = 8, tone_field_limit: float = 0.125, **inpaint_kwargs) -> Dict[str, object]:
     """Inpaint a region of pictures of any size and paste it back in place.  pictures: per sample a uint8 [Hs, Ws, 3] tensor, masks: a
     uint8 [Hs, Ws] tensor of the same Hs x Ws (a byte >= 128 is the hole), both contiguous and on the model's GPU; the sizes may differ
     from sample to sample.  Per sample ONE window is planned around the hole (pbe_amd.window.plan_window with `size`, `context`,
@@ -158,7 +158,11 @@ def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torc
     the list of shaped uint8 masks.  None (the default) takes the masks as they are.
     tone: "mean" or "affine" matches the pasted window's tone to the picture around the hole (match_tone below): each window is pasted
     through its own per-channel map gain * res + offset, and the result gains 'tone' (pbe_amd.window.fit_tone's list) and 'tone_stats'
-    (the int64 [B, 3, 6] table).  'image' stays the uncorrected working-size result.  None (the default) adds no key and no launch."""
+    (the int64 [B, 3, 6] table).  'image' stays the uncorrected working-size result.  None (the default) adds no key and no launch.
+    tone="field" follows a tone that varies across the window (match_tone_field below): each window is pasted with its own low-frequency
+    difference field added, at `tone_cell` working pixels per cell, the cell means clamped to +-`tone_field_limit`.  The result gains 'tone'
+    (pbe_amd.window.tone_field's summary list), 'tone_field' (fp32 [B, 3, Hc, Wc]) and 'tone_cells' (int32 [B, 4, Hc, Wc]), and no
+    'tone_stats'.  tone_margin means what it means for the other modes; tone_gain_limit is ignored (the field is additive, gain 1)."""
     from . import window as _w
     B = len(pictures)
     shape = None if mask_shape is None else _w.shape_args(mask_shape)
@@ -176,7 +180,10 @@ def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torc
     alphas = [ops.feather_alpha(masks[i], wins[i], feather) for i in range(B)]
     result = out["image"].float().contiguous()
     maps = [{}] * B                                       # tone=None: the call it always was
-    if tone is not None:
+    if tone == "field":
+        out["tone"], out["tone_field"], out["tone_cells"] = match_tone_field(inputs["image"], result, masks, wins, size, tone_margin, tone_cell, tone_field_limit)
+        maps = [{"field": out["tone_field"][i], "cell": tone_cell} for i in range(B)]
+    elif tone is not None:
         out["tone"], out["tone_stats"] = match_tone(inputs["image"], result, masks, wins, size, tone, tone_margin, tone_gain_limit)
         maps = [{"tone": (f["gain"], f["offset"])} for f in out["tone"]]
     out["pictures"] = [ops.paste_window(result[i], alphas[i], pictures[i].clone(), wins[i], **maps[i]) for i in range(B)]
@@ -186,7 +193,7 @@ def inpaint_window(model, pictures: Sequence[torch.Tensor], masks: Sequence[torc
     return out
 
 
-TONE_MODES = ("mean", "affine")
+TONE_MODES = ("mean", "affine", "field")
 
 
 def _check_tone(what: str, tone) -> None:
@@ -203,6 +210,8 @@ def match_tone(image: torch.Tensor, result: torch.Tensor, masks: Sequence[torch.
     own per channel; the map brings them back onto the original's, and the paste applies it to the whole window, hole included."""
     from . import window as _w
     _check_tone("match_tone", mode)
+    if mode == "field":
+        raise PbeError("match_tone: mode 'field' has no map per window: match_tone_field makes the difference field")
     B, (H, W) = len(windows), (int(size[0]), int(size[1]))
     sel = torch.empty((B, 1, H, W), dtype=torch.float32, device=image.device)
     for i in range(B):
@@ -211,13 +220,28 @@ def match_tone(image: torch.Tensor, result: torch.Tensor, masks: Sequence[torch.
     return _w.fit_tone(stats.cpu(), mode, gain_limit), stats
 
 
+def match_tone_field(image: torch.Tensor, result: torch.Tensor, masks: Sequence[torch.Tensor], windows: Sequence, size, margin: int = 8, cell: int = 8,
+                     limit: float = 0.125):
+    """The difference fields of a batch of windows: pbe_amd.window.tone_field's (summary list, field fp32 [B, 3, Hc, Wc], cells int32
+    [B, 4, Hc, Wc]) over the selection match_tone takes (pbe_amd.window.tone_selection per window, stacked).  One ops.tone_cells and one
+    ops.tone_field over the batch, one small host read for the summary."""
+    from . import window as _w
+    B, (H, W) = len(windows), (int(size[0]), int(size[1]))
+    sel = torch.empty((B, 1, H, W), dtype=torch.float32, device=image.device)
+    for i in range(B):
+        _w.tone_selection(masks[i], windows[i], (H, W), margin, out=sel[i])
+    field, cells, summary = _w.tone_field(image.contiguous(), result.contiguous(), sel, cell, limit)
+    return summary, field, cells
+
+
 PER_WINDOW_KWARGS = ("x_T", "post_eps", "ref_weights", "ref_regions")       # the arguments of inpaint with a leading batch dimension
 
 
 @torch.no_grad()
 def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], ref: torch.Tensor, *, size=(512, 512), context=0.5,
                   feather: int = 8, connectivity: int = 8, max_holes: int = 16, batch: Optional[int] = None, mask_shape: Optional[dict] = None,
-                  tone: Optional[str] = None, tone_margin: int = 8, tone_gain_limit: float = 1.25, **inpaint_kwargs) -> Dict[str, object]:
+                  tone: Optional[str] = None, tone_margin: int = 8, tone_gain_limit: float = 1.25, tone_cell: int = 8, tone_field_limit: float = 0.125,
+                  **inpaint_kwargs) -> Dict[str, object]:
     """Inpaint every hole of a picture in a window of its own and paste them all back into one picture.  pictures / masks: as in
     inpaint_window (B samples).  Per sample the mask is labelled on the device (ops.mask_components at `connectivity`), the component
     boxes come back in one small read (ops.component_boxes) and pbe_amd.window.plan_holes groups the components whose blend zones could
@@ -237,8 +261,9 @@ def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch
     window fp32 [wh, ww]) and 'inputs' (window_inputs over the N windows).
     mask_shape: as in inpaint_window - each mask is shaped once (pbe_amd.window.shape_mask) before it is labelled, the holes are those
     of the shaped mask, and the result gains 'masks'.  `connectivity` here is the labelling's; the box stage has its own key.
-    tone: as in inpaint_window, one map per WINDOW ('tone' and 'tone_stats' have N entries / rows, concatenated over the chunks).  The
-    selection comes from each window's OWN mask, as alpha does: another group's hole inside the window was a known pixel for the model
+    tone: as in inpaint_window, one map (or, with "field", one difference field: tone_cell, tone_field_limit) per WINDOW ('tone' and
+    'tone_stats', or 'tone_field' and 'tone_cells', have N entries / rows, concatenated over the chunks; "field" ignores
+    tone_gain_limit).  The selection comes from each window's OWN mask, as alpha does: another group's hole inside the window was a known pixel for the model
     and counts as one."""
     from . import window as _w
     B = len(pictures)
@@ -283,7 +308,10 @@ def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch
     result = out["image"].float().contiguous()
     pasted = [p.clone() for p in pictures]
     maps = [{}] * N                                       # tone=None: the call it always was
-    if tone is not None:
+    if tone == "field":
+        out["tone"], out["tone_field"], out["tone_cells"] = match_tone_field(inputs["image"], result, own_masks, wins, size, tone_margin, tone_cell, tone_field_limit)
+        maps = [{"field": out["tone_field"][n], "cell": tone_cell} for n in range(N)]
+    elif tone is not None:
         out["tone"], out["tone_stats"] = match_tone(inputs["image"], result, own_masks, wins, size, tone, tone_margin, tone_gain_limit)
         maps = [{"tone": (f["gain"], f["offset"])} for f in out["tone"]]
     for n, h in enumerate(holes):

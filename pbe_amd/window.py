@@ -216,7 +216,7 @@ def plan_holes(table, picture_hw: Sequence[int], working: Sequence[int], context
 
 
 # ---- the tone of a pasted window (csrc/tone.hip): one affine map per window and channel, fitted on the known pixels ---------------------
-TONE_MODES = ("mean", "affine")
+TONE_MODES = ("mean", "affine", "field")
 
 
 def _f32(v) -> float:
@@ -267,8 +267,10 @@ def fit_tone(stats, mode: str = "affine", gain_limit: float = 1.25, min_pixels: 
       min_pixels = 64.
     An unknown mode, gain_limit < 1 (or not finite), a table of another shape or rows of one sample with different n raise PbeError."""
     import math
+    if mode == "field":
+        raise PbeError("fit_tone: mode 'field' is not a fit of one map per window: pbe_amd.window.tone_field makes the difference field from the pictures themselves")
     if mode not in TONE_MODES:
-        raise PbeError(f"fit_tone: mode must be one of {TONE_MODES}, got {mode!r}")
+        raise PbeError(f"fit_tone: mode must be one of {TONE_MODES[:2]}, got {mode!r}")
     try:
         limit = float(gain_limit)
     except (TypeError, ValueError) as e:
@@ -322,3 +324,57 @@ def tone_selection(mask, window, size, margin: int = 8, out=None):
     if r > 2047:
         raise PbeError(f"tone_selection: a margin of {margin} working pixels is {r} picture pixels in window {tuple(window)}, more than 2047")
     return ops.window_mask(ops.mask_grow(mask, r) if r > 0 else mask, window, size, out=out)
+
+
+# ---- a tone that varies across the window (csrc/tone_field.hip): a low-frequency field of the difference, added by the paste -----------
+def field_levels(grid: Sequence[int]) -> int:
+    """The levels of the pull-push pyramid over a grid of (Hc, Wc) cells, the table included: 1 for a 1 x 1 grid."""
+    h, w, n = int(grid[0]), int(grid[1]), 1
+    while h > 1 or w > 1:
+        h, w, n = (h + 1) // 2, (w + 1) // 2, n + 1
+    return n
+
+
+def tone_field(image, result, sel, cell: int = 8, limit: float = 0.125, min_pixels: int = 64):
+    """A tone that varies across the window - a vignette, a gradient the decoder flattens - as a low-frequency difference field.
+    image fp32 [B, 3, H, W] is what the model saw, result fp32 [B, 3, H, W] in [0, 1] what it returned, sel fp32 [B, 1, H, W] the pixels
+    to trust (tone_selection), all on the GPU.  Returns (field, cells, summary):
+      cells   int32 [B, 4, Hc, Wc] = ops.tone_cells: per cell of `cell` x `cell` working pixels n and the sums of o - q per channel;
+      field   fp32 [B, 3, Hc, Wc] = ops.tone_field: the pull-push fill of the cell means, in [0, 1] units, the cell means clamped to +-limit;
+              ops.paste_window(..., field=field[i], cell=cell) adds it, sampled bilinearly, to the pasted window;
+      summary a list, one dict per window: {"mode": "field", "n", "cell", "grid": [Hc, Wc], "levels", "offset": [3] (the pyramid's top
+              mean per channel: tone="mean"'s offset, clamped to +-limit, for comparison), "field_min": [3], "field_max": [3] (grey
+              levels), "identity"} - from ONE small host read (the cell sums and the field's range are reduced on the device).
+    n < min_pixels (and n = 0 always) gives a field of zeros: too little evidence changes nothing.
+    DECISIONS (none of them is a measurement):
+      pull-push, not a harmonic (Poisson) solve: a fixed operation count, any grid size, no convergence question;
+      a level trusts its own mean fully at one full finest cell of evidence: the cap is cell^2 at every level;
+      limit = 0.125 is 32 grey levels: a larger local difference means that the known pixels were redrawn, and that is not tone;
+      the field is additive, with gain 1; a constant difference gives exactly tone="mean"'s offset in every element.
+    cell outside (4, 8, 16, 32, 64), a limit that is not finite and > 0, min_pixels < 0 and tensors of other shapes raise PbeError."""
+    import torch
+    from . import ops
+    if isinstance(cell, bool) or cell not in ops.TONE_CELLS:
+        raise PbeError(f"tone_field: cell must be one of {ops.TONE_CELLS}, got {cell!r}")
+    try:
+        lim = float(limit)
+    except (TypeError, ValueError) as e:
+        raise PbeError(f"tone_field: limit must be a finite number > 0, got {limit!r}") from e
+    if not (lim > 0.0) or lim == float("inf"):
+        raise PbeError(f"tone_field: limit must be a finite number > 0, got {limit!r}")
+    if isinstance(min_pixels, bool) or int(min_pixels) != min_pixels or min_pixels < 0:
+        raise PbeError(f"tone_field: min_pixels must be an integer >= 0, got {min_pixels!r}")
+    cells = ops.tone_cells(image, result, sel, cell)
+    field = ops.tone_field(cells, cell, lim, int(min_pixels))
+    B, _, Hc, Wc = (int(v) for v in cells.shape)
+    # one host read: the four whole-window sums (exact in fp64: below 2^37) and the field's range per channel
+    small = torch.cat([cells.sum(dim=(2, 3), dtype=torch.int64).double(), field.amin(dim=(2, 3)).double(), field.amax(dim=(2, 3)).double()], dim=1).cpu().tolist()
+    lim32 = _f32(lim)
+    summary = []
+    for row in small:
+        n = int(row[0])
+        identity = n == 0 or n < min_pixels
+        offset = [0.0 if n == 0 else min(max(_f32(int(S) / (255.0 * n)), -lim32), lim32) for S in row[1:4]]
+        summary.append({"mode": "field", "n": n, "cell": int(cell), "grid": [Hc, Wc], "levels": field_levels((Hc, Wc)), "offset": offset,
+                        "field_min": [255.0 * v for v in row[4:7]], "field_max": [255.0 * v for v in row[7:10]], "identity": identity})
+    return field, cells, summary

@@ -39,7 +39,11 @@ to the picture around the hole: per window and channel an offset (`mean`) or a g
 pixels farther than `--tone_margin PX` (default 8) working pixels from the hole, so that the result's known pixels fall back onto the
 original's, and the whole window is pasted through that map.  A line per window reports gains, offsets, the rms difference before and
 after in grey levels and the pixel count; `pasted/<stem>_<seed>.tone.json` holds the same (pbe_amd.window.fit_tone's list).  `results/`
-keeps the uncorrected window.
+keeps the uncorrected window.  `--match_tone field` follows a tone that VARIES across the window (a vignette, a gradient the decoder
+flattens): the difference between the original's and the result's known pixels is summed per cell of `--tone_cell PX` (4, 8, 16, 32 or
+64; default 8) working pixels, filled in over the hole by a pull-push pyramid, clamped to +-`--tone_field_limit V` (default 0.125 of
+full scale) and added to the pasted window.  The line per window reports the pixel count, the grid and the field's range in grey
+levels; the `.tone.json` holds pbe_amd.window.tone_field's summary.
 
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
@@ -98,9 +102,14 @@ def parse(argv=None):
                    "blend zones could touch) gets a window of its own; pasted/ holds all of them")
     p.add_argument("--reference_per_hole", action="store_true", help="with --per_hole: the i-th --reference_path is the exemplar of the i-th hole, "
                    "holes in raster order of their first pixel")
-    p.add_argument("--match_tone", choices=("mean", "affine"), default=None, help="with --paste_back: match the pasted window's tone to the picture "
-                   "around the hole - per window and channel an offset (mean) or a gain and an offset (affine) fitted on the known pixels; "
+    p.add_argument("--match_tone", choices=("mean", "affine", "field"), default=None, help="with --paste_back: match the pasted window's tone to the "
+                   "picture around the hole - per window and channel an offset (mean) or a gain and an offset (affine) fitted on the known pixels, "
+                   "or a low-frequency difference field that follows a tone varying across the window (field); "
                    "pasted/<stem>_<seed>.tone.json holds the fit")
+    p.add_argument("--tone_cell", type=int, default=8, choices=(4, 8, 16, 32, 64), metavar="PX", help="with --match_tone field: the cell of the "
+                   "difference field in working pixels (4, 8, 16, 32 or 64)")
+    p.add_argument("--tone_field_limit", type=float, default=0.125, metavar="V", help="with --match_tone field: the field is clamped to +-V of full "
+                   "scale (0.125 = 32 grey levels)")
     p.add_argument("--tone_margin", type=int, default=8, metavar="PX", help="with --match_tone: known pixels nearer to the hole than this many "
                    "working pixels are left out of the fit")
     p.add_argument("--max_holes", type=int, default=16, help="with --per_hole: more separate holes than this is an error")
@@ -132,6 +141,10 @@ def parse(argv=None):
         raise SystemExit("--match_tone / --tone_margin need --paste_back: the tone is matched where the window is pasted into the picture")
     if opt.tone_margin < 0:
         p.error("--tone_margin must be an integer >= 0")
+    if (opt.tone_cell != 8 or opt.tone_field_limit != 0.125) and opt.match_tone != "field":
+        raise SystemExit("--tone_cell / --tone_field_limit need --match_tone field: the other modes fit one map per window")
+    if not (0.0 < opt.tone_field_limit < float("inf")):
+        p.error("--tone_field_limit must be finite and > 0")
     if opt.per_hole:
         if not opt.paste_back:
             raise SystemExit("--per_hole needs --paste_back: the holes are pasted back into the one picture")
@@ -197,10 +210,16 @@ def save_reference_maps(outdir, stem, seed, ref_maps, H, W):
 
 
 def report_tone(outdir, stem, seed, fits):
-    """--match_tone: a line per window and pasted/<stem>_<seed>.tone.json with pbe_amd.window.fit_tone's list."""
+    """--match_tone: a line per window and pasted/<stem>_<seed>.tone.json with pbe_amd.window.fit_tone's list (tone_field's summary in the
+    field mode)."""
     import json
     fmt = lambda v, spec: "(" + ", ".join(format(x, spec) for x in v) + ")"      # noqa: E731
     for i, f in enumerate(fits):
+        if f.get("mode") == "field":
+            print(f"tone of window {i}: field over n = {f['n']} pixels, grid {f['grid'][0]} x {f['grid'][1]} cells of {f['cell']} ({f['levels']} levels), range "
+                  f"{fmt(f['field_min'], '+.2f')} .. {fmt(f['field_max'], '+.2f')} grey levels, whole-window offset {fmt(f['offset'], '+.4f')}"
+                  + (" (identity)" if f["identity"] else ""))
+            continue
         print(f"tone of window {i}: gain {fmt(f['gain'], '.4f')}, offset {fmt(f['offset'], '+.4f')}, rms {fmt(f['rms_before'], '.2f')} -> "
               f"{fmt(f['rms_after'], '.2f')} grey levels over n = {f['n']} pixels" + (" (identity)" if f["identity"] else ""))
     with open(os.path.join(outdir, "pasted", f"{stem}_{seed}.tone.json"), "w") as fh:
@@ -238,7 +257,8 @@ def run_per_hole(opt, model, device, refs):
     kw["post_eps"] = torch.randn(shape, generator=torch.Generator().manual_seed(opt.seed)).to(device)
     out = pipeline.inpaint_holes(model, [picture], [picture_mask], ref, size=size, context=opt.context, feather=opt.feather, max_holes=opt.max_holes,
                                  steps=opt.ddim_steps, scale=opt.scale, sampler="dpm" if opt.dpm_solver else ("plms" if opt.plms else "ddim"),
-                                 **({} if opt.match_tone is None else {"tone": opt.match_tone, "tone_margin": opt.tone_margin}), **kw)
+                                 **({} if opt.match_tone is None else {"tone": opt.match_tone, "tone_margin": opt.tone_margin}),
+                                 **({"tone_cell": opt.tone_cell, "tone_field_limit": opt.tone_field_limit} if opt.match_tone == "field" else {}), **kw)
     stem = os.path.basename(opt.image_path)[:-4]
     if not opt.skip_save:
         for i in range(N):
@@ -352,13 +372,21 @@ def main(argv=None):
             os.makedirs(os.path.join(opt.outdir, "pasted"), exist_ok=True)
             alpha = ops.feather_alpha(picture_mask, win, opt.feather)
             maps = [None] * xd.shape[0]
-            if opt.match_tone is not None:                                             # per saved sample against the one window the model saw
+            fields = None
+            if opt.match_tone == "field":                                              # per saved sample against the one window the model saw
+                n = xd.shape[0]
+                fits, fields, _ = pipeline.match_tone_field(t["image"].expand(n, -1, -1, -1), xd, [picture_mask] * n, [win] * n, (opt.H, opt.W), opt.tone_margin,
+                                                            opt.tone_cell, opt.tone_field_limit)
+            elif opt.match_tone is not None:
                 n = xd.shape[0]
                 fits, _ = pipeline.match_tone(t["image"].expand(n, -1, -1, -1), xd, [picture_mask] * n, [win] * n, (opt.H, opt.W), opt.match_tone,
                                               opt.tone_margin)
                 maps = [(f["gain"], f["offset"]) for f in fits]
             for i in range(xd.shape[0]):
-                pasted = ops.paste_window(xd[i].contiguous(), alpha, picture.clone(), win, tone=maps[i])
+                if fields is not None:
+                    pasted = ops.paste_window(xd[i].contiguous(), alpha, picture.clone(), win, field=fields[i], cell=opt.tone_cell)
+                else:
+                    pasted = ops.paste_window(xd[i].contiguous(), alpha, picture.clone(), win, tone=maps[i])
                 Image.fromarray(pasted.cpu().numpy()).save(os.path.join(opt.outdir, "pasted", f"{filename[:-4]}_{opt.seed}.png"))
             if opt.match_tone is not None:
                 report_tone(opt.outdir, filename[:-4], opt.seed, fits)
