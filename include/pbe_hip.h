@@ -633,6 +633,34 @@ int pbe_mask_dist2_u8_i32(const void* mask, int32_t* d2, int32_t Hs, int32_t Ws,
 int pbe_mask_from_dist2_u8(const int32_t* d2, void* out_mask, int32_t Hs, int32_t Ws, int32_t t2, int32_t above, pbe_stream_t stream);
 int pbe_fill_boxes_u8(const int32_t* boxes, int32_t n, void* out_mask, int32_t Hs, int32_t Ws, pbe_stream_t stream);
 
+/* The exemplar cut from a uint8 picture on the device (pbe_amd/csrc/exemplar.hip; not in the reference, which resizes the exemplar with
+ * PIL on the host, scripts/inference.py:309): Pillow's 8-bit resize in its own integers, byte-equal to Image.resize.  Additive to ABI 8.
+ * The tables of one axis come from the host (pbe_amd.exemplar.resample_tables: Pillow's precompute_coeffs + normalize_coeffs_8bpc in
+ * float64): bounds i32 [out, 2], rows (xmin, n), and coeffs i32 [out, ksize], the n weights of an output index rounded to 22 fractional
+ * bits, zero past n; both on the device, 4-byte aligned, 1 <= ksize <= 98305.  A pass gives, per byte,
+ *   clip((2^21 + sum_{x < n} src[xmin + x] * coeffs[i, x]) >> 22, 0, 255)       int32 accumulator, arithmetic shift, no float.
+ * The kernels clamp xmin, n and every tap to the operands, so a wrong table cannot make them read outside; it gives wrong bytes.
+ * pbe_resample_h_u8          picture u8 [Hs, Ws, 3], its rows first .. last - 1 -> out u8 [last - first, ow, 3]: the horizontal pass.  mask
+ *                            (may be NULL) u8 [Hs, Ws]: a source pixel whose mask byte is < 128 reads as the three bytes fill3 (HOST
+ *                            pointer, required with a mask).  The source segment of 64 output columns is staged through LDS in rounds
+ *                            of 4096 pixels (whole aligned dwords, each byte once per workgroup); ksize is a loop, not a register array.
+ * pbe_resample_v_u8          src u8 [rows, ow, 3] -> out u8 [oh, ow, 3]: the vertical pass (bounds count rows of src).  mask (may be NULL)
+ *                            u8 [rows, ow] / fill3 as above, for launches on the picture itself.  planes (may be NULL) fp32 [3, oh, ow]
+ *                            takes (byte / 255 - mean3[c]) / std3[c] with the expression of pbe_u8_to_planes_f32 (csrc/u8_norm.h): its bits.
+ *                            With bounds (y, 1) and coefficient 2^22 the pass is a copy (what Pillow does when it skips both passes).
+ * pbe_resample_workspace_bytes  bytes of the intermediate of `rows` rows of `ow` pixels (0 for edges outside 1 .. 16384).
+ * pbe_mask_box_i32           mask u8 [Hs, Ws] -> table i32 [bands, 4], bands = pbe_mask_box_bands(Hs) = ceil(Hs / 32): row b holds
+ *                            (ya, yb, xa, xb), inclusive, of the bytes >= 128 in mask rows 32 b .. 32 b + 31, or four -1 where there is
+ *                            none.  No atomics: one workgroup per band, every element written once; the caller reduces the rows.
+ * All edges 1 .. 16384.  No synchronisation; the entry points return PBE_EINVAL for null / misaligned / out-of-range arguments. */
+size_t pbe_resample_workspace_bytes(int32_t rows, int32_t ow);
+int pbe_resample_h_u8(const void* picture, const void* mask, const uint8_t* fill3, void* out, int32_t Hs, int32_t Ws, int32_t first, int32_t last,
+                      int32_t ow, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, pbe_stream_t stream);
+int pbe_resample_v_u8(const void* src, const void* mask, const uint8_t* fill3, void* out, float* planes, int32_t rows, int32_t ow, int32_t oh,
+                      const int32_t* bounds, const int32_t* coeffs, int32_t ksize, const float* mean3, const float* std3, pbe_stream_t stream);
+int32_t pbe_mask_box_bands(int32_t Hs);
+int pbe_mask_box_i32(const void* mask, int32_t* table, int32_t Hs, int32_t Ws, int32_t bands, pbe_stream_t stream);
+
 /* pbe_tune— developer knobs for A/B runs in one process (never needed for correctness):
  * key 1: force an implicit-GEMM tile config index (-1 = heuristic); key 2: allow split-K (0/1);
  * key 3: attention queries-per-wave factor (0 = heuristic, 1, 2); key 4: ping-pong main loop of the halo-resident conv tiles (0/1);

@@ -2,6 +2,7 @@
 // NCHW API boundary, im2col for the three tiny-Cin convs, GEGLU, timestep embedding, the fused
 // PLMS sampler update, the DPM-Solver++ sampler update, VAE posterior sampling, CLIP patchify.
 #include "common.h"
+#include "u8_norm.h"
 #include "../../include/pbe_hip.h"
 
 #define EW_GRID(n) dim3((unsigned)(((n) + 255) / 256))
@@ -454,7 +455,7 @@ __global__ void u8_to_planes_kernel(const unsigned char* src, float* dst, int C,
         float v = (float)src[i * C + c] / 255.0f;
         if (binarize == 1) v = (1.0f - v) < 0.5f ? 0.0f : 1.0f;
         else if (binarize == 2) v = 1.0f - v;
-        else { v = v - mean[c]; asm volatile("" : "+v"(v)); v = v / sd[c]; }
+        else v = pbe_u8_norm(src[i * C + c], mean[c], sd[c]);              // u8_norm.h: shared with exemplar.hip
         dst[(b * C + c) * HW + px] = v;
     }
 }

@@ -1589,6 +1589,107 @@ def fill_boxes(boxes, shape, out: Optional[torch.Tensor] = None, device=None) ->
     return y
 
 
+# ---- the exemplar cut from a picture (csrc/exemplar.hip): Pillow's 8-bit resize on the device, the box of a mask ----------------------
+MASK_BOX_BAND = 32            # rows of one band of pbe_mask_box_i32
+
+
+def resample_u8(picture: torch.Tensor, out_hw, box=None, filter: str = "bicubic", mask: Optional[torch.Tensor] = None, fill=None, mean=None, std=None,
+                out: Optional[torch.Tensor] = None, out_planes: Optional[torch.Tensor] = None):
+    """uint8 [Hs, Ws, 3] picture on the GPU -> (uint8 [oh, ow, 3], planes): the bytes of Pillow's
+    Image.resize((ow, oh), filter, box=box) - its fixed-point arithmetic restated (pbe_amd.exemplar.resample_tables on the host, the two
+    integer passes on the device), filter "bicubic" (Image.resize's default), "bilinear" or "lanczos".  box: Pillow's (x0, y0, x1, y1),
+    floats allowed, None = the whole picture.  mask uint8 [Hs, Ws] with fill (three bytes): a pixel whose mask byte is < 128 reads as
+    `fill`.  mean / std (three floats each): planes = fp32 [3, oh, ow] = (byte / 255 - mean) / std with u8_to_planes' bits; else None.
+    As Pillow does, a pass whose axis keeps its size under a box that spans it is skipped: zero, one or two resampling launches (with
+    none, one copying launch), plus pbe_u8_to_planes_f32 where the last launch is the horizontal pass.  The horizontal pass runs first,
+    except under Image.resize's rule for very tall pictures (pbe_amd.exemplar.vertical_first)."""
+    from . import exemplar as _ex
+    Hs, Ws, _, _, _, _ = _window_args("resample_u8 picture", picture, 3, (0, 0, 1, 1))
+    try:
+        oh, ow = (int(v) for v in out_hw)
+        exact = len(tuple(out_hw)) == 2 and all(int(v) == v for v in out_hw)
+    except (TypeError, ValueError) as e:
+        raise _l.PbeError(f"resample_u8: out_hw must be two integers (oh, ow), got {out_hw!r}") from e
+    if not exact or min(oh, ow) < 1 or max(oh, ow, Hs, Ws) > 16384:
+        raise _l.PbeError(f"resample_u8: output {out_hw!r} and picture {Hs} x {Ws} must have edges in 1 .. 16384")
+    x0, y0, x1, y1 = _ex.validate_box(box, (Hs, Ws))
+    fill3 = None
+    if (mask is None) != (fill is None):
+        raise _l.PbeError("resample_u8: mask and fill go together (fill is the colour of the pixels whose mask byte is < 128)")
+    if mask is not None:
+        _window_args("resample_u8 mask", mask, 1, (0, 0, 1, 1))
+        if tuple(mask.shape) != (Hs, Ws) or mask.device != picture.device:
+            raise _l.PbeError(f"resample_u8: the mask is {tuple(mask.shape)} on {mask.device}, the picture {Hs} x {Ws} on {picture.device}")
+        fill3 = (C.c_uint8 * 3)(*_ex._fill3(fill))
+    if (mean is None) != (std is None):
+        raise _l.PbeError("resample_u8: mean and std go together")
+    dev = picture.device
+    y = _plane_out("resample_u8", out, (oh, ow, 3), torch.uint8, dev)
+    planes, m, sd = None, None, None
+    if mean is not None:
+        planes = _plane_out("resample_u8 planes", out_planes, (3, oh, ow), torch.float32, dev)
+        m, sd = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    elif out_planes is not None:
+        raise _l.PbeError("resample_u8: out_planes needs mean and std")
+    need_h = ow != Ws or x0 != 0.0 or x1 != ow                   # Pillow's need_horizontal / need_vertical
+    need_v = oh != Hs or y0 != 0.0 or y1 != oh
+    lib = _l.load()
+
+    def up(a):
+        return torch.from_numpy(a).to(dev)
+    def ws(rows, cols):
+        need = lib.pbe_resample_workspace_bytes(rows, cols)
+        if need < rows * cols * 3:
+            raise _l.PbeError(f"resample_u8: no workspace for an intermediate of {rows} x {cols}")
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    bv, kv = _ex.resample_tables(Hs, y0, y1, oh, filter) if need_v else _ex.identity_tables(oh)
+    src, src_mask, rows = picture, mask, Hs
+    if need_h and _ex.vertical_first(Hs, Ws, oh):                 # Image.resize's rule for very tall pictures: the height first, over the full width
+        bh, kh = _ex.resample_tables(Ws, x0, x1, ow, filter)
+        tmp, dbv, dkv, dbh, dkh = ws(oh, Ws), up(bv), up(kv), up(bh), up(kh)
+        _l.check(lib.pbe_resample_v_u8(_p(picture), _p(mask), fill3, _p(tmp), None, Hs, Ws, oh, _p(dbv), _p(dkv), kv.shape[1], None, None, _stream()),
+                 "pbe_resample_v_u8")
+        _l.check(lib.pbe_resample_h_u8(_p(tmp), None, None, _p(y), oh, Ws, 0, oh, ow, _p(dbh), _p(dkh), kh.shape[1], _stream()), "pbe_resample_h_u8")
+        if planes is not None:
+            _l.check(lib.pbe_u8_to_planes_f32(_p(y), _p(planes), 1, 3, oh * ow, m, sd, 0, _stream()), "pbe_u8_to_planes_f32")
+        return y, planes
+    if need_h:
+        bh, kh = _ex.resample_tables(Ws, x0, x1, ow, filter)
+        first, last = (int(bv[0, 0]), int(bv[-1, 0] + bv[-1, 1])) if need_v else (0, Hs)      # the rows the vertical pass reads
+        bv = bv.copy()
+        bv[:, 0] -= first
+        rows = last - first
+        tmp = ws(rows, ow) if need_v else y
+        dbh, dkh = up(bh), up(kh)
+        _l.check(lib.pbe_resample_h_u8(_p(picture), _p(mask), fill3, _p(tmp), Hs, Ws, first, last, ow, _p(dbh), _p(dkh), kh.shape[1], _stream()),
+                 "pbe_resample_h_u8")
+        src, src_mask = tmp, None
+        if not need_v:
+            if planes is not None:
+                _l.check(lib.pbe_u8_to_planes_f32(_p(y), _p(planes), 1, 3, oh * ow, m, sd, 0, _stream()), "pbe_u8_to_planes_f32")
+            return y, planes
+    dbv, dkv = up(bv), up(kv)
+    _l.check(lib.pbe_resample_v_u8(_p(src), _p(src_mask), fill3 if src_mask is not None else None, _p(y), _p(planes), rows, ow, oh, _p(dbv), _p(dkv),
+                                   kv.shape[1], m, sd, _stream()), "pbe_resample_v_u8")
+    return y, planes
+
+
+def mask_box(mask: torch.Tensor):
+    """uint8 [Hs, Ws] mask on the GPU -> (ya, yb, xa, xb), inclusive: the bounding box of the bytes >= 128 (window.hole_box's, without
+    bringing the mask to the host), or None where there is none.  One workgroup per band of 32 rows writes its own box; the
+    ceil(Hs / 32) x 4 integers are read back and reduced here.  BLOCKS on that read-back."""
+    Hs, Ws = _plane_args("mask_box mask", mask, torch.uint8)
+    lib = _l.load()
+    bands = lib.pbe_mask_box_bands(Hs)
+    table = torch.empty((bands, 4), dtype=torch.int32, device=mask.device)
+    _l.check(lib.pbe_mask_box_i32(_p(mask), _p(table), Hs, Ws, bands, _stream()), "pbe_mask_box_i32")
+    t = table.cpu().numpy()
+    t = t[t[:, 1] >= 0]
+    if t.shape[0] == 0:
+        return None
+    return int(t[:, 0].min()), int(t[:, 1].max()), int(t[:, 2].min()), int(t[:, 3].max())
+
+
 def bcast_row(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, B: int, y_bs: int) -> None:
     """out[bi * y_bs + c] = a[c] + b[c] for bi < B."""
     _h(a, "bcast_row a"); _h(b, "bcast_row b"); _h(out, "bcast_row out")

@@ -60,6 +60,17 @@ def load_triple_device(image_path: str, mask_path: str, reference_path: str, dev
     return {"image": img, "mask": mask, "inpaint": ops.mul_planes(img, mask), "ref": ref}
 
 
+def load_reference_device(path: str, device, box=None, mask_path=None, **crop) -> Dict[str, torch.Tensor]:
+    """The exemplar of `path` cut on the GPU (pbe_amd.exemplar.exemplar_from_picture): PIL decodes only, the picture's full-size bytes
+    travel, the crop, Pillow's resize to 224 x 224 and the CLIP normalisation are HIP kernels.  box: Pillow's (x0, y0, x1, y1);
+    mask_path: an image of the picture's size, white = the object; crop: exemplar_from_picture's pad / square / fill / size / filter.
+    Returns its {'ref' [1, 3, 224, 224], 'u8', 'box'}; with no box, mask or crop keyword 'ref' equals load_triple_device's bit for bit."""
+    from .exemplar import exemplar_from_picture
+    picture = torch.from_numpy(np.array(Image.open(path).convert("RGB"), dtype=np.uint8)).to(device)
+    mask = None if mask_path is None else torch.from_numpy(np.array(Image.open(mask_path).convert("L"), dtype=np.uint8)).to(device)
+    return exemplar_from_picture(picture, box=box, mask=mask, **crop)
+
+
 def un_norm(x: torch.Tensor) -> torch.Tensor:
     return (x + 1.0) / 2.0
 

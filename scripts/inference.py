@@ -44,6 +44,15 @@ flattens): the difference between the original's and the result's known pixels i
 64; default 8) working pixels, filled in over the hole by a pull-push pyramid, clamped to +-`--tone_field_limit V` (default 0.125 of
 full scale) and added to the pasted window.  The line per window reports the pixel count, the grid and the field's range in grey
 levels; the `.tone.json` holds pbe_amd.window.tone_field's summary.
+`--reference_on_device` (not in the reference) cuts the exemplar on the device: PIL only decodes `--reference_path`, its full-size bytes
+travel, and Pillow's own resize to 224 x 224 runs as HIP kernels (pbe_amd.exemplar) - the picture is the default path's bit for bit.
+`--reference_box X0 Y0 X1 Y1` (four numbers per `--reference_path`, Pillow's box, fractions allowed) takes that part of the reference as
+the exemplar; `--reference_mask PATH ...` (one per reference, of its size, white = the object) takes the object's bounding box instead;
+`--reference_pad F` grows the box by F of its size on each side, `--reference_square` makes it square about its centre (both inside
+the picture: shifted at a border, not shrunk), `--reference_fill R G B` (with `--reference_mask`) paints everything off the object in that
+colour before the resize.  Any of them implies the device path.  The cut exemplars are written to
+`<outdir>/reference_crops/<stem>_ref<k>.png`.  All of it works with several references, `--reference_per_hole`, `--paste_back` and every
+sampler.
 
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
@@ -119,6 +128,17 @@ def parse(argv=None):
     p.add_argument("--mask_open", type=float, default=0.0, metavar="PX", help="(not in the reference) remove specks of the hole narrower than a disc of this radius")
     p.add_argument("--mask_box", action="store_true", help="(not in the reference) replace every hole by its bounding box; applied after "
                    "--mask_open, --mask_close and --mask_grow, in that order")
+    p.add_argument("--reference_on_device", action="store_true", help="(not in the reference) resize the exemplar on the device: the same picture "
+                   "as the default path, bit for bit, from the reference's full-size bytes")
+    p.add_argument("--reference_box", type=float, nargs="+", default=None, metavar="N", help="(not in the reference) X0 Y0 X1 Y1 per --reference_path: "
+                   "the part of that image to take as the exemplar (Pillow's box, fractions allowed)")
+    p.add_argument("--reference_mask", type=str, nargs="+", default=None, metavar="PATH", help="(not in the reference) one image per --reference_path, "
+                   "of its size, white = the object: the exemplar is the object's bounding box")
+    p.add_argument("--reference_pad", type=float, default=0.0, metavar="F", help="with --reference_box / --reference_mask: grow the box by this "
+                   "fraction of its size on each side")
+    p.add_argument("--reference_square", action="store_true", help="with --reference_box / --reference_mask: grow the box's shorter side to the longer")
+    p.add_argument("--reference_fill", type=int, nargs=3, default=None, metavar=("R", "G", "B"), help="with --reference_mask: the colour of "
+                   "everything off the object")
     p.add_argument("--random_weights", action="store_true", help="name-seeded random weights instead of --ckpt")
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
@@ -133,6 +153,19 @@ def parse(argv=None):
             p.error(f"--reference_weight: {len(w)} weights for {len(refs)} --reference_path images")
         if any(not (x >= 0.0) or x == float("inf") for x in w) or not sum(w) > 0.0:
             p.error("--reference_weight: weights must be finite and >= 0 with a positive sum")
+    refs = opt.reference_path if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
+    if opt.reference_box is not None and len(opt.reference_box) != 4 * len(refs):
+        p.error(f"--reference_box: {len(opt.reference_box)} numbers for {len(refs)} --reference_path images (X0 Y0 X1 Y1 each)")
+    if opt.reference_mask is not None and len(opt.reference_mask) != len(refs):
+        p.error(f"--reference_mask: {len(opt.reference_mask)} masks for {len(refs)} --reference_path images")
+    if opt.reference_box is not None and opt.reference_mask is not None and opt.reference_fill is None:
+        p.error("--reference_box and --reference_mask both place the crop: name one (with --reference_fill the mask paints the background and goes with a box)")
+    if opt.reference_fill is not None and (opt.reference_mask is None or any(not 0 <= v <= 255 for v in opt.reference_fill)):
+        p.error("--reference_fill: three bytes R G B, with --reference_mask (it colours what is off the object)")
+    if not (0.0 <= opt.reference_pad < float("inf")):
+        p.error("--reference_pad must be finite and >= 0")
+    if (opt.reference_pad != 0.0 or opt.reference_square) and opt.reference_box is None and opt.reference_mask is None:
+        p.error("--reference_pad / --reference_square grow a box: they need --reference_box or --reference_mask")
     if not (opt.context >= 0.0) or opt.context == float("inf") or opt.feather < 0 or opt.feather > 2047:
         p.error("--context must be finite and >= 0, --feather an integer in 0 .. 2047")
     if not (-2047.0 <= opt.mask_grow <= 2047.0) or not (0.0 <= opt.mask_close <= 2047.0) or not (0.0 <= opt.mask_open <= 2047.0):
@@ -192,6 +225,33 @@ def load_regions(paths, size, device, window=None):
     return torch.cat(maps, 1).clamp_(0.0, 1.0)
 
 
+def reference_on_device(opt) -> bool:
+    """True when the exemplar is to be cut on the device: --reference_on_device, or any flag that crops it."""
+    return bool(opt.reference_on_device or opt.reference_box is not None or opt.reference_mask is not None or opt.reference_pad != 0.0
+                or opt.reference_square or opt.reference_fill is not None)
+
+
+def cut_references(opt, refs, device):
+    """The exemplars of the --reference_* flags: one fp32 [1, 3, 224, 224] per --reference_path, cut on the device
+    (pbe_amd.preprocess.load_reference_device), and <outdir>/reference_crops/<stem>_ref<k>.png with the bytes of each.  None on the
+    default path, which then runs as it always did."""
+    if not reference_on_device(opt):
+        return None
+    from PIL import Image
+    from pbe_amd import preprocess
+    d, stem = os.path.join(opt.outdir, "reference_crops"), os.path.basename(opt.image_path)[:-4]
+    os.makedirs(d, exist_ok=True)
+    planes = []
+    for k, path in enumerate(refs):
+        box = None if opt.reference_box is None else tuple(opt.reference_box[4 * k:4 * k + 4])
+        e = preprocess.load_reference_device(path, device, box=box, mask_path=None if opt.reference_mask is None else opt.reference_mask[k],
+                                             pad=opt.reference_pad, square=opt.reference_square, fill=opt.reference_fill)
+        Image.fromarray(e["u8"].cpu().numpy()).save(os.path.join(d, f"{stem}_ref{k}.png"))
+        print(f"reference {k}: box (x0, y0, x1, y1) = {e['box']} of {path}")
+        planes.append(e["ref"])
+    return planes
+
+
 def save_reference_maps(outdir, stem, seed, ref_maps, H, W):
     """ref_maps fp32 [B, K, h, w] (ContextMaps.result) -> <outdir>/reference_maps/<stem>_<seed>[_<i>]_ref<j>.png, 8-bit grayscale
     round(255 * map) at the picture size (pipeline.ref_maps_u8: resized on the device).  Returns the paths, sample-major."""
@@ -243,7 +303,11 @@ def run_per_hole(opt, model, device, refs):
     N = len(pbe_window.plan_holes(table, picture_mask.shape, size, opt.context, opt.feather, opt.max_holes))
     if opt.reference_per_hole and len(refs) != N:
         raise SystemExit(f"--reference_per_hole: {len(refs)} --reference_path images for {N} holes")
-    planes = [preprocess.load_triple_device(opt.image_path, opt.mask_path, r, device)["ref"][0] for r in refs]        # each [3, 224, 224]
+    cut = cut_references(opt, refs, device)
+    if cut is not None:
+        planes = [c[0] for c in cut]
+    else:
+        planes = [preprocess.load_triple_device(opt.image_path, opt.mask_path, r, device)["ref"][0] for r in refs]    # each [3, 224, 224]
     kw = {}
     if opt.reference_per_hole:
         ref = torch.stack(planes)                                                      # [N, 3, 224, 224]: exemplar i for hole i
@@ -336,9 +400,12 @@ def main(argv=None):
             t = preprocess.load_triple_device(opt.image_path, opt.mask_path, refs[0], device, mask_shape=mask_shape)   # uint8 up, arithmetic on the GPU
         filename = os.path.basename(opt.image_path)
         test_model_kwargs = {"inpaint_mask": t["mask"], "inpaint_image": t["inpaint"]}
+        cut = cut_references(opt, refs, device)                                        # None on the default path
+        if cut is not None:
+            t["ref"] = cut[0]                                                          # (the triple loader's host-resized exemplar is dropped)
         ref = t["ref"]
         if len(refs) > 1:                                                              # several exemplars: [1, K, 3, 224, 224] -> K context tokens
-            more = [preprocess.load_triple_device(opt.image_path, opt.mask_path, r, device)["ref"] for r in refs[1:]]
+            more = cut[1:] if cut is not None else [preprocess.load_triple_device(opt.image_path, opt.mask_path, r, device)["ref"] for r in refs[1:]]
             ref = torch.stack([ref] + more, 1)
         uc = model.learnable_vector if opt.scale != 1.0 else None
         c = model.proj_out(model.get_learned_conditioning(ref))                      # scripts/inference.py:326-327
