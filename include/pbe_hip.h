@@ -661,6 +661,21 @@ int pbe_resample_v_u8(const void* src, const void* mask, const uint8_t* fill3, v
 int32_t pbe_mask_box_bands(int32_t Hs);
 int pbe_mask_box_i32(const void* mask, int32_t* table, int32_t Hs, int32_t Ws, int32_t bands, pbe_stream_t stream);
 
+/* Noise as a function of per-sample seeds (csrc/noise.hip; ABI 8 additive): Philox4x32-10 as published (Salmon et al., SC'11; multipliers
+ * 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, 10 rounds).  For sample b and element e of its flat array:
+ *   key = (seed lo32, seed hi32), seeds[b] read as unsigned 64 bits;  counter = (e / 4, sub[b], stream_id lo32, stream_id hi32).
+ * pbe_philox_u32        out u32 [B, n_words]: word w of a sample is x[w % 4] of counter w / 4.
+ * pbe_randn_philox_f32  out fp32 [B, n] = a * out + b * z.  From the words of counter q = e / 4: u = ((x0 >> 8) + 1) 2^-24 in (0, 1],
+ *                       v = (x1 >> 8) 2^-24 in [0, 1), r = sqrtf(-2 logf(u)), (s, c) = sincospif(2 v); elements 4q, 4q + 1 are r c, r s and
+ *                       4q + 2, 4q + 3 the same from (x2, x3).  With a == 0 out is never read (NaN in it does not come through) and the
+ *                       result is b * z; otherwise it is fmaf(b, z, a * out): with a == 1 the bits of pbe_axpy_f32 on a plain draw.
+ * seeds i64 [B] and sub i32 [B] (NULL: 0) are device arrays.  A value depends on (seed, sub, stream_id, e) alone: not on B, the sample's
+ * place in the batch, n, or the alignment of out (4 bytes is enough).  No state, no atomics, no synchronisation (capturable); every
+ * element is written exactly once.  B <= 65535, n <= 2^32 - 4. */
+int pbe_philox_u32(uint32_t* out, const int64_t* seeds, const int32_t* sub, int32_t B, int64_t n_words, uint64_t stream_id, pbe_stream_t stream);
+int pbe_randn_philox_f32(float* out, const int64_t* seeds, const int32_t* sub, int32_t B, int64_t n, uint64_t stream_id, float a, float b,
+                         pbe_stream_t stream);
+
 /* pbe_tune— developer knobs for A/B runs in one process (never needed for correctness):
  * key 1: force an implicit-GEMM tile config index (-1 = heuristic); key 2: allow split-K (0/1);
  * key 3: attention queries-per-wave factor (0 = heuristic, 1, 2); key 4: ping-pong main loop of the halo-resident conv tiles (0/1);

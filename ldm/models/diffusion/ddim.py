@@ -26,8 +26,9 @@ class DDIMSampler(PLMSSampler):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
                eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, disable_tqdm=True,
-               conditioning_weights=None, conditioning_regions=None, conditioning_maps=None, **kwargs):
-        """conditioning_weights: per-sample exemplar weights [batch_size, K] as in PLMSSampler.sample, or None; conditioning_regions:
+               conditioning_weights=None, conditioning_regions=None, conditioning_maps=None, seeds=None, seed_sub=None, **kwargs):
+        """seeds / seed_sub: per-sample noise seeds as in PLMSSampler.sample; with eta > 0 the sigma_t term of each step is added by
+        SeededNoise.add_noise_ (one launch, no temporary).  conditioning_weights: per-sample exemplar weights [batch_size, K] as in PLMSSampler.sample, or None; conditioning_regions:
         region maps [batch_size, K, Hr, Wr] as there, or None; conditioning_maps: an attention.ContextMaps that collects the run's
         attribution maps (the conditional half of every U-Net call) as there, or None."""
         if conditioning is None:
@@ -38,11 +39,15 @@ class DDIMSampler(PLMSSampler):
             raise PbeError("DDIMSampler: mask and x0 go together (ddim.py:178-181)")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
-        return self.ddim_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
-                                  log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0, temperature=temperature,
-                                  conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
-                                  conditioning_maps=conditioning_maps, **kwargs)
+        try:
+            x_T = self._seed_run(seeds, seed_sub, x_T, (batch_size, C, H, W))
+            return self.ddim_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
+                                      log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
+                                      unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0, temperature=temperature,
+                                      conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
+                                      conditioning_maps=conditioning_maps, **kwargs)
+        finally:
+            self._seeded = None
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100, unconditional_guidance_scale=1.,
@@ -84,7 +89,9 @@ class DDIMSampler(PLMSSampler):
             if sigma != 0.0:                                  # dir_xt = sqrt(1 - a_prev - sigma_t^2) e_t (ddim.py:234)
                 coef[7] = float(np.sqrt(1.0 - float(self.ddim_alphas_prev[index]) - sigma * sigma))
             img, pred_x0, _ = ops.plms_update(eps, dup, float(unconditional_guidance_scale), img, [], coef, want_e_t=False)
-            if sigma != 0.0:                                  # + sigma_t * noise_like(...) * temperature (ddim.py:235-238)
+            if sigma != 0.0 and self._seeded is not None:     # the same term, drawn and added by one kernel
+                self._seeded.add_noise_(img, sigma * float(temperature))
+            elif sigma != 0.0:                                # + sigma_t * noise_like(...) * temperature (ddim.py:235-238)
                 ops.axpy_(img, sigma * float(temperature), self.noise_like(tuple(img.shape), img.device).float().contiguous())
             if callback:
                 callback(i)

@@ -57,9 +57,9 @@ class DPMSolverSampler(PLMSSampler):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
                eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, disable_tqdm=True,
-               conditioning_weights=None, conditioning_regions=None, conditioning_maps=None, order=2, **kwargs):
-        """The arguments of DDIMSampler.sample (conditioning_weights / conditioning_regions / conditioning_maps as in PLMSSampler.sample)
-        plus order: 2 = DPM-Solver++(2M), 1 = its first order, which is DDIM with eta = 0.  eta must be 0."""
+               conditioning_weights=None, conditioning_regions=None, conditioning_maps=None, order=2, seeds=None, seed_sub=None, **kwargs):
+        """The arguments of DDIMSampler.sample (conditioning_weights / conditioning_regions / conditioning_maps / seeds / seed_sub as in
+        PLMSSampler.sample) plus order: 2 = DPM-Solver++(2M), 1 = its first order, which is DDIM with eta = 0.  eta must be 0."""
         if conditioning is None:
             raise PbeError("DPMSolverSampler.sample: conditioning is required")
         if quantize_x0 or score_corrector is not None or noise_dropout != 0.:
@@ -72,11 +72,15 @@ class DPMSolverSampler(PLMSSampler):
             raise PbeError(f"DPMSolverSampler: order must be 1 or 2, got {order!r}")
         self.make_schedule(ddim_num_steps=S, ddim_eta=0., verbose=verbose)
         C, H, W = shape
-        return self.dpm_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
-                                 log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                 unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
-                                 conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
-                                 conditioning_maps=conditioning_maps, order=order, **kwargs)
+        try:
+            x_T = self._seed_run(seeds, seed_sub, x_T, (batch_size, C, H, W))
+            return self.dpm_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
+                                     log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
+                                     unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
+                                     conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
+                                     conditioning_maps=conditioning_maps, order=order, **kwargs)
+        finally:
+            self._seeded = None
 
     @torch.no_grad()
     def dpm_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100, unconditional_guidance_scale=1.,

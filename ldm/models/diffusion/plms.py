@@ -101,6 +101,8 @@ def guidance_maps(maps, cond, b, device):
 
 
 class PLMSSampler(object):
+    _seeded = None                    # a pbe_amd.noise.SeededNoise for the length of one sample(seeds=...) call, else None
+
     def __init__(self, model, schedule="linear", **kwargs):
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
@@ -113,6 +115,22 @@ class PLMSSampler(object):
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
+
+    def _seed_run(self, seeds, seed_sub, x_T, shape):
+        """sample(seeds=...): the start latent and, until the call returns, every noise draw come from one pbe_amd.noise.SeededNoise
+        (sample i a function of seeds[i] alone; the stream plan is that module's docstring).  Without seeds: x_T as it came, no launch."""
+        if seeds is None:
+            if seed_sub is not None:
+                raise PbeError("sample(): seed_sub names substreams of seeds, which are missing")
+            return x_T
+        if x_T is not None:
+            raise PbeError("sample(): seeds and x_T both given - the start latent is either drawn from the seeds or handed in")
+        from pbe_amd.noise import SeededNoise
+        self._seeded = SeededNoise(seeds, seed_sub, device=self.model.betas.device)
+        return self._seeded.x_T(shape)
+
+    def _noise(self, shape, device):
+        return self.noise_like(shape, device) if self._seeded is None else self._seeded.noise_like(shape, device)
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=True):
         if ddim_eta != 0:
@@ -134,8 +152,10 @@ class PLMSSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
                eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, conditioning_weights=None,
-               conditioning_regions=None, conditioning_maps=None, **kwargs):
-        """conditioning_weights: per-sample exemplar weights [batch_size, K] over conditioning's K tokens (>= 0, positive sum per sample;
+               conditioning_regions=None, conditioning_maps=None, seeds=None, seed_sub=None, **kwargs):
+        """seeds: per-sample noise seeds (an int64 tensor [batch_size] on the GPU or ints in [0, 2^64)), seed_sub their substreams or
+        None: x_T (which must then be None) and the q_sample noise are drawn by pbe_amd.noise.SeededNoise, sample i from seeds[i] alone.
+        conditioning_weights: per-sample exemplar weights [batch_size, K] over conditioning's K tokens (>= 0, positive sum per sample;
         0 = token absent, so a ragged batch is padded to one K), or None: every token counts once.
         conditioning_regions: per-sample, per-token region maps [batch_size, K, Hr, Wr] >= 0 (regional exemplars: where each token
         applies; every transformer level's grid must divide Hr x Wr), or None: every token applies everywhere.
@@ -153,11 +173,15 @@ class PLMSSampler(object):
             raise PbeError("PLMSSampler: mask and x0 go together (plms.py:150-153)")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
-        return self.plms_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
-                                  log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
-                                  conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
-                                  conditioning_maps=conditioning_maps, **kwargs)
+        try:
+            x_T = self._seed_run(seeds, seed_sub, x_T, (batch_size, C, H, W))
+            return self.plms_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
+                                      log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
+                                      unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
+                                      conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
+                                      conditioning_maps=conditioning_maps, **kwargs)
+        finally:
+            self._seeded = None
 
     # ---- one U-Net evaluation with guidance (plms.py:181-195) -----------------------------------
     def _eps(self, x, step, ctx, z_inp, msk, dup, ctx_w=None, ctx_r=None, ctx_m=None):
@@ -199,7 +223,7 @@ class PLMSSampler(object):
     def _blend_known(self, img, x0, mask, step):
         """img_orig = q_sample(x0, ts); img = img_orig * mask + (1 - mask) * img (plms.py:150-153), one kernel."""
         ac = float(self.model.alphas_cumprod[int(step)])
-        return ops.qsample_blend(x0, self.noise_like(tuple(x0.shape), x0.device).float(), mask, img, math.sqrt(ac), math.sqrt(1.0 - ac))
+        return ops.qsample_blend(x0, self._noise(tuple(x0.shape), x0.device).float(), mask, img, math.sqrt(ac), math.sqrt(1.0 - ac))
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, callback=None, timesteps=None, img_callback=None, log_every_t=100,

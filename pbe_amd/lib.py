@@ -142,6 +142,8 @@ SYMBOLS = {
     "pbe_resample_v_u8": (c_i32, [c_vp, c_vp, C.POINTER(C.c_uint8), c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, C.POINTER(c_f32), C.POINTER(c_f32), c_vp]),
     "pbe_mask_box_bands": (c_i32, [c_i32]),
     "pbe_mask_box_i32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "pbe_philox_u32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, C.c_uint64, c_vp]),
+    "pbe_randn_philox_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, C.c_uint64, c_f32, c_f32, c_vp]),
     "pbe_tune": (c_i32, [c_i32, c_i32]),
     "pbe_prof_enable": (c_i32, [c_i32]),
     "pbe_prof_reset": (c_i32, []),
@@ -153,7 +155,7 @@ _lib = None
 _lock = threading.Lock()
 
 SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_astat.hip", "attention.hip", "attention_mx8.hip", "ctx_attention.hip", "norm.hip",
-           "elementwise.hip", "window.hip", "holes.hip", "maskshape.hip", "tone.hip", "tone_field.hip", "exemplar.hip"]
+           "elementwise.hip", "window.hip", "holes.hip", "maskshape.hip", "tone.hip", "tone_field.hip", "exemplar.hip", "noise.hip"]
 HASHED = [os.path.join("csrc", f) for f in SOURCES] + [os.path.join("csrc", "common.h"), os.path.join("csrc", "igemm_kernel.h"), os.path.join("csrc", "tone_bytes.h"), os.path.join("csrc", "u8_norm.h"),
                                                          os.path.join("..", "include", "pbe_hip.h"), "build.py"]
 

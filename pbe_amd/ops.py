@@ -1072,6 +1072,107 @@ def axpy_(y: torch.Tensor, a: float, x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+# ---- noise as a function of per-sample seeds (csrc/noise.hip; the stream plan lives in pbe_amd.noise) ----
+def seed_words(seeds) -> list:
+    """Python ints in [0, 2^64) -> the int64 values that hold them (two's complement at and above 2^63).  Anything else raises."""
+    if isinstance(seeds, (str, bytes)) or not hasattr(seeds, "__iter__"):
+        raise _l.PbeError(f"seeds: expected an int64 tensor [B] on the GPU or a sequence of ints in [0, 2^64), got {type(seeds).__name__}")
+    out = []
+    for s in seeds:
+        if isinstance(s, bool) or not isinstance(s, int):
+            raise _l.PbeError(f"seeds: {s!r} is not an int (a seed is an integer in [0, 2^64))")
+        if not 0 <= s < 1 << 64:
+            raise _l.PbeError(f"seeds: {s} is outside [0, 2^64)")
+        out.append(s - (1 << 64) if s >= 1 << 63 else s)
+    return out
+
+
+def seed_tensor(seeds, B: Optional[int], device=None) -> torch.Tensor:
+    """seeds (an int64 tensor [B] on the GPU, or a sequence of Python ints in [0, 2^64)) -> a contiguous int64 [B] tensor on `device`
+    (None: the current GPU; a tensor stays where it is)."""
+    if isinstance(seeds, torch.Tensor):
+        _req(seeds, torch.int64, "seeds")
+        if seeds.dim() != 1:
+            raise _l.PbeError(f"seeds: expected shape [B], got {tuple(seeds.shape)}")
+        t = seeds.contiguous()
+    else:
+        words = seed_words(seeds)                      # validated before any device is touched
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise _l.PbeError("seeds: the noise is drawn on the GPU (the HIP path has no CPU fallback)")
+        t = torch.tensor(words, dtype=torch.int64, device=device)
+    if B is not None and t.numel() != B:
+        raise _l.PbeError(f"seeds: {t.numel()} seeds for a batch of {B}")
+    return t
+
+
+def sub_tensor(sub, B: int, device) -> Optional[torch.Tensor]:
+    """sub (None, an int32 tensor [B] on the GPU, or a sequence of ints in [0, 2^31)) -> None or a contiguous int32 [B] tensor."""
+    if sub is None:
+        return None
+    if isinstance(sub, torch.Tensor):
+        t = _req(sub, torch.int32, "sub").contiguous()
+    else:
+        vals = list(sub)
+        if any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 31 for v in vals):
+            raise _l.PbeError(f"sub: expected ints in [0, 2^31), got {vals!r}")
+        t = torch.tensor(vals, dtype=torch.int32, device=device)
+    if t.dim() != 1 or t.numel() != B:
+        raise _l.PbeError(f"sub: expected {B} values, got shape {tuple(t.shape)}")
+    return t
+
+
+def _stream_id(stream) -> int:
+    if isinstance(stream, bool) or not isinstance(stream, int) or not 0 <= stream < 1 << 64:
+        raise _l.PbeError(f"stream: expected an int in [0, 2^64), got {stream!r}")
+    return stream
+
+
+def philox_u32(seeds, n_words: int, stream: int = 0, sub=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The raw Philox4x32-10 words: int32 [B, n_words] holding the unsigned words' bits (torch has no uint32 arithmetic; view as
+    numpy uint32 to compare).  Word w of sample b is x[w % 4] of counter (w // 4, sub[b], stream lo32, stream hi32) under key seeds[b]."""
+    sd = seed_tensor(seeds, None, out.device if isinstance(out, torch.Tensor) else None)
+    B, n_words = sd.numel(), int(n_words)
+    sb = sub_tensor(sub, B, sd.device)
+    if B < 1 or n_words < 1:
+        raise _l.PbeError(f"philox_u32: nothing to draw ({B} samples of {n_words} words)")
+    if out is None:
+        out = torch.empty((B, n_words), dtype=torch.int32, device=sd.device)
+    elif out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (B, n_words) or out.device != sd.device:
+        raise _l.PbeError(f"philox_u32: out must be a contiguous int32 [{B}, {n_words}] tensor on the seeds' device")
+    _l.check(_l.load().pbe_philox_u32(_p(out), _p(sd), _p(sb), B, n_words, _stream_id(stream), _stream()), "pbe_philox_u32")
+    return out
+
+
+def randn_seeded(seeds, shape, stream: int, sub=None, out: Optional[torch.Tensor] = None, a: float = 0.0, b: float = 1.0) -> torch.Tensor:
+    """out = a * out + b * z with z standard normal, fp32, of the full shape [B, ...]: sample i is a pure function of (seeds[i], sub[i],
+    stream, element index) - Philox4x32-10 and Box-Muller as include/pbe_hip.h states them - whatever B, the sample's place in the batch
+    or the device.  seeds: an int64 tensor [B] on the GPU or a sequence of Python ints in [0, 2^64) (at and above 2^63: their two's
+    complement); sub: None (0), an int32 tensor [B] or ints in [0, 2^31).  a == 0 never reads out (a fresh tensor unless given); a != 0
+    needs out.  One launch, no temporary, no generator state."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) < 1 or any(s < 1 for s in shape):
+        raise _l.PbeError(f"randn_seeded: shape must be [B, ...] with positive sizes, got {shape}")
+    B = shape[0]
+    n = 1
+    for s in shape[1:]:
+        n *= s
+    if out is not None:
+        _f(out, "randn_seeded out")
+        if tuple(out.shape) != shape or not out.is_contiguous():
+            raise _l.PbeError(f"randn_seeded: out must be a contiguous fp32 tensor of shape {shape}, got {tuple(out.shape)}")
+    elif float(a) != 0.0:
+        raise _l.PbeError("randn_seeded: a != 0 accumulates into out, which is missing")
+    sd = seed_tensor(seeds, B, None if out is None else out.device)
+    if out is not None and sd.device != out.device:
+        raise _l.PbeError(f"randn_seeded: seeds on {sd.device}, out on {out.device}")
+    sb = sub_tensor(sub, B, sd.device)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=sd.device)
+    _l.check(_l.load().pbe_randn_philox_f32(_p(out), _p(sd), _p(sb), B, n, _stream_id(stream), float(a), float(b), _stream()), "pbe_randn_philox_f32")
+    return out
+
+
 def qsample_blend(x0: torch.Tensor, noise: torch.Tensor, mask: torch.Tensor, img: torch.Tensor, sqrt_ac: float, sqrt_1m_ac: float) -> torch.Tensor:
     """img_orig = q_sample(x0, t); img_orig * mask + (1 - mask) * img (plms.py:150-153, ddim.py:178-181), fp32 NCHW."""
     for t, n in ((x0, "x0"), (noise, "noise"), (mask, "mask"), (img, "img")):

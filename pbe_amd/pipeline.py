@@ -68,7 +68,7 @@ def resize_mask(mask: torch.Tensor, size, antialias: bool = True) -> torch.Tenso
 def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *, steps: int = 50, scale: float = 5.0,
             x_T: Optional[torch.Tensor] = None, post_eps: Optional[torch.Tensor] = None, sampler: str = "plms",
             antialias: bool = True, timings: Optional[Dict[str, float]] = None, ref_weights=None, ref_regions=None,
-            return_ref_maps: bool = False) -> Dict[str, torch.Tensor]:
+            return_ref_maps: bool = False, seeds=None, seed_sub=None) -> Dict[str, torch.Tensor]:
     """image [B,3,H,W] in [-1,1], mask [B,1,H,W] in {0,1} (1 = keep), ref [B,3,224,224] CLIP-normalised (or [B,K,3,224,224]: K
     exemplars per sample, with ref_weights [B, K] their non-negative weights or None and ref_regions [B, K, Hr, Wr] >= 0 where each of
     them applies - 1 = fully, 0 = not there; the latent grid and its halvings down to the coarsest attention level must divide
@@ -77,12 +77,23 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     return_ref_maps: also 'ref_maps' fp32 [B, K, h, w] on the latent grid - the share of cross-attention each exemplar received at each
     position, averaged over heads, blocks, sampler steps and levels (ldm.modules.attention.ContextMaps; K = 1: ones).  Collecting them
     sends every level through the fused cross-attention kernel: with ref_regions the picture is the one without return_ref_maps bit for
-    bit; without regions (and K > 1) it is the picture of blocks with ctx_fused_max_width = 1280, within the sampler tolerance of the default."""
+    bit; without regions (and K > 1) it is the picture of blocks with ctx_fused_max_width = 1280, within the sampler tolerance of the default.
+    seeds: one noise seed per sample (an int64 tensor [B] on the GPU or ints in [0, 2^64)), seed_sub their substreams (int32 [B] / ints
+    in [0, 2^31)) or None.  Then every draw of the call is made on the device by pbe_amd.noise (its docstring is the stream plan): the
+    posterior noise from STREAM_POST_EPS - no CPU draw, no upload -, x_T and the samplers' own draws from the sampler's SeededNoise;
+    sample i is a function of (seeds[i], seed_sub[i]) alone, whatever B is.  x_T and post_eps must then be None; the result gains 'seeds'
+    (the int64 tensor).  Without seeds nothing changes: the draws are torch's, as in the reference."""
     from ldm.models.diffusion.ddim import DDIMSampler
     from ldm.models.diffusion.plms import PLMSSampler
     dev = model.device
     image, mask, ref = image.to(dev).float(), mask.to(dev).float(), ref.to(dev).float()
     B = image.shape[0]
+    if seeds is None and seed_sub is not None:
+        raise PbeError("inpaint: seed_sub names substreams of seeds, which are missing")
+    if seeds is not None:
+        if x_T is not None or post_eps is not None:
+            raise PbeError("inpaint: seeds given together with x_T / post_eps - the noise is either drawn from the seeds or handed in")
+        seeds, seed_sub = ops.seed_tensor(seeds, B, dev), ops.sub_tensor(seed_sub, B, dev)
     ev = None
     if timings is not None:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
@@ -92,6 +103,10 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     if ev:
         ev[1].record()
     post = model.encode_first_stage(image * mask)                                        # inference.py:319,330
+    if seeds is not None and hasattr(post, "parameters") and not post.deterministic:
+        from .noise import SeededNoise
+        pb, ph, pw, _ = post.parameters.shape
+        post_eps = SeededNoise(seeds, seed_sub).post_eps((pb, post.z, ph, pw))
     z_inp = model.get_first_stage_encoding(post, noise=post_eps)                         # inference.py:331
     m_lat = resize_mask(mask, z_inp.shape[-2:], antialias)                               # inference.py:332
     if ev:
@@ -102,6 +117,8 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     else:
         smp = (PLMSSampler if sampler == "plms" else DDIMSampler)(model)
     more = {} if ref_regions is None else {"conditioning_regions": ref_regions}
+    if seeds is not None:
+        more["seeds"], more["seed_sub"] = seeds, seed_sub
     cm = None
     if return_ref_maps:
         from ldm.modules.attention import ContextMaps
@@ -121,6 +138,8 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
     out = {"image": img, "latent": z0, "c": c, "z_inpaint": z_inp, "mask_lat": m_lat}
     if cm is not None:
         out["ref_maps"] = cm.result(z_inp.shape[-2:])
+    if seeds is not None:
+        out["seeds"] = seeds
     return out
 
 
@@ -234,14 +253,14 @@ def match_tone_field(image: torch.Tensor, result: torch.Tensor, masks: Sequence[
     return summary, field, cells
 
 
-PER_WINDOW_KWARGS = ("x_T", "post_eps", "ref_weights", "ref_regions")       # the arguments of inpaint with a leading batch dimension
+PER_WINDOW_KWARGS = ("x_T", "post_eps", "ref_weights", "ref_regions", "seeds", "seed_sub")       # the arguments of inpaint with a leading batch dimension
 
 
 @torch.no_grad()
 def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], ref: torch.Tensor, *, size=(512, 512), context=0.5,
                   feather: int = 8, connectivity: int = 8, max_holes: int = 16, batch: Optional[int] = None, mask_shape: Optional[dict] = None,
                   tone: Optional[str] = None, tone_margin: int = 8, tone_gain_limit: float = 1.25, tone_cell: int = 8, tone_field_limit: float = 0.125,
-                  **inpaint_kwargs) -> Dict[str, object]:
+                  hole_seeds: Optional[Dict[int, int]] = None, **inpaint_kwargs) -> Dict[str, object]:
     """Inpaint every hole of a picture in a window of its own and paste them all back into one picture.  pictures / masks: as in
     inpaint_window (B samples).  Per sample the mask is labelled on the device (ops.mask_components at `connectivity`), the component
     boxes come back in one small read (ops.component_boxes) and pbe_amd.window.plan_holes groups the components whose blend zones could
@@ -261,6 +280,12 @@ def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch
     window fp32 [wh, ww]) and 'inputs' (window_inputs over the N windows).
     mask_shape: as in inpaint_window - each mask is shaped once (pbe_amd.window.shape_mask) before it is labelled, the holes are those
     of the shaped mask, and the result gains 'masks'.  `connectivity` here is the labelling's; the box stage has its own key.
+    seeds (through **inpaint_kwargs): B noise seeds, one per PICTURE - window g then draws with its picture's seed and sub = the raster
+    index of its group's first pixel + 1 (min(holes[g]['labels']) + 1: the labels of csrc/holes.hip), so a hole's noise is a function of
+    (picture seed, where the hole starts) and does not change with the other holes, with `batch` or with `max_holes` - or N seeds, one
+    per window, with sub = 0 (where B == N the seeds count per picture).  hole_seeds {g: seed} then gives window g a seed of its own with
+    sub = 0 - one hole re-rolled, the others keep their noise.  seed_sub is not an argument here.  Each holes[g] gains 'seed' and 'sub',
+    and the result 'seeds' as from inpaint.
     tone: as in inpaint_window, one map (or, with "field", one difference field: tone_cell, tone_field_limit) per WINDOW ('tone' and
     'tone_stats', or 'tone_field' and 'tone_cells', have N entries / rows, concatenated over the chunks; "field" ignores
     tone_gain_limit).  The selection comes from each window's OWN mask, as alpha does: another group's hole inside the window was a known pixel for the model
@@ -290,6 +315,29 @@ def inpaint_holes(model, pictures: Sequence[torch.Tensor], masks: Sequence[torch
         ref = ref if N == B and all(h["sample"] == k for k, h in enumerate(holes)) else ref[[h["sample"] for h in holes]]
     elif lead != N:
         raise PbeError(f"inpaint_holes: ref has leading size {lead}; expected {B} (one per sample) or {N} (one per hole)")
+    if inpaint_kwargs.get("seed_sub") is not None:
+        raise PbeError("inpaint_holes: seed_sub is derived from the holes (one seed per picture) or 0 (one seed per hole); do not pass it")
+    if hole_seeds and inpaint_kwargs.get("seeds") is None:
+        raise PbeError("inpaint_holes: hole_seeds overrides single holes of a seeded run; seeds is missing")
+    if inpaint_kwargs.get("seeds") is not None:
+        inpaint_kwargs = dict(inpaint_kwargs)
+        sd = inpaint_kwargs["seeds"]
+        sd = ops.seed_tensor(sd, None).tolist() if isinstance(sd, torch.Tensor) else ops.seed_words(sd)      # the int64 values (one small read)
+        if len(sd) == B:
+            sd, subs = [sd[h["sample"]] for h in holes], [min(h["labels"]) + 1 for h in holes]
+        elif len(sd) == N:
+            subs = [0] * N
+        else:
+            raise PbeError(f"inpaint_holes: {len(sd)} seeds; expected {B} (one per picture) or {N} (one per hole)")
+        for g, s_ in (hole_seeds or {}).items():
+            if isinstance(g, bool) or not isinstance(g, int) or not 0 <= g < N:
+                raise PbeError(f"inpaint_holes: hole_seeds names hole {g!r}; the mask has holes 0 .. {N - 1}")
+            sd[g], subs[g] = ops.seed_words([s_])[0], 0
+        for h, s_, u_ in zip(holes, sd, subs):
+            h["seed"], h["sub"] = s_ & ((1 << 64) - 1), u_
+        dev = pictures[0].device
+        inpaint_kwargs["seeds"] = torch.tensor(sd, dtype=torch.int64, device=dev)
+        inpaint_kwargs["seed_sub"] = torch.tensor(subs, dtype=torch.int32, device=dev)
     for k in PER_WINDOW_KWARGS:
         v = inpaint_kwargs.get(k)
         if v is not None and len(v) != N:

@@ -54,6 +54,15 @@ colour before the resize.  Any of them implies the device path.  The cut exempla
 `<outdir>/reference_crops/<stem>_ref<k>.png`.  All of it works with several references, `--reference_per_hole`, `--paste_back` and every
 sampler.
 
+`--seeds S [S ...]` (not in the reference) makes every picture a function of its own seed: all noise - the start code, the posterior
+noise, the samplers' own draws - comes from pbe_amd.noise (Philox4x32-10 keyed by the seed, drawn on the device), so a seed gives the
+same noise in any batch, on any device and with any torch.  A plain or `--paste_back` run becomes ONE batch with one variant of the
+triple per seed and writes the usual output tree once per seed, that seed in every file name.  With `--per_hole` each seed is one
+pipeline.inpaint_holes call with it as the picture's seed: a hole's noise is then a function of (seed, where the hole starts), and
+`--hole_seed INDEX SEED` (repeatable) re-rolls hole INDEX alone - the others keep their noise; a line per hole prints its (seed, sub).
+`--seeds` excludes `--fixed_code` and `--n_samples` above 1; `--seed` still seeds torch's generators and nothing else.
+Without `--seeds` every run writes the files it always wrote.
+
 Differences, all deliberate: the safety checker and the invisible watermark are dropped (the
 reference overwrites the checker's result, :350-351; both need hub downloads); `--ckpt ""` or
 `--random_weights` runs with name-seeded random weights (no checkpoint exists offline);
@@ -139,6 +148,10 @@ def parse(argv=None):
     p.add_argument("--reference_square", action="store_true", help="with --reference_box / --reference_mask: grow the box's shorter side to the longer")
     p.add_argument("--reference_fill", type=int, nargs=3, default=None, metavar=("R", "G", "B"), help="with --reference_mask: the colour of "
                    "everything off the object")
+    p.add_argument("--seeds", type=int, nargs="+", default=None, metavar="S", help="(not in the reference) one variant of the triple per seed, in one "
+                   "batch, all noise drawn on the device as a function of that seed (pbe_amd.noise); the output tree is written once per seed")
+    p.add_argument("--hole_seed", type=int, nargs=2, action="append", default=None, metavar=("INDEX", "SEED"), help="with --per_hole --seeds "
+                   "(repeatable): hole INDEX draws from SEED instead; the other holes keep their noise")
     p.add_argument("--random_weights", action="store_true", help="name-seeded random weights instead of --ckpt")
     p.add_argument("--dump_tensors", type=str, default="", help="(not in the reference) save the start code, the posterior noise and the "
                    "intermediate tensors of this run to an .npz: what a CPU replay needs to reproduce the run without the device RNG")
@@ -147,6 +160,18 @@ def parse(argv=None):
         p.error("--plms and --dpm_solver are mutually exclusive: name one sampler")
     if opt.dpm_solver and opt.ddim_eta != 0.0:
         p.error("--dpm_solver runs with --ddim_eta 0 (the stochastic variant is not built)")
+    if opt.seeds is not None:
+        if opt.fixed_code:
+            raise SystemExit("--seeds draws the start code from each seed: --fixed_code has nothing to fix")
+        if opt.n_samples != 1:
+            raise SystemExit(f"--seeds runs one sample per seed: --n_samples {opt.n_samples} is not 1")
+        if any(not 0 <= v < 1 << 64 for v in opt.seeds) or len(set(opt.seeds)) != len(opt.seeds):
+            p.error("--seeds: distinct integers in [0, 2^64)")
+    if opt.hole_seed is not None:
+        if opt.seeds is None or not opt.per_hole:
+            raise SystemExit("--hole_seed re-rolls one hole of a --per_hole --seeds run")
+        if any(i < 0 or not 0 <= v < 1 << 64 for i, v in opt.hole_seed) or len({i for i, _ in opt.hole_seed}) != len(opt.hole_seed):
+            p.error("--hole_seed: INDEX >= 0 (each hole once) and SEED in [0, 2^64)")
     if opt.reference_weight is not None:
         w, refs = opt.reference_weight, opt.reference_path if isinstance(opt.reference_path, (list, tuple)) else [opt.reference_path]
         if len(w) != len(refs):
@@ -316,9 +341,22 @@ def run_per_hole(opt, model, device, refs):
         if opt.reference_weight is not None:
             kw["ref_weights"] = torch.tensor([opt.reference_weight], dtype=torch.float64).expand(N, -1).contiguous()
     shape = (N, opt.C, opt.H // opt.f, opt.W // opt.f)
+    if opt.seeds is not None:                                                          # one call per seed, all noise from pbe_amd.noise
+        if any(i >= N for i, _ in opt.hole_seed or []):
+            raise SystemExit(f"--hole_seed: the mask has holes 0 .. {N - 1}")
+        return torch.cat([_per_hole_call(opt, model, picture, picture_mask, ref, planes, N, s,
+                                         dict(kw, seeds=[s], hole_seeds={i: v for i, v in opt.hole_seed or []})) for s in opt.seeds])
     if opt.fixed_code:
         kw["x_T"] = torch.randn(shape, device=device, generator=torch.Generator(device=device).manual_seed(opt.seed))
     kw["post_eps"] = torch.randn(shape, generator=torch.Generator().manual_seed(opt.seed)).to(device)
+    return _per_hole_call(opt, model, picture, picture_mask, ref, planes, N, opt.seed, kw)
+
+
+def _per_hole_call(opt, model, picture, picture_mask, ref, planes, N, tag, kw):
+    """One pipeline.inpaint_holes call of run_per_hole and its files, `tag` (the seed) in every name."""
+    from PIL import Image
+    from pbe_amd import pipeline, preprocess
+    size = (opt.H, opt.W)
     out = pipeline.inpaint_holes(model, [picture], [picture_mask], ref, size=size, context=opt.context, feather=opt.feather, max_holes=opt.max_holes,
                                  steps=opt.ddim_steps, scale=opt.scale, sampler="dpm" if opt.dpm_solver else ("plms" if opt.plms else "ddim"),
                                  **({} if opt.match_tone is None else {"tone": opt.match_tone, "tone_margin": opt.tone_margin}),
@@ -328,13 +366,14 @@ def run_per_hole(opt, model, device, refs):
         for i in range(N):
             t = {k: out["inputs"][k][i:i + 1] for k in ("image", "mask", "inpaint")}
             t["ref"] = (ref[i] if opt.reference_per_hole else planes[0])[None]
-            preprocess.save_outputs_device(opt.outdir, f"{stem}_hole{i}", opt.seed, t, out["image"][i], opt.H, opt.W)
+            preprocess.save_outputs_device(opt.outdir, f"{stem}_hole{i}", tag, t, out["image"][i], opt.H, opt.W)
     os.makedirs(os.path.join(opt.outdir, "pasted"), exist_ok=True)
-    Image.fromarray(out["pictures"][0].cpu().numpy()).save(os.path.join(opt.outdir, "pasted", f"{stem}_{opt.seed}.png"))
+    Image.fromarray(out["pictures"][0].cpu().numpy()).save(os.path.join(opt.outdir, "pasted", f"{stem}_{tag}.png"))
     if opt.match_tone is not None:
-        report_tone(opt.outdir, stem, opt.seed, out["tone"])
+        report_tone(opt.outdir, stem, tag, out["tone"])
     for i, h in enumerate(out["holes"]):
-        print(f"hole {i}: {h['area']} pixels in rows {h['box'][0]} .. {h['box'][1]}, columns {h['box'][2]} .. {h['box'][3]}; window {h['window']}")
+        print(f"hole {i}: {h['area']} pixels in rows {h['box'][0]} .. {h['box'][1]}, columns {h['box'][2]} .. {h['box'][3]}; window {h['window']}"
+              + (f"; noise (seed, sub) = ({h['seed']}, {h['sub']})" if "seed" in h else ""))
     return out["image"].cpu()
 
 
@@ -409,15 +448,31 @@ def main(argv=None):
             ref = torch.stack([ref] + more, 1)
         uc = model.learnable_vector if opt.scale != 1.0 else None
         c = model.proj_out(model.get_learned_conditioning(ref))                      # scripts/inference.py:326-327
+        nb = opt.n_samples
+        if opt.seeds is not None:                                                      # one variant per seed: the triple's tensors, repeated
+            nb = len(opt.seeds)
+            c = c.expand(nb, -1, -1).contiguous()
         cw = None
         if opt.reference_weight is not None:                                           # one weight per exemplar token, the same for every sample
             cw = torch.tensor([opt.reference_weight], dtype=torch.float64).expand(c.shape[0], -1).contiguous()
         post = model.encode_first_stage(test_model_kwargs["inpaint_image"])
         pb, ph, pw, _ = post.parameters.shape
         post_eps = torch.randn((pb, post.z, ph, pw)) if opt.dump_tensors else None   # the CPU draw DiagonalGaussianDistribution.sample() makes itself
-        z_inpaint = model.get_first_stage_encoding(post, noise=None if post_eps is None else post_eps.to(device))
+        if opt.seeds is not None:                                                      # encoded once; each variant samples the posterior with its own noise
+            from pbe_amd.noise import SeededNoise
+            post = type(post)(post.parameters.expand(nb, -1, -1, -1).contiguous(), post.deterministic)
+            eps = SeededNoise(opt.seeds, device=device).post_eps((nb, post.z, ph, pw))
+            post_eps = eps.cpu() if opt.dump_tensors else None
+            z_inpaint = model.get_first_stage_encoding(post, noise=eps)
+        else:
+            z_inpaint = model.get_first_stage_encoding(post, noise=None if post_eps is None else post_eps.to(device))
         test_model_kwargs["inpaint_image"] = z_inpaint
         test_model_kwargs["inpaint_mask"] = pipeline.resize_mask(test_model_kwargs["inpaint_mask"], z_inpaint.shape[-2:])
+        if opt.seeds is not None:
+            test_model_kwargs["inpaint_mask"] = test_model_kwargs["inpaint_mask"].expand(nb, -1, -1, -1).contiguous()
+            extra_seeds = {"seeds": list(opt.seeds)}
+        else:
+            extra_seeds = {}
         cr, extra = None, {}
         if opt.reference_region is not None:                                           # one map per exemplar token, the same for every sample
             cr = load_regions(opt.reference_region, z_inpaint.shape[-2:], device, win).expand(c.shape[0], -1, -1, -1).contiguous()
@@ -427,13 +482,14 @@ def main(argv=None):
             from ldm.modules.attention import ContextMaps
             cm = extra["conditioning_maps"] = ContextMaps()
         shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
-        samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=opt.n_samples, shape=shape, verbose=False,
+        samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=nb, shape=shape, verbose=False,
                                     unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc, eta=opt.ddim_eta,
-                                    x_T=start_code, test_model_kwargs=test_model_kwargs, conditioning_weights=cw, **extra)
+                                    x_T=start_code, test_model_kwargs=test_model_kwargs, conditioning_weights=cw, **extra, **extra_seeds)
         xd = ops.image_post(model.decode_first_stage_nhwc(samples))                  # clamp((x+1)/2, 0, 1), still on the GPU
+        tags = [opt.seed] * xd.shape[0] if opt.seeds is None else list(opt.seeds)      # what names sample i's files
         if not opt.skip_save:
             for i in range(xd.shape[0]):
-                paths = preprocess.save_outputs_device(opt.outdir, filename[:-4], opt.seed, t, xd[i], opt.H, opt.W)
+                paths = preprocess.save_outputs_device(opt.outdir, filename[:-4], tags[i], t, xd[i], opt.H, opt.W)
         if win is not None:                                                            # (an explicit request: written with --skip_save too)
             from PIL import Image
             os.makedirs(os.path.join(opt.outdir, "pasted"), exist_ok=True)
@@ -454,16 +510,26 @@ def main(argv=None):
                     pasted = ops.paste_window(xd[i].contiguous(), alpha, picture.clone(), win, field=fields[i], cell=opt.tone_cell)
                 else:
                     pasted = ops.paste_window(xd[i].contiguous(), alpha, picture.clone(), win, tone=maps[i])
-                Image.fromarray(pasted.cpu().numpy()).save(os.path.join(opt.outdir, "pasted", f"{filename[:-4]}_{opt.seed}.png"))
-            if opt.match_tone is not None:
+                Image.fromarray(pasted.cpu().numpy()).save(os.path.join(opt.outdir, "pasted", f"{filename[:-4]}_{tags[i]}.png"))
+            if opt.match_tone is not None and opt.seeds is None:
                 report_tone(opt.outdir, filename[:-4], opt.seed, fits)
+            elif opt.match_tone is not None:
+                for i, s_ in enumerate(tags):
+                    report_tone(opt.outdir, filename[:-4], s_, fits[i:i + 1])
         ref_maps = None
         if cm is not None:                                                             # (an explicit request: written with --skip_save too)
             ref_maps = cm.result(z_inpaint.shape[-2:])
-            save_reference_maps(opt.outdir, filename[:-4], opt.seed, ref_maps, opt.H, opt.W)
+            if opt.seeds is None:
+                save_reference_maps(opt.outdir, filename[:-4], opt.seed, ref_maps, opt.H, opt.W)
+            else:
+                for i, s_ in enumerate(tags):
+                    save_reference_maps(opt.outdir, filename[:-4], s_, ref_maps[i:i + 1], opt.H, opt.W)
         x = xd.cpu()
         if opt.dump_tensors:
             import numpy as np
+            if opt.seeds is not None:                                                  # the start code the sampler drew: stream 0 of each seed
+                from pbe_amd.noise import STREAM_X_T
+                start_code = ops.randn_seeded(list(opt.seeds), [nb] + shape, STREAM_X_T)
             np.savez(opt.dump_tensors, x_T=(start_code if start_code is not None else torch.zeros(0)).float().cpu().numpy(),
                      post_eps=post_eps.numpy(), c=c.float().cpu().numpy(), z_inpaint=z_inpaint.float().cpu().numpy(),
                      mask64=test_model_kwargs["inpaint_mask"].float().cpu().numpy(), latent=samples.float().cpu().numpy(), image=x.numpy(),
