@@ -393,7 +393,7 @@ def test_the_wrappers_refuse_cpu_tensors_and_bad_arguments_before_any_launch():
                                ([[0, 1, 0, 1]], (8, 16385), "16384"), ([[0, 1, 0, 1]], (8,), "shape")):
         with pytest.raises(PbeError, match=word):
             ops.fill_boxes(boxes, shape)
-    from pbe_amd.ops import _radius
+    from pbe_amd.ops_picture import _radius
     for r in (2047.5, -2048, float("nan"), float("inf"), "2", None, True):
         with pytest.raises(PbeError, match="real number in -2047 .. 2047"):
             _radius("r", r, True)

@@ -195,7 +195,7 @@ def test_tone_paste_emulation_passes_and_the_gate_rejects_wrong_pastes(case):
 
 # ---- 6. no CPU fallback ----------------------------------------------------------------------------------------------------------------
 def test_tone_ops_refuse_cpu_tensors_and_bad_arguments():
-    from pbe_amd import ops, pipeline
+    from pbe_amd import ops, ops_picture, pipeline
     from pbe_amd.lib import PbeError
     from pbe_amd.window import tone_selection
     image, result, sel = torch.zeros(1, 3, 8, 8), torch.zeros(1, 3, 8, 8), torch.zeros(1, 1, 8, 8)
@@ -206,8 +206,8 @@ def test_tone_ops_refuse_cpu_tensors_and_bad_arguments():
         ops.paste_window(torch.zeros(3, 8, 8), torch.zeros(10, 10), pic, (0, 0, 10, 10), tone=((1, 1, 1), (0, 0, 0)))
     for bad in ((1.0, 0.0), ((1, 1), (0, 0, 0)), ((1, 1, 1), (0, 0, float("nan"))), ((1, float("inf"), 1), (0, 0, 0)), "ab", ((1, 1, 1), (0, 0, 0), (0, 0, 0))):
         with pytest.raises(PbeError, match="tone"):
-            ops._tone_pair(bad)
-    g, b = ops._tone_pair(((1.25, 1, 0.5), (0.1, 0, -0.1)))
+            ops_picture._tone_pair(bad)
+    g, b = ops_picture._tone_pair(((1.25, 1, 0.5), (0.1, 0, -0.1)))
     assert list(g) == [1.25, 1.0, 0.5] and list(b) == [float(F(0.1)), 0.0, float(F(-0.1))]
     for tone in ("median", True, 1):
         with pytest.raises(PbeError, match="tone"):
