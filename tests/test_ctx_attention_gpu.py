@@ -13,6 +13,7 @@ import guard
 import modelbuild as build
 from accgate import CLOSE, close_verdict, rel_l2
 from oracle_loader import O
+from test_accuracy_gpu import report as accuracy_report
 from test_model_gpu import BLOCK_TOL, FWD_TOL, SAMPLER_OPT_TOL, report      # the project's tolerances and its parity report (same file, same format)
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,10 @@ def _gate(name, got, o):
     report(f"ctx_attention {name}", r, ctxref.REL_L2_FACTOR * rel_l2(emu, want))
     print(f"ctx_attention {name}: {text}")
     assert ok, f"{name}: {text}"
+    import ctxgate                                                           # beside it: every element within its own bound (tests/ctxgate.py)
+    v = ctxgate.verdict(got, o, emu=emu)
+    accuracy_report(f"{'ctx_attention ' + name:64s} err/bound={v.ratio:.3f} at {v.where} rel_l2={v.r_got:.3e} (emulation {v.r_emu:.3e})")
+    assert v.ok, f"{name}: {v}"
 
 
 # ---- the kernel ----------------------------------------------------------------------------------------------------------------------

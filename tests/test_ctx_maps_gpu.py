@@ -76,6 +76,15 @@ def test_map_kernel_against_fp64_reference(dev, shape, form):
     report(f"ctx_attention map {form} {mr.shape_id(shape)}: max|d| (bound 2^-11)", float((amap.double().cpu() - want).abs().max()), mr.ABS_BOUND)
     print(f"ctx_attention map {form} {mr.shape_id(shape)}: {text}")
     assert ok, text
+    import ctxgate                                                           # beside it: Y and the map per element (tests/ctxgate.py)
+    from test_accuracy_gpu import report as accuracy_report
+    ref = ctxgate.reference(o, None if form == "plain" else table.float())
+    v = ctxgate.verdict(y1, o, None if form == "plain" else table.float(), ref=ref)
+    accuracy_report(f"{'ctx_attention ' + form + ' ' + mr.shape_id(shape):64s} err/bound={v.ratio:.3f} at {v.where} rel_l2={v.r_got:.3e} (emulation {v.r_emu:.3e})")
+    assert v.ok, str(v)
+    ok2, ratio, where, text2 = ctxgate.map_verdict(amap, o, None if form == "plain" else table.float(), ref=ref)
+    accuracy_report(f"{'ctx_attention map ' + form + ' ' + mr.shape_id(shape):64s} err/bound={ratio:.3f} at {where}")
+    assert ok2, text2
     # the operands may carry the target themselves (what the transformer blocks use); run to run: the same bits
     again = torch.zeros_like(amap)
     y2, _ = ops.ctx_attention(x, oc.with_map(again, False), st, ctxref.EPS, tokens=N)

@@ -37,6 +37,11 @@ def _gate(name, got, o, table):
     report(f"ctx_attention rw {name}", rel_l2(got.cpu(), want), ctxref.REL_L2_FACTOR * rel_l2(emu, want))
     print(f"ctx_attention rw {name}: {text}")
     assert ok, f"{name}: {text}"
+    import ctxgate                                                           # beside it: every element within its own bound (tests/ctxgate.py)
+    from test_accuracy_gpu import report as accuracy_report
+    v = ctxgate.verdict(got, o, table.float(), emu=emu)
+    accuracy_report(f"{'ctx_attention rw ' + name:64s} err/bound={v.ratio:.3f} at {v.where} rel_l2={v.r_got:.3e} (emulation {v.r_emu:.3e})")
+    assert v.ok, f"{name}: {v}"
 
 
 def _rw(oc, table, dev):
