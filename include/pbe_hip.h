@@ -165,8 +165,13 @@ typedef struct pbe_conv3x3_desc {
     void* workspace;        /* optional split-K scratch, as in pbe_gemm_desc */
     size_t workspace_bytes;
     int32_t tile_cfg;       /* -1 = heuristic, else tile config | (split-K factor << 8), as in pbe_gemm_desc */
-    int32_t kblock;         /* channel block cb of Wp's K order: k = ((ci/cb)*9 + tap)*cb + ci%cb; multiple of 64 that
-                               divides C1 and C2 (0 = 64).  A pixel's 9 taps are then re-read within 9*cb/64 k-tiles (L2 hits) */
+    int32_t kblock;         /* channel block cb of Wp's K order: k = ((ci/cb)*T + tap)*cb + ci%cb, ci counted over the concat X | X2; multiple
+                               of 64 that divides C1 and C2 (0 = 64; anything else is PBE_EINVAL).  T = taps of the form:
+                                 upsample 0 and 1: T = 9, tap = dy*3 + dx.  A pixel's 9 taps are then re-read within 9*cb/64 k-tiles (L2 hits)
+                                 upsample 2:       T = 4, tap = ty*2 + tx, in each of the four weight sets [Cout][4*Cin] alike
+                                                   (pbe_amd.ops.pack_conv3x3_up_phases packs cb = 64)
+                               The halo-resident tiles take cb = 64 only: at another kblock a request for one runs a gather tile instead.
+                               The result is the same conv at every kblock; its fp32 summation order (k-tiles of 64 in K order) is not */
     /* Y feeds a GroupNorm (ResBlock: conv -> GroupNorm32 -> SiLU, openaimodel.py:213-227; the block's output -> the next normalisation):
      * group_stats_out != NULL asks the conv's copy-out for the per-(sample, row block, group) partial (sum, sumsq) of the STORED fp16
      * values, in pbe_groupnorm_f16's partial layout [B][blocks][group_stats_groups][2] (fp32; size it for blocks <= Ho*Wo / 64).
