@@ -191,6 +191,11 @@ int pbe_conv3x3_plan(const pbe_conv3x3_desc* d, int32_t* out6, size_t* workspace
  * offset of the parameter block's first tail field (= head size), offset of its last tail field}; mg_x = floor(2^32 / x) and
  * mh_x = ceil(2^20 / x) as 32-bit patterns (pbe_amd/csrc/igemm_kernel.h: udiv_mg, udiv_h). */
 int pbe_conv3x3_prologue(const pbe_conv3x3_desc* d, int32_t* out32);
+/* Host only: row cfg of the tile table the planners choose from.  out8 = {BM, BN, waves along m, waves along n, ring depth S in k-tiles
+ * of 64 (S - 1 in flight), forms bit mask (1 dense, 2 gather conv, 4 halo-resident conv, 8 extended epilogue, 16 fp8 operands,
+ * 32 A-stationary, 64 forced only), halo image rows (0: not a halo tile), workgroups of the tile a CU holds}; PBE_EINVAL past the last
+ * row (the rows are numbered from 0 without gaps). */
+int pbe_tile_info(int32_t cfg, int32_t* out8);
 
 /* im2col for the three small-Cin convs (9->320 U-Net in, 3->128 VAE in, 4->512 VAE decoder in):
  * X fp16 NHWC [B,H,W,Cp] -> out fp16 [B*Ho*Wo, 9*Cp]. */

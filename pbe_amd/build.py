@@ -64,13 +64,17 @@ def _compile(src: str, extra) -> str:
     return obj
 
 
-def build_diagnostic(defines, out_path: str) -> str:
-    """A separate library with extra -D flags (e.g. PBE_STAMPS) for tools/: own object directory, never the shipped .so."""
+def build_diagnostic(defines, out_path: str, only=None) -> str:
+    """A separate library with extra -D flags (e.g. PBE_STAMPS) for tools/: own object directory, never the shipped .so.
+    only: the sources whose code the defines change; the rest links the shipped library's objects (compiled first where stale)."""
     obj_dir = out_path + ".obj"
     os.makedirs(obj_dir, exist_ok=True)
+    os.makedirs(OBJ, exist_ok=True)
     objs = []
 
     def one(src):
+        if only is not None and src not in only:
+            return _compile(src, [])
         obj = os.path.join(obj_dir, os.path.splitext(src)[0] + ".o")
         cmd = [_hipcc(), *FLAGS, *EXTRA.get(src, []), *[f"-D{d}" for d in defines], "-c", os.path.join(CSRC, src), "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)

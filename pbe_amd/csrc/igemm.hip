@@ -210,6 +210,15 @@ extern "C" int pbe_conv3x3_prologue(const pbe_conv3x3_desc* d, int32_t* out32) {
     return PBE_OK;
 }
 
+extern "C" int pbe_tile_info(int32_t cfg, int32_t* out8) {
+    PBE_REQUIRE(out8, "pbe_tile_info: null output");
+    PBE_REQUIRE(cfg >= 0 && cfg < kNCfg, "pbe_tile_info: no tile %d (the table has %d rows)", cfg, kNCfg);
+    const TileCfg& t = kTiles[cfg];
+    const int32_t v[8] = {t.bm, t.bn, t.nwm, t.nwn, t.s, (int32_t)t.forms, t.hpa, t.slots_per_cu};
+    memcpy(out8, v, sizeof(v));
+    return PBE_OK;
+}
+
 // ---- MX-fp8 output (pbe_gemm_mx8out_f16): the GEMM's output columns leave as pbe_attention_mx8 operands ----
 static int fill_mx8(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, IGemmP& p, const char* who) {
     PBE_REQUIRE(d && mx, "%s: null descriptor", who);

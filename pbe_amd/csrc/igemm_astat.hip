@@ -123,7 +123,11 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
     auto step = [&](auto WAITC, auto KTC, int n0, int sbuf) {
         constexpr int WAIT = decltype(WAITC)::value, kt = decltype(KTC)::value;
         PBE_ACC_T0();
+#if PBE_RACE_MUTANT == 3
+        if (q == Q - 1) wait_vmcnt<0>(); else wait_vmcnt<WAIT + PW>();      // as if W(q) itself may stay in flight (igemm_kernel.h, PBE_RACE_MUTANT)
+#else
         if (q == Q - 1) wait_vmcnt<0>(); else wait_vmcnt<WAIT>();
+#endif
         PBE_ACC(acc_w_);
         PBE_ACC_T0();
         __builtin_amdgcn_s_barrier();

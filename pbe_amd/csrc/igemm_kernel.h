@@ -148,6 +148,21 @@ static_assert(offsetof(IGemmP, bias) == 232 && offsetof(IGemmP, ldc) == 256 && o
 #define PBE_SETPRIO(x) do { } while (0)
 #endif
 
+// Diagnostic build (-DPBE_RACE_MUTANT=1 | 2 | 3, never the shipped library): the positive control of the race screens (tests/racescreen.py,
+// DESIGN.md "Race screens").  Each value relaxes the counted vmcnt wait in front of ONE structure's LDS fragment reads by one tile's
+// pieces, i.e. the waves read a ring slot whose DMA may still be in flight: 1 = the ring loop (MODE 0 / 1), 2 = the halo loops (MODE 2,
+// both forms), 3 = the A-stationary loop (igemm_astat.hip: every wait but the run's last; its screens compare with tile 9's bits, not with
+// integers).  1 and 2 never before the slice's tenth k-tile (PBE_RACE_MUTANT_KT): the slot's previous occupant is then a k-tile of the
+// same slice, which the screens' diagnosis can name.  A loop that keeps ONE tile in flight beyond the one it
+// waits for is relaxed at that k-tile only (every relaxed wait shows: the tile was issued one period ago); a ring that keeps two or more
+// hides a single early wait (the tile was issued two periods ago and the earlier waits kept the queue short), so there every wait from
+// that k-tile on is relaxed and the waves run ahead of the DMA.  Only the immediate of an s_waitcnt changes: no global address, store or
+// barrier depends on it, so the worst outcome is a wrong number.  0 compiles the shipped code, token for token.
+#ifndef PBE_RACE_MUTANT
+#define PBE_RACE_MUTANT 0
+#endif
+#define PBE_RACE_MUTANT_KT 9
+
 static __device__ __attribute__((aligned(16))) unsigned int g_pbe_zero16[4] = {0u, 0u, 0u, 0u};   // (one copy per translation unit)
 
 #define EX_LN 1
@@ -835,7 +850,15 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
                     }
                     PBE_ACC(acc_m_);
                     PBE_ACC_T0();
+#if PBE_RACE_MUTANT == 2
+                    if (grp == 0) {                                                                  // as if W(kt + 1) may fly too, once per slice
+                        if (tap == 8 && blk == blk0 && w) wait_vmcnt<2 * kPWG>();
+                        else if (w) wait_vmcnt<kPWG>();
+                        else wait_vmcnt<0>();
+                    }
+#else
                     if (grp == 0) { if (w) wait_vmcnt<kPWG>(); else wait_vmcnt<0>(); }      // W(kt + 1) landed; this period's tile may fly
+#endif
                     PBE_ACC(acc_w_);
                     __builtin_amdgcn_sched_barrier(0);
                     PBE_ACC_T0();
@@ -871,6 +894,27 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
                     const int wleft = min(nk2 - 1 - kt, D - 1);
                     const bool a_young = next_a && tap >= 1 && tap <= D;
                     PBE_ACC_T0();
+#if PBE_RACE_MUTANT == 2
+                    if (D == 1 ? kt != blk0 * 9 + PBE_RACE_MUTANT_KT : kt < blk0 * 9 + PBE_RACE_MUTANT_KT) {
+                        if (a_young) {
+                            if (D >= 3 && wleft >= 2) wait_vmcnt<2 * LW + LAH>();
+                            else if (D >= 2 && wleft >= 1) wait_vmcnt<LW + LAH>();
+                            else wait_vmcnt<LAH>();
+                        } else {
+                            if (D >= 3 && wleft >= 2) wait_vmcnt<2 * LW>();
+                            else if (D >= 2 && wleft >= 1) wait_vmcnt<LW>();
+                            else wait_vmcnt<0>();
+                        }
+                    } else if (a_young) {                    // as if wleft + 1 weight tiles may stay in flight: W(kt) itself
+                        if (D >= 3 && wleft >= 2) wait_vmcnt<(D >= 3 ? 3 : 1) * LW + LAH>();
+                        else if (D >= 2 && wleft >= 1) wait_vmcnt<(D >= 2 ? 2 : 1) * LW + LAH>();
+                        else wait_vmcnt<LW + LAH>();
+                    } else {
+                        if (D >= 3 && wleft >= 2) wait_vmcnt<(D >= 3 ? 3 : 1) * LW>();
+                        else if (D >= 2 && wleft >= 1) wait_vmcnt<(D >= 2 ? 2 : 1) * LW>();
+                        else wait_vmcnt<LW>();
+                    }
+#else
                     if (a_young) {
                         if (D >= 3 && wleft >= 2) wait_vmcnt<2 * LW + LAH>();
                         else if (D >= 2 && wleft >= 1) wait_vmcnt<LW + LAH>();
@@ -880,6 +924,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
                         else if (D >= 2 && wleft >= 1) wait_vmcnt<LW>();
                         else wait_vmcnt<0>();
                     }
+#endif
                     PBE_ACC(acc_w_);
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     PBE_ACC_T0();
@@ -942,9 +987,19 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
 #endif
         const int rem = min(nk - 1 - kt, D - 1);     // later tiles that may stay in flight
         PBE_ACC_T0();
+#if PBE_RACE_MUTANT == 1
+        if (D == 1 ? kt == kt0 + PBE_RACE_MUTANT_KT : kt >= kt0 + PBE_RACE_MUTANT_KT) {      // as if one more tile may stay in flight: tile kt itself
+            if (D >= 3 && rem >= 2) wait_vmcnt<(D >= 3 ? 3 : 1) * LPT>();
+            else if (D >= 2 && rem >= 1) wait_vmcnt<(D >= 2 ? 2 : 1) * LPT>();
+            else wait_vmcnt<LPT>();
+        } else if (D >= 3 && rem >= 2) wait_vmcnt<2 * LPT>();
+        else if (D >= 2 && rem >= 1) wait_vmcnt<LPT>();
+        else wait_vmcnt<0>();
+#else
         if (D >= 3 && rem >= 2) wait_vmcnt<2 * LPT>();
         else if (D >= 2 && rem >= 1) wait_vmcnt<LPT>();
         else wait_vmcnt<0>();
+#endif
         PBE_ACC(acc_w_);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         PBE_ACC_T0();
