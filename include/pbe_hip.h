@@ -189,7 +189,7 @@ int pbe_conv3x3_plan(const pbe_conv3x3_desc* d, int32_t* out6, size_t* workspace
  * tdiv, mg_tdiv, split_per, sv_ns, sv_gdiv, mg_sv_gdiv, hw, mg_hw, mg_wo, per_blk, mg_per_blk, mg_kb, th, hw2, hps, nsub, halo rows, tiles
  * per image, mg_tpi, mh_hps, mh_hw2, log2 W, log2 pixels per (sub-)image, halo image rows of the tile,
  * offset of the parameter block's first tail field (= head size), offset of its last tail field}; mg_x = floor(2^32 / x) and
- * mh_x = ceil(2^20 / x) as 32-bit patterns (pbe_amd/csrc/igemm_kernel.h: udiv_mg, udiv_h). */
+ * mh_x = ceil(2^20 / x) as 32-bit patterns (pbe_amd/csrc/igemm_params.h: udiv_mg, udiv_h). */
 int pbe_conv3x3_prologue(const pbe_conv3x3_desc* d, int32_t* out32);
 /* Host only: row cfg of the tile table the planners choose from.  out8 = {BM, BN, waves along m, waves along n, ring depth S in k-tiles
  * of 64 (S - 1 in flight), forms bit mask (1 dense, 2 gather conv, 4 halo-resident conv, 8 extended epilogue, 16 fp8 operands,

@@ -48,8 +48,7 @@ def _stale(target: str, deps) -> bool:
 
 def _compile(src: str, extra) -> str:
     obj = os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
-    deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "igemm_kernel.h"), os.path.join(CSRC, "tone_bytes.h"), os.path.join(CSRC, "u8_norm.h"),
-            os.path.join(HERE, "..", "include", "pbe_hip.h"), os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, src), *[os.path.join(HERE, rel) for rel in _libmod.HEADERS], os.path.abspath(__file__)]
     hash_flag = []
     if src == "runtime.hip":                     # the library's identity: rebuilt whenever ANY source changed
         hash_flag = [f'-DPBE_SRC_HASH="{_libmod.source_hash()}"']

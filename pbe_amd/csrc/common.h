@@ -110,7 +110,7 @@ static inline void pbe_raise_dynamic_lds(std::atomic<uint64_t>& done, const void
     done.fetch_or(bit, std::memory_order_release);
 }
 
-// ---- MX-fp8 (OCP e4m3 + E8M0 per 32 elements): the quantiser (attention_mx8.hip) and the GEMM epilogue's MX copy-out (igemm_kernel.h,
+// ---- MX-fp8 (OCP e4m3 + E8M0 per 32 elements): the quantiser (attention_mx8.hip) and the GEMM epilogue's MX copy-out (igemm_mx8_out.h,
 //      mx8_block_lds) share this code ----
 // OCP e4m3 of y, round to nearest even, saturating at +-448 (never NaN), subnormals kept (quantum 2^-9).  Integer / power-of-two
 // arithmetic only: v_cvt_pk_fp8_f32 disagreed with this rounding on some of the adversarial blocks (outliers, fp16 subnormals) of the

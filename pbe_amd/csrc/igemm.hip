@@ -1,6 +1,6 @@
-// Host side of the implicit-GEMM entry points: descriptor checks, plan queries, developer knobs.  The kernel and its planner are in
-// igemm_kernel.h (tile table kTiles); the instantiations in igemm_{dense,conv,halo,f8,ex*}.hip.
-#include "igemm_kernel.h"
+// Host side of the implicit-GEMM entry points: descriptor checks, plan queries, developer knobs.  The planner is
+// in igemm_plan.h, the kernel and the tile table kTiles in igemm_kernel.h; the instantiations in igemm_{dense,conv,halo,f8,ex*,astat}.hip.
+#include "igemm_plan.h"
 
 #ifdef PBE_STAMPS
 unsigned long long* g_pbe_stamps = nullptr;

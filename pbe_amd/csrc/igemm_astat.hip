@@ -16,22 +16,29 @@
 // Rows of 128 B with the chunk swizzle of igemm_kernel.h (position p of row r holds chunk p ^ (r & 7)): the same conflict-free
 // ds_read_b128 fragment reads.  The arithmetic (accumulation order, epilogue association) is that of the streaming kernel: bit-identical
 // output, checked by tests/test_ops_gpu.py::test_gemm_a_stationary_matches_streaming_tile.
-#include "igemm_kernel.h"
+#include "igemm_plan.h"
 
 namespace {
 constexpr int ABM = 128, AKT = 5;
+// The dynamic LDS of astat_regs_kernel<TN, *>, stated once for the kernel and launch_regs: [weight ring, RS slots] [16 staging rows per wave]
+// [svec: 2 buffers x (bias | colsum) x BN floats]
+template <int TN> struct AstatGeom {
+    static constexpr int BN = 16 * TN, SLOT = BN * 128, RS = 3;      // (a ring of 4 fits the 128-column form: measured slower, 0.70 -> 0.73 of the streaming tile's time cold)
+    static constexpr int STGR = BN / 2 + 8, STGW = 16 * STGR * 2;     // halfs per staging row; bytes of a wave's staging rows
+    static constexpr int STG_OFF = RS * SLOT, SVEC_OFF = STG_OFF + 4 * STGW, SVEC_BYTES = 2 * 2 * BN * 4, LDS_BYTES = RS * SLOT + 4 * STGW + SVEC_BYTES;
+    static_assert(SVEC_OFF + SVEC_BYTES == LDS_BYTES && BN % 32 == 0 && LDS_BYTES <= 80 * 1024, "the last region ends at LDS_BYTES; two workgroups per CU");
+};
 }  // namespace
 
 // FORM 0: GEGLU output (the FeedForward projection).  FORM 1: q | k | v^T of the fused self-attention projection - plain fp16 columns, alpha on
 // the columns below alpha_cols only, the tiles at and beyond vt_col0 stored transposed (IGemmP.vt), as the EX_LN | EX_VT streaming form does.
 // FORM 2: FORM 1 with the MX-fp8 copy-out (pbe_gemm_mx8out_f16): the same staged fp16 rows leave as pbe_attention_mx8's operands - an
-// 80-column q | k half row is two d = 40 heads, a transposed staging row 32 tokens, i.e. one MX block (igemm_kernel.h, mx8_*).
+// 80-column q | k half row is two d = 40 heads, a transposed staging row 32 tokens, i.e. one MX block (igemm_mx8_out.h, mx8_*).
 template <int TN, int FORM>
 __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int run, int tiles_m) {
     constexpr int TM = 2, BN = 16 * TN, PW = BN / 8 / 4;          // PW = weight pieces (8 rows x 128 B) per wave and k-tile
-    constexpr int SLOT = BN * 128, RS = 3;      // (a ring of 4 fits the 128-column form: measured slower, 0.70 -> 0.73 of the streaming tile's time cold)
-    constexpr int STGR = BN / 2 + 8;                               // halfs per staging row
-    constexpr int STGW = 16 * STGR * 2;
+    using G = AstatGeom<TN>;                                       // the LDS layout
+    constexpr int SLOT = G::SLOT, RS = G::RS, STGR = G::STGR, STGW = G::STGW;
     constexpr int NST = (16 * (BN / 16) + 63) / 64;                // store instructions per 16 rows x BN / 2 columns (chunks of 16 bytes)
     constexpr int VROW = 40;                                       // halfs per row of the transposed staging (32 tokens + pad)
     // stores a tile's epilogue leaves in the vmcnt queue: GEGLU 2 NST; plain 4 NST, transposed TN (the counted waits take the smaller)
@@ -42,7 +49,6 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
     // waits of the next tile's first two k-tiles pass before their weight slot has landed.
     static_assert(FORM != 2 || (EST <= 12 && EST <= 2 * (TN / 2)), "form 2: the MX copy-out must issue at least EST stores per tile");
     static_assert(FORM == 0 || (TN % 2 == 0 && 32 * VROW * 2 <= 16 * (BN / 2 + 8) * 2), "transposed staging: two 16-column groups at a time");
-    static_assert(BN % 32 == 0 && RS * SLOT + 4 * STGW + 2 * 2 * BN * 4 <= 80 * 1024, "two workgroups per CU");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wm = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -50,8 +56,8 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
     const int rn = (int)udiv_mg(blockIdx.x, (unsigned)tiles_m, p.mg_tdiv), mb = (int)blockIdx.x - rn * tiles_m;
     const int m0 = mb * ABM, nt0 = rn * run;
     const int Q = run * AKT;
-    h16* stg = reinterpret_cast<h16*>(smem + RS * SLOT + wm * STGW);
-    float* svec = reinterpret_cast<float*>(smem + RS * SLOT + 4 * STGW);       // [2 buffers][bias | colsum][BN]
+    h16* stg = reinterpret_cast<h16*>(smem + G::STG_OFF + wm * STGW);
+    float* svec = reinterpret_cast<float*>(smem + G::SVEC_OFF);       // [2 buffers][bias | colsum][BN]
     const int fr = lane & 15, fq = lane >> 4;
     PBE_ACC_DECL;
     PBE_STAMP(0);
@@ -123,11 +129,8 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
     auto step = [&](auto WAITC, auto KTC, int n0, int sbuf) {
         constexpr int WAIT = decltype(WAITC)::value, kt = decltype(KTC)::value;
         PBE_ACC_T0();
-#if PBE_RACE_MUTANT == 3
-        if (q == Q - 1) wait_vmcnt<0>(); else wait_vmcnt<WAIT + PW>();      // as if W(q) itself may stay in flight (igemm_kernel.h, PBE_RACE_MUTANT)
-#else
-        if (q == Q - 1) wait_vmcnt<0>(); else wait_vmcnt<WAIT>();
-#endif
+        // (mutant 3: as if W(q) itself may stay in flight - igemm_params.h, PBE_RACE_MUTANT)
+        if (q == Q - 1) wait_vmcnt<0>(); else wait_vmcnt<WAIT + (PBE_RACE_MUTANT == 3 ? PW : 0)>();
         PBE_ACC(acc_w_);
         PBE_ACC_T0();
         __builtin_amdgcn_s_barrier();
@@ -301,11 +304,11 @@ __global__ void __launch_bounds__(256, 2) astat_regs_kernel(const IGemmP p, int 
 template <int TN, int FORM>
 static void launch_regs(IGemmP p, hipStream_t s) {
     constexpr int BN = 16 * TN;
-    constexpr int lds = 3 * BN * 128 + 4 * 16 * (BN / 2 + 8) * 2 + 2 * 2 * BN * 4;
+    constexpr int lds = AstatGeom<TN>::LDS_BYTES;
     const int tiles_m = p.M / ABM, tiles_n = p.N / BN;
     int run = tiles_n;                                     // the longest run of column tiles that still gives every CU its two workgroups
     while (run > 1 && ((long)tiles_m * (tiles_n / run) < 512 || tiles_n % run)) --run;
-    p.tdiv = tiles_m; p.mg_tdiv = mg_of((unsigned)tiles_m);                   // the kernel's prologue divides by multiplying (igemm_kernel.h, udiv_mg)
+    p.tdiv = tiles_m; p.mg_tdiv = mg_of((unsigned)tiles_m);                   // the kernel's prologue divides by multiplying (igemm_params.h, udiv_mg)
     p.per_blk = run; p.mg_per_blk = mg_of((unsigned)run);
     static std::atomic<uint64_t> attr_done{0};
     pbe_raise_dynamic_lds(attr_done, reinterpret_cast<const void*>(&astat_regs_kernel<TN, FORM>), lds);

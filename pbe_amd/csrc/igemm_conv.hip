@@ -1,5 +1,5 @@
 // 3x3 conv gather (MODE 1) tiles of the implicit-GEMM kernel (igemm_kernel.h).
-#include "igemm_kernel.h"
+#include "igemm_plan.h"
 
 int pbe_dispatch_conv(IGemmP p, int batch, hipStream_t s, size_t ws_bytes, int want_cfg) {
     const Plan pl = plan_igemm(p, batch, ws_bytes, want_cfg, 1);

@@ -1,5 +1,5 @@
 // Extended-epilogue GEMMs (the transformer block's chain): plan, then the instantiation that carries exactly the requested features.
-#include "igemm_kernel.h"
+#include "igemm_plan.h"
 
 // (LayerNorm fold / row statistics / column-range alpha / V^T tiles; never split-K)
 int pbe_dispatch_ex(IGemmP p, int batch, hipStream_t s, int want_cfg) {

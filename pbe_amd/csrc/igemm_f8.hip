@@ -1,5 +1,5 @@
 // fp8 (OCP e4m3) operand tiles of the implicit-GEMM kernel (igemm_kernel.h).
-#include "igemm_kernel.h"
+#include "igemm_plan.h"
 
 // fp8 operands: the F_F8 subset of the dense tiles (no split-K: the slab reduce does not carry the operand scales)
 int pbe_dispatch_f8(IGemmP p, int batch, hipStream_t s, int want_cfg) {

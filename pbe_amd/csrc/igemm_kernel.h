@@ -30,173 +30,9 @@
 //   * what bounds the big conv tiles on real data is the power limit: cycles removed from the schedule come back
 //     as a lower clock.
 #pragma once
-#include <cstddef>
-#include <type_traits>
-#include <utility>
-#include "common.h"
-#include "../../include/pbe_hip.h"
-
-struct IGemmP {
-    // ---- HEAD: everything a workgroup reads between kernel entry and its first LDS-DMA, contiguous so the scalar loads of the prologue
-    //      come from the first cache lines of the kernarg segment (offsets pinned by the static_asserts below).  A REORDER ONLY: the
-    //      compiler still fetches the head as the code reaches it, and a mode skips the fields of the others
-    //      (hw / mg_hw .. mg_kb: MODE 1; h_*: MODE 2).  astat_regs_kernel reads mg_tdiv (divisor tiles_m) and mg_per_blk (its run) ----
-    const h16* A; const h16* A2; const h16* W;
-    long lda, lda2, ldw;
-    long sA, sW;
-    int M, N, K, K1;
-    int splits;
-    int m_fast;     // an XCD's run of tiles walks m fastest (one weight panel, many activation rows) instead of n fastest (launch_cfg)
-    // launch-invariant prologue values (igemm_prologue, host): the kernel holds no run-time division before its first fetch.
-    // mg_* = floor(2^32 / divisor) for udiv_mg (exact for every 32-bit numerator), mh_* = ceil(2^20 / divisor) for the halo rows' udiv_h
-    int tdiv; unsigned mg_tdiv;                          // tile id -> (tm_i, tn_i): divisor tiles_m (m fastest) or tiles_n
-    int split_per;                                       // split-K: k-tiles (MODE 0 / 1) or channel blocks (MODE 2) per slice
-    int sv_ns;                                           // samples per tile of the staged epilogue vectors
-    int sv_gdiv; unsigned mg_sv_gdiv;                    // row tiles per sample (group_rows / BM, >= 1): first sample of a tile = tm_i / sv_gdiv
-    // conv gather
-    int H, Wd, C1, C2, Ho, Wo, cstride, pad, ups, cb;   // cb = channel block of the K order (multiple of 64)
-    int phase;                                           // MODE 1: nearest-2x upsample + 3x3 conv as FOUR 2x2 convs on the source grid (see the tap table); blockIdx.y = output phase
-    int th;                                              // MODE 2: image rows per tile (tile = th full rows, or whole images)
-    int hw; unsigned mg_hw, mg_wo;                       // MODE 1 tap table: output pixels per sample, m -> (b, oy, ox)
-    int per_blk; unsigned mg_per_blk, mg_kb;             // MODE 1 split-K resume: k-tiles per channel block (taps x cb / 64), per tap
-    // MODE 2 halo geometry: row stride W + 1, halo rows per (sub-)image, whole images per tile, valid halo rows, row tiles per image,
-    // log2 of the image width and of the pixels per (sub-)image (both powers of two: halo_rows)
-    int h_hw2, h_hps, h_nsub, h_rows, h_tpi; unsigned mg_h_tpi, mh_hps, mh_hw2; int h_lgw, h_lgimg;
-    // ---- TAIL: epilogue, statistics and diagnostic fields ----
-    h16* C;
-    const float* bias; const h16* rowvec; const h16* resid;
-    long ldc, ldr;
-    int ldv, group_rows;
-    long sC, sR;
-    float alpha; int act; int bias_row; int vec;
-    // fp8 (OCP e4m3) operands: rows are bytes (the loader sees them as K/2 halfs); C = acc * sa[m] * sw[n] (* alpha) + ...
-    const float* sa; const float* sw; long ssa, ssw;
-    // split-K: gridDim.z slices of the k-tile range, fp32 partial slabs [splits][M][N]
-    float* ws;
-    // extended epilogue of the dense tiles (EX instantiations, the transformer block's GEMM chain; ldm/modules/attention.py:198-252):
-    int alpha_cols;                  // > 0: alpha multiplies columns n < alpha_cols only (q of a fused q | k | v launch, pre-scaled for the attention kernel)
-    const float* ln_stat;            // LayerNorm folded into THIS GEMM: A holds the raw rows x, W = W * gamma, bias = W beta (+ bias), and
-    int ln_parts; long ln_ld;        //   the epilogue forms rstd[m] * (acc - mean[m] * colsum[n]); (sum, sumsq) of row m = sum over ln_parts float2 partials
-    const float* ln_c1; float ln_eps; double ln_inv_k;
-    long rstat_ld;
-    float* rstat;                    // this launch's OUTPUT rows feed a LayerNorm: per (column tile, row) partial (sum, sumsq) of the stored fp16 values
-    h16* vt; int vt_col0, vt_tok;    // columns n >= vt_col0 are stored TRANSPOSED: vt[b * vt_bs + (n - vt_col0) * vt_rs + tok], m = b * vt_tok + tok
-    long vt_bs, vt_rs;               //   (V^T for the attention kernel from the same launch as q | k)
-    // conv output feeds a GroupNorm: per (sample, row block of the tile grid, group) partial (sum, sumsq) of the STORED fp16 values (after the
-    // residual add), in pbe_groupnorm_f16's partial layout [B][blocks][groups][2] - the norm's statistics pass is then not launched
-    float* gstat; int gs_cg, gs_groups, gs_hw;      // channels per group, groups of the whole tensor, output pixels per sample
-    int* gs_report;                                 // HOST pointer (launch_cfg): row blocks per sample the launch writes partials for, 0 = this tile cannot
-    // MX-fp8 output (EX_MX instantiations, pbe_gemm_mx8out_f16): column ranges [mx_c0, mx_c0 + width) of the output leave as OCP e4m3 bytes
-    // + E8M0 scales in pbe_quant_mx8_f16's layouts (include/pbe_hip.h) instead of fp16; C is not written.  Shared B, H, N, D (N % 64 == 0);
-    // mx_crow: rows are the H*D channels of V^T, columns its N tokens, blockIdx.y = sample (the swapped V^T GEMM); else rows are tokens
-    unsigned char* mx_data[3]; unsigned char* mx_scale[3];
-    int mx_c0[3], mx_layout[3]; float mx_alpha[3]; int mx_nr, mx_crow;
-    int mx_H, mx_N, mx_D, mx_DP, mx_DV;
-    int sv_ok;      // bias + row vector of a tile come from LDS (set per tile shape in launch_cfg)
-#ifdef PBE_STAMPS
-    unsigned long long* stamps;     // diagnostic build only (tools/phase_stamps.py): 16 words per workgroup
-#endif
-};
-// the head is what the host fills for the prologue and what a workgroup fetches first: four 64-byte lines of the kernarg segment
-constexpr size_t kIGemmHeadBytes = offsetof(IGemmP, C);
-static_assert(offsetof(IGemmP, A) == 0 && offsetof(IGemmP, lda) == 24 && offsetof(IGemmP, M) == 64 && offsetof(IGemmP, tdiv) == 88 &&
-              offsetof(IGemmP, H) == 112 && offsetof(IGemmP, hw) == 160 && offsetof(IGemmP, h_hw2) == 184 && kIGemmHeadBytes == 224,
-              "IGemmP: the prologue head moved");
-static_assert(offsetof(IGemmP, bias) == 232 && offsetof(IGemmP, ldc) == 256 && offsetof(IGemmP, alpha) == 296 && offsetof(IGemmP, ws) == 344 &&
-              offsetof(IGemmP, ln_stat) == 360, "IGemmP: the epilogue tail moved");
-
-// Diagnostic build (-DPBE_STAMPS, never the shipped library): wave 0 of every workgroup records s_memtime at its phase
-// boundaries into a buffer of its own; no output value depends on a stamp (cdna_hip_programming.md section 7, in-kernel stamps).
-#ifdef PBE_STAMPS
-#define PBE_STAMP(i)                                                                                                   \
-    do {                                                                                                               \
-        if (p.stamps && threadIdx.x == 0) {                                                                            \
-            const long wg_ = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;                     \
-            p.stamps[wg_ * 16 + (i)] = ((i) == 7 || (i) == 8) ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();    \
-        }                                                                                                              \
-    } while (0)
-// main-loop accounting of wave 0: cycles inside the counted vmcnt waits (words 9), the barrier after the fragment reads (10) and
-// the barrier that ends a k-tile (11), DMA issue + fragment reads up to lgkmcnt(0) (12), the MFMA block (13)
-#define PBE_ACC_DECL unsigned long long acc_w_ = 0, acc_b1_ = 0, acc_b2_ = 0, acc_r_ = 0, acc_m_ = 0, acc_t_ = 0
-#define PBE_ACC_T0() acc_t_ = __builtin_amdgcn_s_memtime()
-#define PBE_ACC(v) v += __builtin_amdgcn_s_memtime() - acc_t_
-#define PBE_ACC_STORE()                                                                                                \
-    do {                                                                                                               \
-        if (p.stamps && threadIdx.x == 0) {                                                                            \
-            const long wg_ = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;                     \
-            p.stamps[wg_ * 16 + 9] = acc_w_; p.stamps[wg_ * 16 + 10] = acc_b1_; p.stamps[wg_ * 16 + 11] = acc_b2_;    \
-            p.stamps[wg_ * 16 + 12] = acc_r_; p.stamps[wg_ * 16 + 13] = acc_m_;                                       \
-        }                                                                                                              \
-    } while (0)
-#else
-#define PBE_STAMP(i) do { } while (0)
-#define PBE_ACC_DECL do { } while (0)
-#define PBE_ACC_T0() do { } while (0)
-#define PBE_ACC(v) do { } while (0)
-#define PBE_ACC_STORE() do { } while (0)
-#endif
-
-// Priority of the MFMA block.  PBE_PRIO_MODE: 0 = s_setprio 1 around every MFMA block, 1 = none (shipped: same-device A/B over the
-// whole pipeline, conv class 193.2 -> 191.9 ms, GEMM class unchanged), 2 = static: waves 4-7 of an 8-wave tile at priority 1 for
-// the whole main loop (MI355X_MICROARCH.md, Two waves per SIMD, item 4: 192.1 ms)
-#ifndef PBE_PRIO_MODE
-#define PBE_PRIO_MODE 1
-#endif
-#if PBE_PRIO_MODE == 0
-#define PBE_SETPRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define PBE_SETPRIO(x) do { } while (0)
-#endif
-
-// Diagnostic build (-DPBE_RACE_MUTANT=1 | 2 | 3, never the shipped library): the positive control of the race screens (tests/racescreen.py,
-// DESIGN.md "Race screens").  Each value relaxes the counted vmcnt wait in front of ONE structure's LDS fragment reads by one tile's
-// pieces, i.e. the waves read a ring slot whose DMA may still be in flight: 1 = the ring loop (MODE 0 / 1), 2 = the halo loops (MODE 2,
-// both forms), 3 = the A-stationary loop (igemm_astat.hip: every wait but the run's last; its screens compare with tile 9's bits, not with
-// integers).  1 and 2 never before the slice's tenth k-tile (PBE_RACE_MUTANT_KT): the slot's previous occupant is then a k-tile of the
-// same slice, which the screens' diagnosis can name.  A loop that keeps ONE tile in flight beyond the one it
-// waits for is relaxed at that k-tile only (every relaxed wait shows: the tile was issued one period ago); a ring that keeps two or more
-// hides a single early wait (the tile was issued two periods ago and the earlier waits kept the queue short), so there every wait from
-// that k-tile on is relaxed and the waves run ahead of the DMA.  Only the immediate of an s_waitcnt changes: no global address, store or
-// barrier depends on it, so the worst outcome is a wrong number.  0 compiles the shipped code, token for token.
-#ifndef PBE_RACE_MUTANT
-#define PBE_RACE_MUTANT 0
-#endif
-#define PBE_RACE_MUTANT_KT 9
-
+#include "igemm_params.h"
+#include "igemm_mx8_out.h"
 static __device__ __attribute__((aligned(16))) unsigned int g_pbe_zero16[4] = {0u, 0u, 0u, 0u};   // (one copy per translation unit)
-
-#define EX_LN 1
-#define EX_ST 2
-#define EX_VT 4
-#define EX_MX 8        // MX-fp8 copy-out (IGemmP.mx_*): a compile-time form of copy_out, never a run-time branch of the fp16 kernels
-#define PBE_GLDS16(gsrc, ldst)                                                                     \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc),         \
-                                     (__attribute__((address_space(3))) void*)(ldst), 16, 0, 0)
-
-// Divisions of the prologue by launch-invariant divisors: the host passes a reciprocal (igemm_prologue), the kernel multiplies.
-// n / d for ANY 32-bit n and 1 <= d < 2^31, mg = floor(2^32 / d) (2^32 - 1 for d = 1): n mg / 2^32 lies in (n / d - 1, n / d], so the
-// estimate is the quotient or one less and one fix-up makes it exact (5 scalar instructions against ~40 of the generic division)
-__host__ __device__ __forceinline__ unsigned udiv_mg(unsigned n, unsigned d, unsigned mg) {
-    unsigned q = (unsigned)(((unsigned long long)n * mg) >> 32);
-    q += (n - q * d >= d) ? 1u : 0u;
-    return q;
-}
-static inline unsigned mg_of(unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)((1ull << 32) / d); }
-// a / d for 0 <= a < 1024 and 1 <= d <= 512 (halo rows and their divisors: HPA <= 512), mh = ceil(2^20 / d).  With e = mh d - 2^20, 0 <= e < d:
-// a mh / 2^20 = a / d + a e / (d 2^20), and the excess a e / (d 2^20) < a / 2^20 < 2^-10 < 1 / d.  a / d lies at least 1 / d below the next
-// integer, so the floor is the quotient - exact without a fix-up, one 24-bit multiply and a shift
-// (the float-reciprocal form this replaces took 9 instructions, ~50 times per lane of a halo tile)
-__host__ __device__ __forceinline__ int udiv_h(int a, unsigned mh) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return (int)(__umul24((unsigned)a, mh) >> 20);
-#else
-    return (int)(((unsigned)a * mh) >> 20);
-#endif
-}
-static inline unsigned mh_of(unsigned d) { return (unsigned)(((1u << 20) + d - 1) / d); }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 typedef long i64;
 // one 16-byte fragment = two 8-byte fp8 operands: both MFMAs take the SAME byte positions from the two matrices, so together
@@ -208,131 +44,86 @@ __device__ __forceinline__ f32x4 mfma_pair_f8(const h16x8& w, const h16x8& a, f3
     return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(wv[1], av[1], acc, 0, 0, 0);
 }
 
-// ---- MX-fp8 copy-out (EX_MX; also the A-stationary tile's form 2): staged fp16 values -> pbe_quant_mx8_f16's bytes and scales ----
-// A block's values are the fp16 values pbe_gemm_f16 would store, times the range's alpha in fp32, then pbe_quant_mx8_f16's arithmetic
-// (mx8_scale_exp / mx8_e4m3, common.h) to pbe_quant_mx8_f16's addresses: bit-identical to the two-launch path by construction.
-// One block straight from the staged values at src (len in {8, 16, 24, 32}: whole 16-byte chunks; zeros past it, as the quantiser pads):
-// the amax in a first pass over the LDS, then the bytes 16 values at a time - 16 live floats instead of 32 (the A-stationary tile's
-// epilogue holds its A block and accumulators in registers: the whole-block form spilled 100 bytes per lane there).
-__device__ __forceinline__ int mx8_block_lds(const h16* src, int len, float al, unsigned char* dst) {
-    typedef int i32x4_ __attribute__((ext_vector_type(4)));
-    float amax = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (8 * c < len) {
-            const h16x8 x = *reinterpret_cast<const h16x8*>(src + 8 * c);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf((float)x[e] * al));
-        }
-    }
-    const int se = mx8_scale_exp(amax);
-    const float inv = __uint_as_float((unsigned)(254 - se) << 23);                          // 1 / 2^(se - 127), exact
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-        i32x4_ w;
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-            const int c = 2 * hf + cc;
-            h16x8 x = {};
-            if (8 * c < len) x = *reinterpret_cast<const h16x8*>(src + 8 * c);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                unsigned word = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float v = 8 * c + 4 * q + e < len ? (float)x[4 * q + e] * al : 0.f;
-                    word |= mx8_e4m3(v * inv) << (8 * e);
-                }
-                w[2 * cc + q] = (int)word;
-            }
-        }
-        *reinterpret_cast<i32x4_*>(dst + 16 * hf) = w;
-    }
-    return se;
-}
+// The dynamic LDS of one igemm_kernel instantiation, stated ONCE: the kernel takes its byte offsets from here, launch_cfg (igemm_plan.h) the
+// byte count, the svec row count and GS_OK.  [ring: S stages of A | W k-tiles (MODE 2: two halo images, then the weight ring); the epilogue's
+// fp16 C tile reuses it] [tab: 9 taps x BM pixel indices, MODE 1] [svec: bias + row vector, SVEC_ROWS samples x BN floats] [sca | scw | lnc -
+// F8: scales of A's rows, of W's rows; EX: rstd and -mean rstd per row, colsum per column]
+template <int BM, int BN, int NWM, int NWN, int MODE, int S, int HPA, bool F8, int EX> struct TileGeom {
+    static constexpr int NT = NWM * NWN * 64, WM = BM / NWM, CLD = BN + 8, KIB160 = 160 * 1024;
+    static constexpr int A_BYTES = BM * 128, W_BYTES = BN * 128, STAGE = A_BYTES + W_BYTES;
+    static constexpr int HALO_BYTES = HPA * 128, WRING_OFF = 2 * HALO_BYTES;             // MODE 2: one halo image; the weight ring behind two
+    static constexpr int RING = MODE == 2 ? WRING_OFF + S * W_BYTES : S * STAGE;
+    static constexpr int C_PASS = WM * CLD * 2, MAIN = RING > C_PASS ? RING : C_PASS;    // the C tile of one wave-row group
+    static constexpr int TAB_OFF = RING, TAB_BYTES = MODE == 1 ? 9 * BM * 4 : 0, SVEC_OFF = MAIN + TAB_BYTES;
+    static constexpr int SVEC_ROWS = MAIN + 4 * BN * 4 <= KIB160 ? 4 : 3;                // samples per tile the staged vectors can serve (sv_ok)
+    static constexpr bool SCALES = F8 || (EX & 7) != 0;
+    static constexpr int SCA_OFF = SVEC_OFF + 4 * BN * 4, SCW_OFF = SCA_OFF + BM * 4, LNC_OFF = SCW_OFF + BM * 4;
+    static constexpr int SCALE_BYTES = F8 ? (BM + BN) * 4 : (EX & 7) != 0 ? (2 * BM + BN) * 4 : 0;
+    static constexpr int LDS_BYTES = MAIN + TAB_BYTES + (SCALES ? 4 : SVEC_ROWS) * BN * 4 + SCALE_BYTES;
+    // whole C tile at once when it fits the ring's LDS, else one wave-row group per pass; GroupNorm statistics from the copy-out: scratch behind the C tile
+    static constexpr bool ONE_PASS = (size_t)BM * CLD * 2 <= (size_t)S * STAGE;
+    static constexpr int GS_OFF = (BM * CLD * 2 + 15) & ~15;
+    static constexpr bool GS_OK = MODE != 0 && ONE_PASS && !F8 && (NT / (BN / 8)) >= 1 && (size_t)GS_OFF + ((size_t)(NT / (BN / 8)) * BN + BN) * 8 <= (size_t)RING;
+    static_assert((!SCALES || SVEC_ROWS == 4) && (ONE_PASS ? BM * CLD * 2 : C_PASS) <= MAIN, "sca sits four svec rows behind svec; the C tile of a pass ends before svec");
+    static_assert((F8 ? SCW_OFF + BN * 4 : (EX & 7) != 0 ? LNC_OFF + BN * 4 : SVEC_OFF + SVEC_ROWS * BN * 4) == LDS_BYTES, "the last region ends at LDS_BYTES");
+    static_assert(LDS_BYTES <= KIB160, "tile does not fit the 160 KiB LDS");
+};
 
-// the range holding output column n (the last one starting at or left of it), -1: none
-__device__ __forceinline__ int mx8_range(const IGemmP& p, int n) {
-    int r = -1;
-    for (int q = 0; q < p.mx_nr; ++q)
-        if (p.mx_c0[q] <= n && (r < 0 || p.mx_c0[q] > p.mx_c0[r])) r = q;
-    return r;
+// ---- the tile table: every (BM, BN, NWM, NWN, S, HPA) the kernel is instantiated for; the planner and the dispatch (igemm_plan.h) walk it ----
+// Forms a tile is instantiated for (TileCfg.forms): the dispatch of each form launches exactly these rows, the planner picks among them.
+enum : unsigned {
+    F_DENSE = 1u << 0,      // MODE 0 (igemm_dense.hip)
+    F_CONV = 1u << 1,       // MODE 1 gather (igemm_conv.hip)
+    F_HALO = 1u << 2,       // MODE 2 halo-resident conv (igemm_halo.hip); hpa = rows of its halo image
+    F_EX = 1u << 3,         // extended epilogue (igemm_ex_{ln,st,qkv,all}.hip)
+    F_F8 = 1u << 4,         // fp8 operands (igemm_f8.hip)
+    F_ASTAT = 1u << 5,      // A-stationary (igemm_astat.hip), where pbe_astat_ok() holds
+    F_FORCED = 1u << 6,     // only through desc.tile_cfg / the tuned table, never by the heuristic
+};
+// s = ring depth in k-tiles of 64 (the weight ring of the halo / A-stationary tiles): the deepest that fits the LDS share of the tile's
+// workgroups per CU.  eff = relative per-FLOP efficiency of the tile when the chip is full (ordered by staged bytes per FLOP); eff_shallow
+// the same for shallow-K problems (< 10 k-tiles), dominated by the prologue / epilogue.  Both efficiency columns are fitted to the 472
+// measured shapes of profiles/r01_autotune_report.txt (the heuristic then costs 4 % over the best tile per shape, 12 % before the fit);
+// pbe_amd/tuned_mi355x.json overrides them per shape (desc.tile_cfg), so they only decide shapes outside the table.
+// f8 = the tile an fp8-operand problem runs when the planner picks this one (the fp8 form instantiates a subset of the dense tiles).
+struct TileCfg { int bm, bn, nwm, nwn, s, slots_per_cu; double eff, eff_shallow; int hpa; unsigned forms; int f8; };
+static constexpr TileCfg kTiles[] = {
+    {256, 256, 2, 4, 2, 1, 1.00, 0.82, 0, F_DENSE | F_CONV, 3},                     // 0: 128 KiB
+    {256, 128, 4, 2, 3, 1, 0.82, 0.72, 0, F_DENSE | F_CONV, 3},                     // 1: 144 KiB
+    {128, 256, 2, 4, 3, 1, 0.75, 0.66, 0, F_DENSE | F_CONV, 3},                     // 2: 144 KiB
+    {128, 128, 2, 2, 2, 2, 0.88, 1.00, 0, F_DENSE | F_CONV | F_EX | F_F8, 3},       // 3:  64 KiB, 4 waves: two workgroups per CU
+    {128, 64, 2, 2, 2, 3, 0.65, 0.84, 0, F_DENSE | F_CONV | F_EX | F_F8, 4},        // 4:  48 KiB
+    {64, 128, 2, 2, 2, 3, 0.65, 0.85, 0, F_DENSE | F_CONV | F_EX, 6},               // 5:  48 KiB
+    {64, 64, 2, 2, 2, 4, 0.60, 0.80, 0, F_DENSE | F_CONV | F_EX | F_F8, 6},         // 6:  32 KiB
+    {256, 320, 2, 4, 2, 1, 1.05, 0.80, 0, F_DENSE | F_CONV, 8},                     // 7: 144 KiB: N = 320 / 640 / 960 / 1280 without column padding (142 FLOP per staged byte)
+    {128, 320, 2, 4, 2, 1, 0.96, 0.95, 0, F_DENSE | F_CONV | F_EX | F_F8, 8},       // 8: 112 KiB: same, half the rows: fills the chip when M / 256 < 256 tiles
+    {128, 160, 2, 2, 2, 2, 0.90, 0.97, 0, F_DENSE | F_CONV | F_EX | F_F8, 9},       // 9:  72 KiB, 4 waves: two workgroups per CU overlap each other's prologue / epilogue
+    // halo-resident 3x3 conv tiles (stride 1, pad 1, image width 8 .. 128 = tile width, and the tile's bm pixels are whole rows of one
+    // image or a whole number of images - halo_rows(); any other map runs the gather tiles): only the weights stream per k-tile
+    {256, 160, 4, 2, 3, 1, 1.40, 1.40, 392, F_HALO, 9},                   // 10: 160 KiB: 256 pixels (4 rows at 64x64) x 160 channels, 8 waves, ping-pong
+    {128, 160, 4, 2, 3, 1, 1.20, 1.20, 264, F_HALO, 9},                   // 11: 128 KiB: 128 pixels x 160 channels
+    {128, 320, 2, 4, 2, 1, 1.25, 1.25, 264, F_HALO, 9},                   // 12: 149 KiB: 128 pixels x 320 channels
+    {256, 128, 4, 2, 3, 1, 1.30, 1.30, 392, F_HALO, 9},                   // 13: 148 KiB: channel counts that are multiples of 128 only, ping-pong
+    {128, 128, 4, 2, 3, 1, 1.10, 1.10, 392, F_HALO, 9},                   // 14: 148 KiB: one 128-pixel row of a 128-wide image (VAE)
+    // deep-ring forms of the small dense tiles, ONE workgroup per CU: for grids of <= 256 workgroups (M <= 2 048 rows) the second
+    // workgroup of a CU never arrives, and S = 2 then leaves one k-tile in flight per CU - a k-tile per DMA round trip
+    {128, 128, 2, 2, 4, 1, 0.50, 0.50, 0, F_DENSE | F_CONV | F_EX, 3},              // 15: 128 KiB
+    {128, 64, 2, 2, 4, 1, 0.40, 0.40, 0, F_DENSE | F_CONV | F_EX, 4},               // 16:  96 KiB
+    {64, 64, 2, 2, 4, 2, 0.38, 0.38, 0, F_DENSE | F_CONV | F_EX, 6},                // 17:  64 KiB
+    {128, 160, 2, 2, 4, 1, 0.52, 0.52, 0, F_DENSE | F_CONV | F_EX, 9},              // 18: 144 KiB
+    // A-stationary persistent tiles (igemm_astat.hip): K = 320 GEGLU projection with the LayerNorm fold, A block in registers, 4 waves,
+    // two workgroups per CU; only through desc.tile_cfg / the tuned table where pbe_astat_ok() holds
+    {128, 128, 4, 1, 3, 2, 0.0, 0.0, 0, F_ASTAT | F_FORCED, 9},           // 19: weight ring 48 KiB
+    {128, 160, 4, 1, 3, 2, 0.0, 0.0, 0, F_ASTAT | F_FORCED, 9},           // 20: weight ring 60 KiB (256 registers, 14 spilled)
+    // dense 8-wave tile with 160 columns: 6.5 LDS-DMA pieces per wave and k-tile against 40 MFMAs (the 4-wave 128x160 tile: 9)
+    {256, 160, 4, 2, 3, 1, 0.0, 0.0, 0, F_DENSE | F_FORCED, 9}};          // 21: 156 KiB
+static constexpr int kNCfg = sizeof(kTiles) / sizeof(kTiles[0]);
+static constexpr bool f8_column_ok() {      // every row maps to a tile the fp8 form instantiates
+    for (const TileCfg& t : kTiles)
+        if (!(kTiles[t.f8].forms & F_F8)) return false;
+    return true;
 }
-
-// V^T scale of block (sample b, channel c of the range, tokens tok .. tok + 31) at (b, h, tok / 32, d).  The last channel of a head also writes
-// the head's scale pad rows [D, DV) as 1.0 (pbe_attention_mx8 reads them: pad rows and the ones row): 8 bytes at a time (the scale rows
-// are 16-byte aligned, DV % 32 == 0, D % 8 == 0)
-__device__ __forceinline__ void mx8_vt_scale(const IGemmP& p, int r, int b, int c, int tok, int se) {
-    const int D = p.mx_D, DV = p.mx_DV;
-    const int h = c / D, d = c - h * D;
-    unsigned char* sp = p.mx_scale[r] + (((long)b * p.mx_H + h) * (p.mx_N >> 5) + (tok >> 5)) * DV;
-    sp[d] = (unsigned char)se;
-    if (d == D - 1)
-        for (int q = D; q < DV; q += 8) *reinterpret_cast<unsigned long long*>(sp + q) = 0x7f7f7f7f7f7f7f7full;
-}
-
-// V^T block (sample b, channel c of the range, 32 staged tokens from token tok): bytes row b H D + c, then its scale
-__device__ __forceinline__ void mx8_vt_block(const IGemmP& p, int r, const h16* src, int b, int c, int tok) {
-    const int se = mx8_block_lds(src, 32, p.mx_alpha[r], p.mx_data[r] + ((long)b * p.mx_H * p.mx_D + c) * p.mx_N + tok);
-    mx8_vt_scale(p, r, b, c, tok, se);
-}
-
-// The same block over a lane pair (l, l ^ 32) of one wave: half hf = l >> 5 holds tokens 16 hf .. 16 hf + 15, the amax meets over the pair
-// (a maximum: exact in any order), each half converts and stores its 16 bytes, the lower lane the scale - every lane of the wave busy where
-// a lane per block would leave half of them idle (the A-stationary tile's 32-channel passes)
-__device__ __forceinline__ void mx8_vt_block_pair(const IGemmP& p, int r, const h16* src, int b, int c, int tok, int hf) {
-    typedef int i32x4_ __attribute__((ext_vector_type(4)));
-    const float al = p.mx_alpha[r];
-    const h16x8 x[2] = {*reinterpret_cast<const h16x8*>(src + 16 * hf), *reinterpret_cast<const h16x8*>(src + 16 * hf + 8)};
-    float amax = 0.f;
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf((float)x[c2][e] * al));
-    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-    const int se = mx8_scale_exp(amax);
-    const float inv = __uint_as_float((unsigned)(254 - se) << 23);                          // 1 / 2^(se - 127), exact
-    i32x4_ w;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        unsigned word = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) word |= mx8_e4m3((float)x[q >> 1][4 * (q & 1) + e] * al * inv) << (8 * e);
-        w[q] = (int)word;
-    }
-    *reinterpret_cast<i32x4_*>(p.mx_data[r] + ((long)b * p.mx_H * p.mx_D + c) * p.mx_N + tok + 16 * hf) = w;
-    if (hf == 0) mx8_vt_scale(p, r, b, c, tok, se);
-}
-
-// TOKENS blocks of `rows` staged rows (LDS row stride ld halfs, output rows mrow0 ..) x `cols` columns from output column x0, all inside
-// range r: block (h, j) = columns h D + 32 j .. + min(32, D - 32 j) of the range; the head's last block also writes the all-padding block
-// behind it (DP / 32 - blocks per head <= 1: zero bytes, scale 1.0).  Threads t0, t0 + nt, ... take one (row, block) each, blocks fastest.
-__device__ __forceinline__ void mx8_token_blocks(const IGemmP& p, int r, const h16* st, int ld, int rows, int x0, int cols, int mrow0, int t0, int nt) {
-    const int D = p.mx_D, Hh = p.mx_H, Nt = p.mx_N, DP = p.mx_DP;
-    const int nbh = (D + 31) >> 5, npb = DP >> 5;
-    auto nblk = [&](int x) { const int hh = x / D; return hh * nbh + (x - hh * D + 31) / 32; };           // blocks left of column x
-    const int c0 = p.mx_c0[r], rel0 = x0 - c0, rel1 = min(x0 + cols, c0 + Hh * D) - c0;
-    if (rel1 <= rel0) return;
-    const int b0 = nblk(rel0), cnt = nblk(rel1) - b0;
-    const float al = p.mx_alpha[r];
-    for (int idx = t0; idx < rows * cnt; idx += nt) {
-        const int row = idx / cnt, gb = b0 + (idx - row * cnt);
-        const int m = mrow0 + row;
-        if (m >= p.M) continue;
-        const int h = gb / nbh, j = gb - h * nbh, len = min(32, D - 32 * j);
-        unsigned char* dst = p.mx_data[r] + (long)m * Hh * DP + h * DP + 32 * j;
-        const int se = mx8_block_lds(st + row * ld + (c0 + h * D + 32 * j - x0), len, al, dst);
-        const int b = m / Nt, n = m - b * Nt;
-        unsigned char* sp = p.mx_scale[r] + (((long)b * Hh + h) * npb + j) * Nt + n;
-        sp[0] = (unsigned char)se;
-        if (j == nbh - 1 && npb > nbh) {
-            typedef int i32x4_ __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<i32x4_*>(dst + 32) = (i32x4_){0, 0, 0, 0};
-            *reinterpret_cast<i32x4_*>(dst + 48) = (i32x4_){0, 0, 0, 0};
-            sp[Nt] = 127;
-        }
-    }
-}
+static_assert(f8_column_ok(), "kTiles: an f8 column names a tile without F_F8");
 
 // (the 4-wave tiles live two workgroups per CU - two waves per SIMD, 256 registers each.  The V^T form of the 128x160 tile would take 268
 //  and halve the occupancy: its bound is declared; the LayerNorm-only (252) and statistics-only (228) forms fit unconstrained and
@@ -362,15 +153,13 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     // (A "ping-pong" form of the main loop for the 8-wave tiles - wave groups 0-3 / 4-7 offset by one barrier, [fragment reads +
     //  DMA issue | MFMAs] with two barriers per k-tile - was built and measured on every conv / GEMM shape of the path: bit-identical
     //  output, 7 % slower on the conv class (780.9 -> 724.0 TFLOP/s), 2 % slower on the GEMM class.  profiles/r02_ab_pingpong_rejected.txt.)
+    using G = TileGeom<BM, BN, NWM, NWN, MODE, S, HPA, F8, EX>;      // the LDS layout
     constexpr int NW = NWM * NWN, NT = NW * 64;
     constexpr int D = S - 1;
     constexpr int WM = BM / NWM, WN = BN / NWN, TM = WM / 16, TN = WN / 16;
-    constexpr int A_BYTES = BM * 128, W_BYTES = BN * 128, STAGE = A_BYTES + W_BYTES;
+    constexpr int A_BYTES = G::A_BYTES, W_BYTES = G::W_BYTES, STAGE = G::STAGE, CLD = G::CLD;
     constexpr int PA = BM / 8, PW = BN / 8;           // 8-row x 128-byte DMA pieces (1 KiB = one wave instruction)
     constexpr int LA = PA / NW, LW = (PW + NW - 1) / NW, LPT = LA + LW;
-    constexpr int CLD = BN + 8;
-    // MODE 2 LDS: [halo image 0][halo image 1][weight ring S x BN rows]
-    constexpr int RING = MODE == 2 ? 2 * HPA * 128 + S * W_BYTES : S * STAGE;
     static_assert(S >= 2 && S <= 4 && PA % NW == 0 && BM % 16 == 0 && BN % 16 == 0, "A pieces must divide over the waves (weight pieces may be padded)");
     static_assert(MODE != 2 || (HPA % 8 == 0 && HPA >= BM), "halo image must hold the tile");
     static_assert(EXF == 0 || (MODE == 0 && !F8), "extended epilogue: dense fp16 tiles only");
@@ -432,10 +221,10 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     // the shifted re-reads hit L2 instead of going back to the Infinity Cache / HBM (measured: tap-major order re-fetched the
     // input 9x beyond L2).  The tap -> input-pixel map of this tile's BM rows is built once into LDS:
     // tab[tap][row] = pixel index, or -1 outside the (virtual) image.
-    int* tab = reinterpret_cast<int*>(smem + RING);
+    int* tab = reinterpret_cast<int*>(smem + G::TAB_OFF);
     // Epilogue vectors of this tile, staged ONCE (their global latency hides under the first DMA tile):
     // svec[s][c] = bias[n0 + c] + rowvec[first sample of the tile + s][n0 + c], up to 4 samples per tile.
-    float* svec = reinterpret_cast<float*>(smem + (RING > WM * CLD * 2 ? RING : WM * CLD * 2) + (MODE == 1 ? 9 * BM * 4 : 0));
+    float* svec = reinterpret_cast<float*>(smem + G::SVEC_OFF);
     const int sv_ns = p.sv_ns;                       // samples per tile (tile is sample-aligned when sv_ok)
     if (MODE == 1) {
         const int hw = p.hw, Hv = p.H << p.ups, Wv = p.Wd << p.ups;
@@ -572,9 +361,9 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     const int rsw = (fq ^ (fr & 7)) << 4;             // byte offset of k-step 0's chunk; k-step 1 is rsw ^ 64
     const int a_rd = (wm * WM + fr) * 128, w_rd = (wn * WN + fr) * 128;
 
-    float* sca = svec + 4 * BN;                       // F8: per-row scale of A for this tile's rows, then per-column scale (W's rows)
-    float* scw = sca + BM;                            // EX + LayerNorm fold: sca[row] = rstd, scw[row] = -mean * rstd, lnc[col] = colsum of W * gamma
-    float* lnc = scw + BM;
+    float* sca = reinterpret_cast<float*>(smem + G::SCA_OFF);      // F8: per-row scale of A for this tile's rows, then per-column scale (W's rows)
+    float* scw = reinterpret_cast<float*>(smem + G::SCW_OFF);      // EX + LayerNorm fold: sca[row] = rstd, scw[row] = -mean * rstd, lnc[col] = colsum of W * gamma
+    float* lnc = reinterpret_cast<float*>(smem + G::LNC_OFF);
     auto stage_svec = [&]() {
         if constexpr (F8) {
             for (int idx = tid; idx < BM + BN; idx += NT) {
@@ -627,7 +416,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     if constexpr (MODE == 2) {
         constexpr int PAH = HPA / 8, LAH = (PAH + NW - 1) / NW;
         unsigned char* abuf = smem;
-        unsigned char* wring = smem + 2 * HPA * 128;
+        unsigned char* wring = smem + G::WRING_OFF;
         // Halo image of one (sub-)image of the tile: TH + 2 rows of TW + 1 pixels + 1.  A tile spans the image's whole width, so
         // x = -1 and x = TW are always padding: the zero row right of image row y IS the zero row left of image row y + 1
         // (row stride TW + 1 instead of TW + 2; 4 rows of 64 pixels: 391 halo rows instead of 396 - what lets a third weight slot
@@ -676,7 +465,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
         auto issue_a = [&](int blk, int buf) {
             if (p.C2 && blk * 64 == p.C1) halo_base(blk);
 #pragma unroll
-            for (int i = 0; i < LAH; ++i) issue_a1(buf * (HPA * 128), i);
+            for (int i = 0; i < LAH; ++i) issue_a1(buf * G::HALO_BYTES, i);
         };
         auto issue_w1 = [&](int kt, int slot, int i) {
             PBE_GLDS16(w_row[i] + (long)kt * 64, wring + slot * W_BYTES + min(wave + NW * i, PW - 1) * 1024);
@@ -728,7 +517,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
                 return (trow - 1) * HW2 + (tap - 3 * trow - 1);
             };
             auto frag_addrs = [&](int blk_n, int tap_n, int slot_n) {      // in one go (prologue only)
-                const int shift = tile_shift(tap_n), abase = ((blk_n - blk0) & 1) * (HPA * 128), wb = 2 * HPA * 128 + slot_n * W_BYTES;
+                const int shift = tile_shift(tap_n), abase = ((blk_n - blk0) & 1) * G::HALO_BYTES, wb = G::WRING_OFF + slot_n * W_BYTES;
 #pragma unroll
                 for (int j = 0; j < TM; ++j) {
                     const int ar = hc[j] + shift;
@@ -801,7 +590,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
             //   next block.
             auto block = [&](auto LASTC, int blk) {
                 constexpr bool LAST = decltype(LASTC)::value;
-                const int abase = ((blk - blk0) & 1) * (HPA * 128), abase_o = (HPA * 128) - abase;
+                const int abase = ((blk - blk0) & 1) * G::HALO_BYTES, abase_o = G::HALO_BYTES - abase;
                 const h16* hbase = zsrc;                   // source of halo row 0's chunk for block blk + 1
                 long hcs = 0;
                 if (!LAST) {
@@ -846,19 +635,12 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
                         //  hoisted out of the block loop into 70 more registers and the kernel spills)
                         int hw2 = HW2;
                         asm volatile("" : "+s"(hw2));
-                        mfmas((trow - 1) * hw2 + (tn - 3 * trow - 1), tap == 8 ? abase_o : abase, 2 * HPA * 128 + ((tap + 1) % 3) * W_BYTES);
+                        mfmas((trow - 1) * hw2 + (tn - 3 * trow - 1), tap == 8 ? abase_o : abase, G::WRING_OFF + ((tap + 1) % 3) * W_BYTES);
                     }
                     PBE_ACC(acc_m_);
                     PBE_ACC_T0();
-#if PBE_RACE_MUTANT == 2
-                    if (grp == 0) {                                                                  // as if W(kt + 1) may fly too, once per slice
-                        if (tap == 8 && blk == blk0 && w) wait_vmcnt<2 * kPWG>();
-                        else if (w) wait_vmcnt<kPWG>();
-                        else wait_vmcnt<0>();
-                    }
-#else
-                    if (grp == 0) { if (w) wait_vmcnt<kPWG>(); else wait_vmcnt<0>(); }      // W(kt + 1) landed; this period's tile may fly
-#endif
+                    // W(kt + 1) landed; this period's tile may fly (mutant 2: as if W(kt + 1) may fly too, once per slice)
+                    if (grp == 0) { if (PBE_RACE_MUTANT == 2 && tap == 8 && blk == blk0 && w) wait_vmcnt<2 * kPWG>(); else if (w) wait_vmcnt<kPWG>(); else wait_vmcnt<0>(); }
                     PBE_ACC(acc_w_);
                     __builtin_amdgcn_sched_barrier(0);
                     PBE_ACC_T0();
@@ -880,7 +662,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
         } else {
             int slot_rd = 0, slot_wr = D % S;
             for (int blk = blk0; blk < blk1; ++blk) {
-                const unsigned char* ab = abuf + ((blk - blk0) & 1) * (HPA * 128);
+                const unsigned char* ab = abuf + ((blk - blk0) & 1) * G::HALO_BYTES;
                 const bool next_a = blk + 1 < blk1;
 #pragma unroll 1
                 for (int tap = 0; tap < 9; ++tap) {          // (not unrolled: 9 copies of the body cost registers and 30 000 lines of ISA)
@@ -894,37 +676,10 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
                     const int wleft = min(nk2 - 1 - kt, D - 1);
                     const bool a_young = next_a && tap >= 1 && tap <= D;
                     PBE_ACC_T0();
-#if PBE_RACE_MUTANT == 2
-                    if (D == 1 ? kt != blk0 * 9 + PBE_RACE_MUTANT_KT : kt < blk0 * 9 + PBE_RACE_MUTANT_KT) {
-                        if (a_young) {
-                            if (D >= 3 && wleft >= 2) wait_vmcnt<2 * LW + LAH>();
-                            else if (D >= 2 && wleft >= 1) wait_vmcnt<LW + LAH>();
-                            else wait_vmcnt<LAH>();
-                        } else {
-                            if (D >= 3 && wleft >= 2) wait_vmcnt<2 * LW>();
-                            else if (D >= 2 && wleft >= 1) wait_vmcnt<LW>();
-                            else wait_vmcnt<0>();
-                        }
-                    } else if (a_young) {                    // as if wleft + 1 weight tiles may stay in flight: W(kt) itself
-                        if (D >= 3 && wleft >= 2) wait_vmcnt<(D >= 3 ? 3 : 1) * LW + LAH>();
-                        else if (D >= 2 && wleft >= 1) wait_vmcnt<(D >= 2 ? 2 : 1) * LW + LAH>();
-                        else wait_vmcnt<LW + LAH>();
-                    } else {
-                        if (D >= 3 && wleft >= 2) wait_vmcnt<(D >= 3 ? 3 : 1) * LW>();
-                        else if (D >= 2 && wleft >= 1) wait_vmcnt<(D >= 2 ? 2 : 1) * LW>();
-                        else wait_vmcnt<LW>();
-                    }
-#else
-                    if (a_young) {
-                        if (D >= 3 && wleft >= 2) wait_vmcnt<2 * LW + LAH>();
-                        else if (D >= 2 && wleft >= 1) wait_vmcnt<LW + LAH>();
-                        else wait_vmcnt<LAH>();
-                    } else {
-                        if (D >= 3 && wleft >= 2) wait_vmcnt<2 * LW>();
-                        else if (D >= 2 && wleft >= 1) wait_vmcnt<LW>();
-                        else wait_vmcnt<0>();
-                    }
-#endif
+                    const bool shipped = PBE_RACE_MUTANT != 2 || (D == 1 ? kt != blk0 * 9 + PBE_RACE_MUTANT_KT : kt < blk0 * 9 + PBE_RACE_MUTANT_KT);
+                    if (shipped) { if (a_young) ring_wait<LW, LAH, D>(wleft); else ring_wait<LW, 0, D>(wleft); }
+                    else if (a_young) ring_wait<LW, LAH, D, 1>(wleft);      // as if wleft + 1 weight tiles may stay in flight: W(kt) itself
+                    else ring_wait<LW, 0, D, 1>(wleft);
                     PBE_ACC(acc_w_);
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     PBE_ACC_T0();
@@ -987,19 +742,9 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
 #endif
         const int rem = min(nk - 1 - kt, D - 1);     // later tiles that may stay in flight
         PBE_ACC_T0();
-#if PBE_RACE_MUTANT == 1
-        if (D == 1 ? kt == kt0 + PBE_RACE_MUTANT_KT : kt >= kt0 + PBE_RACE_MUTANT_KT) {      // as if one more tile may stay in flight: tile kt itself
-            if (D >= 3 && rem >= 2) wait_vmcnt<(D >= 3 ? 3 : 1) * LPT>();
-            else if (D >= 2 && rem >= 1) wait_vmcnt<(D >= 2 ? 2 : 1) * LPT>();
-            else wait_vmcnt<LPT>();
-        } else if (D >= 3 && rem >= 2) wait_vmcnt<2 * LPT>();
-        else if (D >= 2 && rem >= 1) wait_vmcnt<LPT>();
-        else wait_vmcnt<0>();
-#else
-        if (D >= 3 && rem >= 2) wait_vmcnt<2 * LPT>();
-        else if (D >= 2 && rem >= 1) wait_vmcnt<LPT>();
-        else wait_vmcnt<0>();
-#endif
+        const bool relaxed = PBE_RACE_MUTANT == 1 && (D == 1 ? kt == kt0 + PBE_RACE_MUTANT_KT : kt >= kt0 + PBE_RACE_MUTANT_KT);
+        if (relaxed) ring_wait<LPT, 0, D, 1>(rem);      // as if one more tile may stay in flight: tile kt itself
+        else ring_wait<LPT, 0, D>(rem);
         PBE_ACC(acc_w_);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         PBE_ACC_T0();
@@ -1077,12 +822,8 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     };
     const h16* Rb = p.resid ? p.resid + bz * p.sR : nullptr;
     constexpr int CPR = BN / 8;
-    // whole C tile at once when it fits the ring's LDS, else one wave-row group per pass
-    constexpr bool ONE_PASS = (size_t)BM * CLD * 2 <= (size_t)S * STAGE;
+    constexpr bool ONE_PASS = G::ONE_PASS, GS_OK = G::GS_OK;      // whole C tile per pass; GroupNorm statistics from the copy-out (TileGeom)
     constexpr int NG = ONE_PASS ? 1 : NWM;            // passes
-    // GroupNorm statistics from the copy-out (convs, whole-tile epilogues): scratch behind the C tile, inside the ring's LDS
-    constexpr int GS_OFF = (BM * CLD * 2 + 15) & ~15;
-    constexpr bool GS_OK = MODE != 0 && ONE_PASS && !F8 && (NT / (BN / 8)) >= 1 && (size_t)GS_OFF + ((size_t)(NT / (BN / 8)) * BN + BN) * 8 <= (size_t)RING;
     constexpr int GR = ONE_PASS ? BM : WM;            // rows per pass
     // The register -> LDS half has a compile-time FAST path (bias / row vector staged in svec, one sample per tile, no
     // per-row bias): the generic form (per-element bounds checks, global bias loads and row-vector gathers with an
@@ -1310,7 +1051,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
                 // ...): 8 column sums + 8 sums of squares in registers, then a fixed-order fold over the row slots and over a group's columns
                 // through LDS (no atomics: bit-reproducible).  Row batches of 4: the residual loads of a batch are issued together.
                 constexpr int RSL = NT / CPR, GB = 4;
-                float* red = reinterpret_cast<float*>(smem + GS_OFF);
+                float* red = reinterpret_cast<float*>(smem + G::GS_OFF);
                 const int slot = tid / CPR, ch = tid - slot * CPR, n = n0 + ch * 8;
                 float ca[8], cq[8];
 #pragma unroll
@@ -1491,317 +1232,3 @@ static __global__ void __launch_bounds__(256) splitk_reduce_kernel(const IGemmP 
     }
     *reinterpret_cast<h16x4*>(p.C + (long)m * p.ldc + n) = o;
 }
-
-// ---- host side --------------------------------------------------------------------------------
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-struct Plan { int cfg; int splits; };
-// Forms a tile is instantiated for (TileCfg.forms): the dispatch of each form launches exactly these rows, the planner picks among them.
-enum : unsigned {
-    F_DENSE = 1u << 0,      // MODE 0 (igemm_dense.hip)
-    F_CONV = 1u << 1,       // MODE 1 gather (igemm_conv.hip)
-    F_HALO = 1u << 2,       // MODE 2 halo-resident conv (igemm_halo.hip); hpa = rows of its halo image
-    F_EX = 1u << 3,         // extended epilogue (igemm_ex_{ln,st,qkv,all}.hip)
-    F_F8 = 1u << 4,         // fp8 operands (igemm_f8.hip)
-    F_ASTAT = 1u << 5,      // A-stationary (igemm_astat.hip), where pbe_astat_ok() holds
-    F_FORCED = 1u << 6,     // only through desc.tile_cfg / the tuned table, never by the heuristic
-};
-// s = ring depth in k-tiles of 64 (the weight ring of the halo / A-stationary tiles): the deepest that fits the LDS share of the tile's
-// workgroups per CU.  eff = relative per-FLOP efficiency of the tile when the chip is full (ordered by staged bytes per FLOP); eff_shallow
-// the same for shallow-K problems (< 10 k-tiles), dominated by the prologue / epilogue.  Both efficiency columns are fitted to the 472
-// measured shapes of profiles/r01_autotune_report.txt (the heuristic then costs 4 % over the best tile per shape, 12 % before the fit);
-// pbe_amd/tuned_mi355x.json overrides them per shape (desc.tile_cfg), so they only decide shapes outside the table.
-// f8 = the tile an fp8-operand problem runs when the planner picks this one (the fp8 form instantiates a subset of the dense tiles).
-struct TileCfg { int bm, bn, nwm, nwn, s, slots_per_cu; double eff, eff_shallow; int hpa; unsigned forms; int f8; };
-static constexpr TileCfg kTiles[] = {
-    {256, 256, 2, 4, 2, 1, 1.00, 0.82, 0, F_DENSE | F_CONV, 3},                     // 0: 128 KiB
-    {256, 128, 4, 2, 3, 1, 0.82, 0.72, 0, F_DENSE | F_CONV, 3},                     // 1: 144 KiB
-    {128, 256, 2, 4, 3, 1, 0.75, 0.66, 0, F_DENSE | F_CONV, 3},                     // 2: 144 KiB
-    {128, 128, 2, 2, 2, 2, 0.88, 1.00, 0, F_DENSE | F_CONV | F_EX | F_F8, 3},       // 3:  64 KiB, 4 waves: two workgroups per CU
-    {128, 64, 2, 2, 2, 3, 0.65, 0.84, 0, F_DENSE | F_CONV | F_EX | F_F8, 4},        // 4:  48 KiB
-    {64, 128, 2, 2, 2, 3, 0.65, 0.85, 0, F_DENSE | F_CONV | F_EX, 6},               // 5:  48 KiB
-    {64, 64, 2, 2, 2, 4, 0.60, 0.80, 0, F_DENSE | F_CONV | F_EX | F_F8, 6},         // 6:  32 KiB
-    {256, 320, 2, 4, 2, 1, 1.05, 0.80, 0, F_DENSE | F_CONV, 8},                     // 7: 144 KiB: N = 320 / 640 / 960 / 1280 without column padding (142 FLOP per staged byte)
-    {128, 320, 2, 4, 2, 1, 0.96, 0.95, 0, F_DENSE | F_CONV | F_EX | F_F8, 8},       // 8: 112 KiB: same, half the rows: fills the chip when M / 256 < 256 tiles
-    {128, 160, 2, 2, 2, 2, 0.90, 0.97, 0, F_DENSE | F_CONV | F_EX | F_F8, 9},       // 9:  72 KiB, 4 waves: two workgroups per CU overlap each other's prologue / epilogue
-    // halo-resident 3x3 conv tiles (stride 1, pad 1, image width 8 .. 128 = tile width, and the tile's bm pixels are whole rows of one
-    // image or a whole number of images - halo_rows(); any other map runs the gather tiles): only the weights stream per k-tile
-    {256, 160, 4, 2, 3, 1, 1.40, 1.40, 392, F_HALO, 9},                   // 10: 160 KiB: 256 pixels (4 rows at 64x64) x 160 channels, 8 waves, ping-pong
-    {128, 160, 4, 2, 3, 1, 1.20, 1.20, 264, F_HALO, 9},                   // 11: 128 KiB: 128 pixels x 160 channels
-    {128, 320, 2, 4, 2, 1, 1.25, 1.25, 264, F_HALO, 9},                   // 12: 149 KiB: 128 pixels x 320 channels
-    {256, 128, 4, 2, 3, 1, 1.30, 1.30, 392, F_HALO, 9},                   // 13: 148 KiB: channel counts that are multiples of 128 only, ping-pong
-    {128, 128, 4, 2, 3, 1, 1.10, 1.10, 392, F_HALO, 9},                   // 14: 148 KiB: one 128-pixel row of a 128-wide image (VAE)
-    // deep-ring forms of the small dense tiles, ONE workgroup per CU: for grids of <= 256 workgroups (M <= 2 048 rows) the second
-    // workgroup of a CU never arrives, and S = 2 then leaves one k-tile in flight per CU - a k-tile per DMA round trip
-    {128, 128, 2, 2, 4, 1, 0.50, 0.50, 0, F_DENSE | F_CONV | F_EX, 3},              // 15: 128 KiB
-    {128, 64, 2, 2, 4, 1, 0.40, 0.40, 0, F_DENSE | F_CONV | F_EX, 4},               // 16:  96 KiB
-    {64, 64, 2, 2, 4, 2, 0.38, 0.38, 0, F_DENSE | F_CONV | F_EX, 6},                // 17:  64 KiB
-    {128, 160, 2, 2, 4, 1, 0.52, 0.52, 0, F_DENSE | F_CONV | F_EX, 9},              // 18: 144 KiB
-    // A-stationary persistent tiles (igemm_astat.hip): K = 320 GEGLU projection with the LayerNorm fold, A block in registers, 4 waves,
-    // two workgroups per CU; only through desc.tile_cfg / the tuned table where pbe_astat_ok() holds
-    {128, 128, 4, 1, 3, 2, 0.0, 0.0, 0, F_ASTAT | F_FORCED, 9},           // 19: weight ring 48 KiB
-    {128, 160, 4, 1, 3, 2, 0.0, 0.0, 0, F_ASTAT | F_FORCED, 9},           // 20: weight ring 60 KiB (256 registers, 14 spilled)
-    // dense 8-wave tile with 160 columns: 6.5 LDS-DMA pieces per wave and k-tile against 40 MFMAs (the 4-wave 128x160 tile: 9)
-    {256, 160, 4, 2, 3, 1, 0.0, 0.0, 0, F_DENSE | F_FORCED, 9}};          // 21: 156 KiB
-static constexpr int kNCfg = sizeof(kTiles) / sizeof(kTiles[0]);
-static constexpr bool f8_column_ok() {      // every row maps to a tile the fp8 form instantiates
-    for (const TileCfg& t : kTiles)
-        if (!(kTiles[t.f8].forms & F_F8)) return false;
-    return true;
-}
-static_assert(f8_column_ok(), "kTiles: an f8 column names a tile without F_F8");
-
-#ifdef PBE_STAMPS
-extern unsigned long long* g_pbe_stamps;
-#endif
-extern int g_pbe_force_cfg;     // (defined in igemm.hip) pbe_tune(1, cfg index [| splits << 8]) forces a tile config (and split-K factor); -1 = heuristic
-extern int g_pbe_allow_splitk;  // pbe_tune(2, 0/1)
-
-// k-tiles of 64 per split-K granule: a halo tile splits at channel-block boundaries (9 taps)
-static inline int no_empty_slices(int nk, int granule, int s) {
-    const int units = (nk + granule - 1) / granule;
-    if (s > units) s = units;
-    if (s < 2) return 1;
-    const int per = (units + s - 1) / s;
-    return (units + per - 1) / per;
-}
-
-// Split-K at all: batch 1, a workspace, and the 4-column rows of C (and the residual) the reduce kernel writes (reads)
-static inline bool splitk_ok(const IGemmP& p, int batch) {
-    return g_pbe_allow_splitk && batch == 1 && p.ws && !(p.N & 3) && !(p.ldc & 3) && !(p.resid && (p.ldr & 3));
-}
-
-// Clamp a split-K factor to what the problem allows: >= 4 k-tiles of 64 per slice, slabs fit the workspace, no empty slice
-static int clamp_splits(const IGemmP& p, const TileCfg& c, size_t ws_bytes, int s) {
-    const int nk = (p.K + 63) >> 6;
-    if (s > nk / 4) s = nk / 4;
-    while (s > 1 && (size_t)s * p.M * p.N * sizeof(float) > ws_bytes) --s;
-    return no_empty_slices(nk, c.hpa ? 9 : 1, s);
-}
-
-static int splits_for(const IGemmP& p, const TileCfg& c, int batch, size_t ws_bytes, long tiles) {
-    if (!splitk_ok(p, batch)) return 1;
-    const int nk = (p.K + 63) >> 6;                          // k-tiles of 64
-    const long slots = 256L * c.slots_per_cu;
-    if (tiles * 4 > slots * 3 || nk < 8) return 1;           // grid already fills >= 75 % of the chip
-    const int s = (int)((slots * 5 / 4 + tiles - 1) / tiles);
-    return clamp_splits(p, c, ws_bytes, s > 32 ? 32 : s);
-}
-
-// Can this conv run as a halo-resident tile of bm pixels with a halo image of hpa rows?  Returns the image rows per tile (0: no).
-static int halo_rows(const IGemmP& p, int mode, int bm, int hpa) {
-    if (mode != 1 || p.cstride != 1 || p.pad != 1 || p.ups || p.phase || p.cb != 64) return 0;
-    const int W = p.Wd, H = p.H;
-    if (W < 8 || W > 128 || (W & (W - 1)) || bm % W || (p.M % bm)) return 0;
-    const int th = bm / W < H ? bm / W : H;
-    if (H % th || bm % (th * W)) return 0;                        // a tile is whole rows of one image or a whole number of images:
-    const int nsub = bm / (th * W);                               // whole images per tile when the image is smaller than the tile
-    if (nsub > 1 && th != H) return 0;                            // the kernel derives image and row of a pixel from nsub * th * W == bm
-    if (nsub * ((th + 2) * (W + 1) + 1) > hpa) return 0;       // halo rows: row stride W + 1 (shared zero column) + 1
-    return th;
-}
-
-bool pbe_astat_ok(const IGemmP& p, int batch, int cfg);      // igemm_astat.hip: can tile 19 / 20 run this problem?
-
-// MX-fp8 copy-out (IGemmP.mx_*): can tile t write its blocks without any 32-element MX block crossing a tile boundary?  Every range starts
-// on a column tile, TOKENS ranges end on one too, every column-tile boundary inside a TOKENS range is a block boundary (h D + 32 j) - at
-// half-tile granularity for the A-stationary tile, whose q|k rows leave BN / 2 columns at a time - and V^T blocks of 32 tokens start on
-// 32-token boundaries (rows: every tile height is a multiple of 32; columns of the channel-row form: every tile width is).
-static inline bool mx_tile_ok(const IGemmP& p, const TileCfg& t) {
-    if (t.bm % 32 || t.bn % 32) return false;
-    if (p.mx_crow) return true;
-    const int D = p.mx_D, w = (t.forms & F_ASTAT) ? t.bn / 2 : t.bn;
-    for (int r = 0; r < p.mx_nr; ++r) {
-        if (p.mx_c0[r] % t.bn) return false;
-        if (p.mx_layout[r] != PBE_MX8_TOKENS) continue;
-        const int width = p.mx_H * D;
-        if ((p.mx_c0[r] + width) % t.bn && p.mx_c0[r] + width != p.N) return false;
-        for (int x = w; x < width; x += w)
-            if ((x % D) % 32) return false;
-    }
-    return true;
-}
-static inline bool ex_needed(const IGemmP& p) { return p.alpha_cols > 0 || p.ln_stat || p.rstat || p.vt; }
-
-// V^T columns start on a column tile (igemm_kernel's vtile): a tile with n0 < vt_col0 stores ALL its columns to C.  The widths the
-// extended-epilogue heuristic can choose among: is one of them a divisor of vt_col0?  (A requested tile that cannot run the problem
-// falls back to the heuristic, and the forced-only A-stationary tiles are as wide as streaming ones, so this decides every tile_cfg.)
-static inline bool vt_tile_exists(int vt_col0) {
-    for (const TileCfg& t : kTiles)
-        if ((t.forms & F_EX) && !(t.forms & F_FORCED) && vt_col0 % t.bn == 0) return true;
-    return false;
-}
-static inline const char* ex_tile_widths(char* buf, size_t n) {      // "64, 128, 160, 320": the distinct widths above, ascending, for error texts
-    size_t len = 0;
-    buf[0] = 0;
-    for (int last = 0;;) {
-        int next = 0;
-        for (const TileCfg& t : kTiles)
-            if ((t.forms & F_EX) && !(t.forms & F_FORCED) && t.bn > last && (!next || t.bn < next)) next = t.bn;
-        if (!next || len + 8 > n) return buf;
-        len += snprintf(buf + len, n - len, "%s%d", len ? ", " : "", next);
-        last = next;
-    }
-}
-
-// want_cfg: -1 = heuristic; else (tile config index) | (split-K factor << 8), factor 0 = heuristic factor for that tile.
-// A requested factor is clamped to what the problem allows (batch 1, >= 4 k-tiles of 64 per slice, slabs fit the workspace).
-// (the developer knobs g_pbe_force_cfg / g_pbe_allow_splitk are READ here and never written outside pbe_tune: a caller that must
-//  not split passes ws_bytes = 0, the fallback below passes use_force = false)
-static Plan plan_igemm(const IGemmP& p, int batch, size_t ws_bytes, int want_cfg, int mode, bool use_force = true) {
-    Plan best{3, 1};
-    double best_score = -1.0;
-    const int want = (use_force && g_pbe_force_cfg >= 0) ? g_pbe_force_cfg : want_cfg;
-    const int forced = (want >= 0 && (want & 255) < kNCfg) ? (want & 255) : -1;
-    const int want_splits = want >= 0 ? (want >> 8) & 255 : 0;
-    const bool shallow = ((p.K + 63) >> 6) < 10;
-    // candidates: the tiles of the problem's form (fp8 operands score the dense tiles and run the f8 column of the pick, below)
-    const unsigned forms = mode == 1 ? F_CONV | F_HALO : ex_needed(p) ? F_EX | F_ASTAT : F_DENSE;
-    for (int c = 0; c < kNCfg; ++c) {
-        if (forced >= 0 && c != forced) continue;
-        const TileCfg& t = kTiles[c];
-        if (!(t.forms & forms) || ((t.forms & F_FORCED) && forced != c)) continue;
-        if ((t.forms & F_ASTAT) && !pbe_astat_ok(p, batch, c)) continue;
-        if (p.vt && p.vt_col0 % t.bn) continue;                              // extended epilogue: V^T columns start on a tile
-        if (p.mx_nr && !mx_tile_ok(p, kTiles[p.sa ? t.f8 : c])) continue;    // MX-fp8 copy-out: the tile that launches keeps every block whole
-        if (t.hpa && !halo_rows(p, mode, t.bm, t.hpa)) continue;              // a forced halo tile that does not apply falls back below
-        if (t.hpa && p.N % 8) continue;
-        const long tm = (p.M + t.bm - 1) / t.bm, tn = (p.N + t.bn - 1) / t.bn;
-        const long tiles = tm * tn * batch;
-        const int sp = forced >= 0 && want_splits > 0 ? (splitk_ok(p, batch) ? clamp_splits(p, t, ws_bytes, want_splits) : 1)
-                                                      : splits_for(p, t, batch, ws_bytes, tiles);
-        const double useful = (double)p.M * p.N * batch / ((double)tiles * t.bm * t.bn);
-        const double blocks = (double)tiles * sp, slots = 256.0 * t.slots_per_cu;
-        const double rounds = (double)((long)((blocks + slots - 1) / slots));
-        const double quant = blocks / (rounds * slots);
-        const double split_cost = sp > 1 ? 0.93 : 1.0;        // slab write + reduce launch
-        const double score = (shallow ? t.eff_shallow : t.eff) * useful * (0.30 + 0.70 * quant) * split_cost;
-        if (score > best_score) { best_score = score; best = Plan{c, sp}; }
-    }
-    if (best_score < 0.0 && forced >= 0)              // the requested tile cannot run this problem: let the heuristic choose
-        return plan_igemm(p, batch, ws_bytes, -1, mode, false);
-    if (p.sa) best.cfg = kTiles[best.cfg].f8;         // fp8 operands (fill_gemm sets the scales): the tile that launches
-    return best;
-}
-
-extern int g_pbe_pingpong;      // pbe_tune(4, 0/1): ping-pong main loop of the halo-resident conv tiles
-extern int g_pbe_mfast;         // pbe_tune(5, 0/1): let a launch walk its tiles m fastest per XCD when that fetches fewer bytes
-
-// What a launch of tile bm x bn knows before any workgroup starts (p.splits set by the dispatch): the tile order, the halo tile's rows and
-// every launch-invariant value of the kernel's prologue (IGemmP head), so that no workgroup divides before its first fetch.
-// mode: 0 dense, 1 conv gather, 2 halo-resident conv.
-static void igemm_prologue(IGemmP& p, int batch, int bm, int bn, int mode) {
-    const int tiles_m = cdiv(p.M, bm), tiles_n = cdiv(p.N, bn);
-    {   // bytes the 8 L2s fetch under either tile order (an XCD owns a contiguous run of tiles_m * tiles_n / 8 tiles)
-        const double a_bytes = mode != 0 ? 2.0 * (double)(p.M / (p.Ho * p.Wo)) * p.H * p.Wd * (p.C1 + p.C2) : 2.0 * p.M * (double)p.K;
-        const double w_bytes = 2.0 * p.N * (double)p.K;
-        const double run = tiles_m * (double)tiles_n / 8.0;
-        auto frac = [](double blocks_touched, int blocks) { const double f = blocks_touched / blocks; return f < 1.0 ? f : 1.0; };
-        const double n_fast = a_bytes * frac(run / tiles_n + 1.0, tiles_m) + w_bytes * frac(run, tiles_n);
-        const double m_fast = w_bytes * frac(run / tiles_m + 1.0, tiles_n) + a_bytes * frac(run, tiles_m);
-        p.m_fast = (g_pbe_mfast && batch == 1 && m_fast < 0.9 * n_fast) ? 1 : 0;
-    }
-    p.tdiv = p.m_fast ? tiles_m : tiles_n; p.mg_tdiv = mg_of((unsigned)p.tdiv);
-    const int units = mode == 2 ? (p.C1 + p.C2) >> 6 : (p.K + 63) >> 6;            // what split-K slices: channel blocks of a halo tile, else k-tiles
-    p.split_per = p.splits > 1 ? (units + p.splits - 1) / p.splits : units;
-    p.sv_ns = (p.rowvec && p.group_rows < bm) ? bm / p.group_rows : 1;
-    p.sv_gdiv = p.group_rows > bm ? p.group_rows / bm : 1; p.mg_sv_gdiv = mg_of((unsigned)p.sv_gdiv);
-    if (mode != 0) {
-        const int kb = p.cb >> 6;
-        p.hw = p.Ho * p.Wo; p.mg_hw = mg_of((unsigned)p.hw); p.mg_wo = mg_of((unsigned)p.Wo);
-        p.per_blk = (p.phase ? 4 : 9) * kb; p.mg_per_blk = mg_of((unsigned)p.per_blk); p.mg_kb = mg_of((unsigned)kb);
-    }
-    if (mode == 2) {                                                             // halo geometry (igemm_kernel MODE 2; halo_rows admitted the map)
-        const int W = p.Wd, th = bm / W < p.H ? bm / W : p.H, img_px = th * W;
-        p.th = th;
-        p.h_hw2 = W + 1; p.h_hps = (th + 2) * (W + 1) + 1;
-        p.h_nsub = bm / img_px; p.h_rows = p.h_nsub * p.h_hps;
-        p.h_tpi = p.H / th; p.mg_h_tpi = mg_of((unsigned)p.h_tpi);
-        p.mh_hps = mh_of((unsigned)p.h_hps); p.mh_hw2 = mh_of((unsigned)p.h_hw2);
-        p.h_lgw = __builtin_ctz((unsigned)W); p.h_lgimg = __builtin_ctz((unsigned)img_px);
-    }
-}
-
-template <int BM, int BN, int NWM, int NWN, int S, int MODE, int HPA = 0, bool PP = false, bool F8 = false, int EX = 0>
-static void launch_cfg(IGemmP p, int batch, hipStream_t s) {
-    // (ping-pong only where a wave's MFMA phase - (BM/NWM/16) x (BN/NWN/16) x 2 MFMAs - is as long as its read phase: measured
-    //  25 % SLOWER on the 128x160 halo tile, whose 20 MFMAs cannot cover 14 fragment reads + 3 DMA issues)
-    if constexpr (MODE == 2 && !PP && S == 3 && (BM / NWM / 16) * (BN / NWN / 16) >= 16) {
-        if (g_pbe_pingpong) { launch_cfg<BM, BN, NWM, NWN, S, MODE, HPA, true>(p, batch, s); return; }
-    }
-    constexpr size_t ring = MODE == 2 ? (size_t)2 * HPA * 128 + (size_t)S * BN * 128 : (size_t)S * (BM + BN) * 128;
-    constexpr size_t c_bytes = (size_t)(BM / NWM) * (BN + 8) * 2;
-    constexpr int SVR = (ring > c_bytes ? ring : c_bytes) + 4 * BN * sizeof(float) <= 160 * 1024 ? 4 : 3;                              // svec rows (samples per tile)
-    constexpr size_t lds = (ring > c_bytes ? ring : c_bytes) + (MODE == 1 ? 9 * BM * sizeof(int) : 0) + ((EX & 7) != 0 ? 4 : SVR) * BN * sizeof(float) +     // + svec[SVR][BN]
-                           (F8 ? (BM + BN) * sizeof(float) : 0) + ((EX & 7) != 0 ? (2 * BM + BN) * sizeof(float) : 0);                            // + operand scales / LayerNorm rows + colsum
-    p.sv_ok = !p.rowvec || p.group_rows % BM == 0 || (BM % p.group_rows == 0 && BM / p.group_rows <= SVR);
-    static_assert(lds <= 160 * 1024, "tile does not fit the 160 KiB LDS");
-    static std::atomic<uint64_t> attr_done{0};
-    pbe_raise_dynamic_lds(attr_done, reinterpret_cast<const void*>(&igemm_kernel<BM, BN, NWM, NWN, MODE, S, HPA, PP, F8, EX>), (int)lds);
-    const int tiles_m = cdiv(p.M, BM), tiles_n = cdiv(p.N, BN);
-    dim3 grid((unsigned)(tiles_m * tiles_n), batch, p.splits > 1 ? p.splits : 1);
-    igemm_prologue(p, batch, BM, BN, MODE);
-    {   // GroupNorm statistics from the copy-out: only where the kernel's GS_OK holds and a tile is a whole number of groups inside one sample
-        constexpr int NTH = NWM * NWN * 64;
-        constexpr bool one_pass = (size_t)BM * (BN + 8) * 2 <= (size_t)S * (BM + BN) * 128;
-        constexpr size_t gs_off = ((size_t)BM * (BN + 8) * 2 + 15) & ~(size_t)15;
-        constexpr bool gs_ok = MODE != 0 && one_pass && !F8 && gs_off + ((size_t)(NTH / (BN / 8)) * BN + BN) * 8 <= ring;
-        if (p.gstat && !(gs_ok && p.splits <= 1 && batch == 1 && p.gs_cg > 0 && p.gs_hw % BM == 0 && BN % p.gs_cg == 0 && !p.phase && p.vec && p.act != PBE_ACT_GEGLU))
-            p.gstat = nullptr;
-        if (p.gs_report) *p.gs_report = p.gstat ? p.gs_hw / BM : 0;
-    }
-    // profiling brackets exactly ONE kernel each, so the event averages agree with rocprofv3's per-kernel averages
-    pbe_prof_begin(MODE != 0 ? PBE_K_CONV3 : PBE_K_GEMM, s);
-    hipLaunchKernelGGL((igemm_kernel<BM, BN, NWM, NWN, MODE, S, HPA, PP, F8, EX>), grid, dim3(NWM * NWN * 64), lds, s, p);
-    {   // algorithmic bytes: every operand once (fp16): activations, weights, output, fused residual
-        const double nout = p.act == PBE_ACT_GEGLU ? p.N * 0.5 : (double)p.N;
-        const double a_el = MODE != 0 ? (double)(p.M / (p.Ho * p.Wo)) * p.H * p.Wd * (p.C1 + p.C2) : (double)p.M * p.K * batch;
-        const double w_el = (double)p.N * p.K * ((MODE == 0 && p.sW) ? batch : 1);
-        const double c_el = (double)p.M * nout * batch * (p.resid ? 2.0 : 1.0);
-        pbe_prof_end(MODE != 0 ? PBE_K_CONV3 : PBE_K_GEMM, s, 2.0 * p.M * (double)p.N * p.K * batch * (F8 ? 2.0 : 1.0), 2.0 * (a_el + w_el + c_el));
-    }
-    if (p.splits > 1) {
-        const long work = (long)p.M * (p.N >> 2);
-        pbe_prof_begin(PBE_K_SPLITK, s);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, p);
-        pbe_prof_end(PBE_K_SPLITK, s, (double)p.M * p.N * (4.0 * p.splits + 2.0));       // bytes: fp32 slabs in, fp16 out
-    }
-}
-
-
-// ---- dispatch: launch tile `cfg` of kTiles in one form.  The rows are walked at compile time and launch_cfg is instantiated for the
-// rows that carry the form bit only; a tile without it is an error (the planner never picks one) ----
-template <unsigned FORM, int MODE, bool F8, int EX, size_t I>
-static bool launch_row(IGemmP p, int batch, hipStream_t s) {
-    constexpr TileCfg t = kTiles[I];
-    if constexpr ((t.forms & FORM) != 0) {
-        launch_cfg<t.bm, t.bn, t.nwm, t.nwn, t.s, MODE, t.hpa, false, F8, EX>(p, batch, s);
-        return true;
-    }
-    return false;
-}
-
-template <unsigned FORM, int MODE, bool F8, int EX, size_t... I>
-static bool launch_rows(int cfg, IGemmP p, int batch, hipStream_t s, std::index_sequence<I...>) {
-    return ((cfg == (int)I && launch_row<FORM, MODE, F8, EX, I>(p, batch, s)) || ...);
-}
-
-template <unsigned FORM, int MODE, bool F8 = false, int EX = 0>
-static int launch_tile(int cfg, IGemmP p, int batch, hipStream_t s) {
-    if (launch_rows<FORM, MODE, F8, EX>(cfg, p, batch, s, std::make_index_sequence<kNCfg>{})) return PBE_OK;
-    return pbe_set_error(PBE_ENOTSUP, "igemm: tile config %d is not instantiated in form 0x%x", cfg, FORM);
-}
-
-// ---- the instantiations live in five translation units (igemm_dense / _conv / _halo / _f8 / _ex .hip), compiled in parallel ----
-int pbe_dispatch_dense(IGemmP p, int batch, hipStream_t s, size_t ws_bytes, int want_cfg);      // MODE 0
-int pbe_dispatch_conv(IGemmP p, int batch, hipStream_t s, size_t ws_bytes, int want_cfg);       // MODE 1 gather tiles; forwards F_HALO tiles to
-int pbe_launch_halo(int cfg, IGemmP p, int batch, hipStream_t s);                               // MODE 2 halo-resident tiles
-int pbe_dispatch_f8(IGemmP p, int batch, hipStream_t s, int want_cfg);
-int pbe_dispatch_ex(IGemmP p, int batch, hipStream_t s, int want_cfg);           // picks the feature combination: igemm_ex_{ln,st,qkv,all}.hip
-int pbe_launch_ex_ln(int cfg, IGemmP p, int batch, hipStream_t s);
-int pbe_launch_ex_st(int cfg, IGemmP p, int batch, hipStream_t s);
-int pbe_launch_ex_qkv(int cfg, IGemmP p, int batch, hipStream_t s);
-int pbe_launch_ex_all(int cfg, IGemmP p, int batch, hipStream_t s);
-void pbe_launch_astat(int cfg, IGemmP p, hipStream_t s);                                                  // tiles 19 / 20 (igemm_astat.hip)
-// MX-fp8 copy-out forms (pbe_gemm_mx8out_f16): the q|k|v^T tiles (igemm_ex_qkv.hip, A-stationary tile 20 in igemm_astat.hip) and the fp8 tiles
-int pbe_launch_ex_qkv_mx8(int cfg, IGemmP p, int batch, hipStream_t s);
-int pbe_launch_f8_mx8(int cfg, IGemmP p, int batch, hipStream_t s);

@@ -157,8 +157,10 @@ _lock = threading.Lock()
 
 SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_astat.hip", "attention.hip", "attention_mx8.hip", "ctx_attention.hip", "norm.hip",
            "elementwise.hip", "window.hip", "holes.hip", "maskshape.hip", "tone.hip", "tone_field.hip", "exemplar.hip", "noise.hip"]
-HASHED = [os.path.join("csrc", f) for f in SOURCES] + [os.path.join("csrc", "common.h"), os.path.join("csrc", "igemm_kernel.h"), os.path.join("csrc", "tone_bytes.h"), os.path.join("csrc", "u8_norm.h"),
-                                                         os.path.join("..", "include", "pbe_hip.h"), "build.py"]
+# the shared headers, relative to this directory: every object file depends on them (build.py) and the source hash covers them
+HEADERS = [os.path.join("csrc", f) for f in ("common.h", "igemm_params.h", "igemm_mx8_out.h", "igemm_kernel.h", "igemm_plan.h", "tone_bytes.h", "u8_norm.h")] + [
+    os.path.join("..", "include", "pbe_hip.h")]
+HASHED = [os.path.join("csrc", f) for f in SOURCES] + HEADERS + ["build.py"]
 
 
 def source_hash() -> str:

@@ -29,7 +29,7 @@ GK1 = 96                        # second source from k = 96: inside k-tile 1 (a 
 
 
 def halo_fits(tile, B, H, W):
-    """The halo rule of the planner (igemm_kernel.h, halo_rows) for tile on a [B, H, W] map."""
+    """The halo rule of the planner (igemm_plan.h, halo_rows) for tile on a [B, H, W] map."""
     bm, hpa = HALO_TILES[tile]
     if W < 8 or W > 128 or W & (W - 1) or bm % W or (B * H * W) % bm:
         return False

@@ -1,4 +1,4 @@
-"""The contract between the conv planner (halo_rows / plan_igemm, igemm_kernel.h) and the halo-resident conv tiles 10 .. 14 (the MODE 2
+"""The contract between the conv planner (halo_rows / plan_igemm, igemm_plan.h) and the halo-resident conv tiles 10 .. 14 (the MODE 2
 prologue of igemm_kernel): whenever a plan names a halo tile, the tile's BM output rows are exactly the pixels of the image rows the
 kernel stages for it.  Host-only plan queries with stand-in pointers (as tests/test_launch_cpu.py); nothing is launched.
 
