@@ -62,6 +62,7 @@ size_t pbe_sizeof_attn_desc(void);
 size_t pbe_sizeof_attn_mx8_desc(void);
 size_t pbe_sizeof_mx8_out_desc(void);
 size_t pbe_sizeof_ctx_attn_desc(void);
+size_t pbe_sizeof_gnfold_desc(void);
 /* The implicit-GEMM kernels' parameter block (internal to the library; for layout tests): its size, and the size of its HEAD - the leading
  * bytes that hold everything a workgroup reads before its first fetch; epilogue, statistics and diagnostic fields lie behind it. */
 size_t pbe_sizeof_igemm_params(void);
@@ -332,6 +333,27 @@ typedef struct pbe_mx8_out_desc {
 } pbe_mx8_out_desc;
 int pbe_gemm_mx8out_f16(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, pbe_stream_t stream);
 int pbe_gemm_mx8out_plan(const pbe_gemm_desc* d, const pbe_mx8_out_desc* mx, int32_t* out6);
+
+/* pbe_gemm_gnfold_f16 - pbe_gemm_f16 on GroupNorm(A) without the normalised tensor: A holds the RAW rows x [M, K] of `tokens` rows per
+ * sample, and the kernel replaces every A element by fp16(x * sc[b, k] + sh[b, k]) (one fp32 multiply-add, one rounding) behind its LDS
+ * read - the value and the bits pbe_groupnorm_apply_f16(silu = 0) would have stored, so C and row_stats_out equal those of the two
+ * launches.  table: fp32 [samples][K / 8][16] from pbe_groupnorm_table_f32 (sc | sh of 8 consecutive channels), ld = 2 K floats per
+ * sample, ceil(M / tokens) samples.  Accepted: a 2-D fp16 problem (batch 1, no A2, ln_stats, VT, alpha_cols, GEGLU; bias, rowvec, resid,
+ * act and row_stats_out as in pbe_gemm_f16), K % 64 == 0, K <= 1280, and a tile whose row count divides `tokens` (a tile's rows then
+ * belong to one sample; a requested tile that does not is replaced by the heuristic's pick among those that do).  PBE_EINVAL
+ * otherwise: the caller then runs pbe_groupnorm_apply_f16 and pbe_gemm_f16.  Never split-K.
+ * pbe_gemm_gnfold_plan: the tile that launches (out6 as pbe_gemm_plan), host only; PBE_EINVAL where pbe_gemm_gnfold_f16 refuses.
+ * pbe_groupnorm_table_f32: sc[b, c] = rstd[b, g] gamma[c], sh[b, c] = beta[c] - mean[b, g] sc[b, c] from the partial statistics
+ * [B][blocks][groups][2] (group_stats_out of pbe_conv3x3_f16), with the finalise and the fp32 expressions of pbe_groupnorm_apply_f16. */
+typedef struct pbe_gnfold_desc {
+    const float* table; /* fp32 [samples][K / 8][16], 16-byte aligned */
+    int64_t ld;         /* floats per sample: 2 K */
+    int32_t tokens;     /* rows of A per sample */
+} pbe_gnfold_desc;
+int pbe_groupnorm_table_f32(const float* partials, int32_t blocks, const float* gamma, const float* beta, float* table, int32_t B, int32_t HW,
+                            int32_t C, int32_t groups, float eps, pbe_stream_t stream);
+int pbe_gemm_gnfold_f16(const pbe_gemm_desc* d, const pbe_gnfold_desc* g, pbe_stream_t stream);
+int pbe_gemm_gnfold_plan(const pbe_gemm_desc* d, const pbe_gnfold_desc* g, int32_t* out6);
 
 /* ---------------------------------------------------------------------------------------------
  * pbe_ctx_attention_f16 — x + attn2(LayerNorm(x), context) of a transformer block (attention.py:207-230, 268-272) for a SHORT context

@@ -654,18 +654,29 @@ class BasicTransformerBlock(HipModule):
         r = ops.gemm(a, a1.wo, a1.bo, rowvec=rowvec, group_rows=0 if rowvec is None else N, resid=x2d, out=out, row_stats=want)
         return r if mode == "folded" else (r, None)
 
-    def _ff(self, x, st, mode):
-        """x + ff(norm3(x)); st: RowStats of x (folded)."""
+    def _ff(self, x, st, mode, tail=None, paired=False):
+        """x + ff(norm3(x)); st: RowStats of x (folded).  tail (folded only; SpatialTransformer._tail): the transformer's proj_out composed
+        into this projection - resid + [h | x] w^T + b in ONE launch over the two-source K loop; a guidance pair (x holds both halves, the
+        residual serves both) launches once per half under the pair's pinned plan, as the separate proj_out does."""
         p = self.pk()
         if mode == "folded":
             h = ops.gemm(x, p.wg, p.c2g, act=ops.ACT_GEGLU, ln=(st, p.c1g, p.eps3))
+            if tail is not None:
+                if not paired:
+                    return ops.gemm(h, tail.w, tail.b, a2=x, resid=tail.resid)
+                M = x.shape[0] // 2
+                y = torch.empty((2 * M, tail.w.shape[0]), dtype=torch.float16, device=x.device)
+                with ops.pinned_batch_scale(2):
+                    for half in (0, 1):
+                        ops.gemm(h[half * M:(half + 1) * M], tail.w, tail.b, a2=x[half * M:(half + 1) * M], resid=tail.resid, out=y[half * M:(half + 1) * M])
+                return y
             fp = self.ff.pk()
             return ops.gemm(h, fp.w2, fp.b2, resid=x)
         if mode == "f8":
             return self.ff.run_f8(*ops.layernorm_f8(x, p.g3, p.b3, p.eps3), resid=x)
         return self.ff.run(ops.layernorm(x, p.g3, p.b3, p.eps3), resid=x)
 
-    def _block(self, x2d, B, N, ctx, stats, paired):
+    def _block(self, x2d, B, N, ctx, stats, paired, tail=None):
         """The stage chain of run (ctx for B samples) and run_paired (x2d serves both halves, ctx holds 2B samples).  What does not depend
         on the context runs once; the halves of a pair part at the first launch that does - attn1's out-projection for a one-token
         constant, attn2 for multi-token operands - each writing its half of one 2B buffer and of its row statistics."""
@@ -696,19 +707,19 @@ class BasicTransformerBlock(HipModule):
                     y, st = self._attn2(x1, st1, c, B, N, folded, out, tgt)
         if paired:                                               # the joined buffer, with the partial count the last launch reported
             y, st = x, ops.RowStats(buf, st.parts, 2 * M) if folded else None
-        return self._ff(y, st, mode)
+        return self._ff(y, st, mode, tail, paired)
 
-    def run(self, x2d, B, N, ctx_vec, stats=None):
+    def run(self, x2d, B, N, ctx_vec, stats=None, tail=None):
         """x2d [B*N, C] fp16 residual stream -> the block's output, same shape.  ctx_vec = context_operands(context) for the B samples:
         [B, C] = attn2's constant for a one-token context, or the multi-token operands (ops.CtxOperands / ContextKV); stats =
         ops.RowStats of x2d's rows when its producer emitted them (SpatialTransformer's proj_in does), else the folded chain computes
-        them.  Stages and modes: _block."""
-        return self._block(x2d, B, N, ctx_vec, stats, False)
+        them.  tail: _ff.  Stages and modes: _block."""
+        return self._block(x2d, B, N, ctx_vec, stats, False, tail)
 
-    def run_paired(self, x2d, B, N, ctx_vec, stats=None):
+    def run_paired(self, x2d, B, N, ctx_vec, stats=None, tail=None):
         """Guidance pair with a SHARED input: x2d [B*N, C] serves both halves, ctx_vec holds the 2B contexts -> [2B*N, C], the bits of
         run on the duplicated input.  Everything upstream of the first launch that depends on the context runs once at batch B (_block)."""
-        return self._block(x2d, B, N, ctx_vec, stats, True)
+        return self._block(x2d, B, N, ctx_vec, stats, True, tail)
 
     def forward(self, x, context=None, context_weights=None, context_row_weights=None, attn_map=None):
         """x [B, N, C], context [B, K, Dc] with K >= 1 tokens per sample (context_weights [B, K] or None) -> [B, N, C].
@@ -733,6 +744,16 @@ class BasicTransformerBlock(HipModule):
         return self.run(x.view(B * N, Cc), B, N, o).view(B, N, Cc)
 
 
+def compose_tail(wpo, bpo, wff, bff):
+    """proj_out after ff-out as ONE linear map of [h | x2]: ([Wpo Wff | Wpo] fp16 [Cin, Kff + inner], Wpo bff + bpo fp32 [Cin]); the products in
+    fp64 from the masters, rounded once."""
+    with torch.no_grad():
+        po = wpo.detach().double().reshape(wpo.shape[0], -1)
+        w = torch.cat([po @ wff.detach().double(), po], 1)
+        b = po @ bff.detach().double() + bpo.detach().double()
+        return w.to(torch.float16).contiguous(), b.to(torch.float32).contiguous()
+
+
 class SpatialTransformer(HipModule):
     """GroupNorm(eps 1e-6) -> 1x1 proj_in -> transformer block(s) -> 1x1 proj_out -> + input."""
 
@@ -746,10 +767,33 @@ class SpatialTransformer(HipModule):
             [BasicTransformerBlock(inner, n_heads, d_head, dropout=dropout, context_dim=context_dim) for _ in range(depth)])
         self.proj_out = zero_module(nn.Conv2d(inner, in_channels, kernel_size=1, stride=1, padding=0))
 
+    fold_groupnorm = True       # the GroupNorm rides on proj_in's A operand where x carries its producer's statistics (ops.gemm gn=); False: the separate pass (A/B runs)
+    # The fold's dispatch bound, from profiles/stfold_shape_profile.txt: at C = 320 norm + proj_in take 15.7 + 22.4 us against 6.5 + 22.2 folded;
+    # at C = 640 the table's 5 KB of LDS cost the tuned 64x128 tile its third workgroup per CU, 640 workgroups then run in two rounds and
+    # the pair takes 7.3 + 30.4 us against 14.1 + 19.3: wider levels keep the separate pass (the kernel itself takes K <= 1280)
+    fold_groupnorm_max_width = 320
+    # proj_out composed into the last block's ff-out projection (_tail).  It changes low-order bits, so a stand-alone module keeps the two
+    # launches and their bits (tests/golden/block_parent.npz pins them launch for launch); the U-Net switches it on for its transformers
+    fold_tail = False
+
     def _pack(self):
-        return SimpleNamespace(g=f32(self.norm.weight), b=f32(self.norm.bias), eps=self.norm.eps,
-                               wi=ops.pack_linear(self.proj_in.weight), bi=f32(self.proj_in.bias),
-                               wo=ops.pack_linear(self.proj_out.weight), bo=f32(self.proj_out.bias))
+        """proj_out composed into the last block's ff-out (both linear, both constant): with x3 = x2 + h Wff^T + bff,
+        x + x3 Wpo^T + bpo = x + [h | x2] [Wpo Wff | Wpo]^T + (Wpo bff + bpo).  The products are formed in fp64 from the fp32 masters and
+        rounded to fp16 once."""
+        ns = SimpleNamespace(g=f32(self.norm.weight), b=f32(self.norm.bias), eps=self.norm.eps,
+                             wi=ops.pack_linear(self.proj_in.weight), bi=f32(self.proj_in.bias),
+                             wo=ops.pack_linear(self.proj_out.weight), bo=f32(self.proj_out.bias))
+        ns.wt, ns.bt = compose_tail(self.proj_out.weight, self.proj_out.bias, self.transformer_blocks[-1].ff.net[2].weight,
+                                    self.transformer_blocks[-1].ff.net[2].bias)
+        return ns
+
+    def _tail(self, p, x2d, N, cv):
+        """The composed ff-out + proj_out operands for the LAST block, where it runs the LayerNorm-folded chain on a one-token constant
+        (the fp8 and plain modes and the multi-token attn2 routes keep the two launches), else None."""
+        blk = self.transformer_blocks[-1]
+        if not (self.fold_tail and isinstance(cv, torch.Tensor) and blk._mode(N) == "folded"):
+            return None
+        return SimpleNamespace(w=p.wt, b=p.bt, resid=x2d)
 
     def context_vectors(self, context, context_weights=None, context_regions=None, maps=False):
         """Per block, what its run() needs of context [B, K, Dc]: the [B, C] constant for K = 1, the multi-token operands for K > 1
@@ -793,10 +837,23 @@ class SpatialTransformer(HipModule):
         B, H, W, Cc = x.shape
         N = H * W
         ctx_vecs = self._levelled(ctx_vecs, H, W, maps)
-        h, st = ops.gemm(ops.groupnorm(x, p.g, p.b, p.eps, False).view(B * N, Cc), p.wi, p.bi, row_stats=True)   # statistics for the first block's norm1
-        for blk, cv in zip(self.transformer_blocks, ctx_vecs):
-            h, st = blk.run(h, B, N, cv, stats=st), None
-        return ops.gemm(h, p.wo, p.bo, resid=x.view(B * N, Cc)).view(B, H, W, Cc)
+        x2d = x.view(B * N, Cc)
+        h, st = self._proj_in(p, x, B, N)                                    # statistics for the first block's norm1
+        tail = self._tail(p, x2d, N, ctx_vecs[-1])
+        last = len(self.transformer_blocks) - 1
+        for i, (blk, cv) in enumerate(zip(self.transformer_blocks, ctx_vecs)):
+            h, st = blk.run(h, B, N, cv, stats=st, tail=tail if i == last else None), None
+        if tail is not None:
+            return h.view(B, H, W, Cc)
+        return ops.gemm(h, p.wo, p.bo, resid=x2d).view(B, H, W, Cc)
+
+    def _proj_in(self, p, x, B, N):
+        """proj_in(GroupNorm(x)) -> (h, RowStats of h): the norm folded into the GEMM's A operand where x carries its producing conv's
+        statistics (the launch falls back to the separate pass where no tile's rows divide N), else the norm's own launch(es)."""
+        st = ops.group_stats_of(x, self.norm.num_groups) if self.fold_groupnorm and x.shape[-1] <= self.fold_groupnorm_max_width else None
+        if st is not None:
+            return ops.gemm(x.view(B * N, -1), p.wi, p.bi, row_stats=True, gn=(st, p.g, p.b, p.eps))
+        return ops.gemm(ops.groupnorm(x, p.g, p.b, p.eps, False, groups=self.norm.num_groups).view(B * N, -1), p.wi, p.bi, row_stats=True)
 
     def run_paired(self, x, ctx_vecs, maps=None):
         """x [B, H, W, C] shared by the two halves of a guidance pair, ctx_vecs = context_vectors of the 2B contexts (one- or multi-token)
@@ -807,8 +864,13 @@ class SpatialTransformer(HipModule):
         ctx_vecs = self._levelled(ctx_vecs, H, W, maps)
         x2d = x.view(B * N, Cc)
         with ops.pinned_batch_scale(2):
-            h, st = ops.gemm(ops.groupnorm(x, p.g, p.b, p.eps, False).view(B * N, Cc), p.wi, p.bi, row_stats=True)
-        h = self.transformer_blocks[0].run_paired(h, B, N, ctx_vecs[0], stats=st)
+            h, st = self._proj_in(p, x, B, N)
+        last = len(self.transformer_blocks) - 1
+        # (depth > 1: the last block runs at batch 2B, where the shared residual has no row per sample of the second half: two launches)
+        tail = self._tail(p, x2d, N, ctx_vecs[0]) if last == 0 else None
+        h = self.transformer_blocks[0].run_paired(h, B, N, ctx_vecs[0], stats=st, tail=tail)
+        if tail is not None:
+            return h.view(2 * B, H, W, Cc)
         for blk, cv in zip(list(self.transformer_blocks)[1:], ctx_vecs[1:]):
             h = blk.run(h, 2 * B, N, cv)
         y = torch.empty((2 * B * N, Cc), dtype=torch.float16, device=x.device)

@@ -173,7 +173,9 @@ class UNetModel(HipModule):
             heads, dh = (num_heads, ch // num_heads) if num_head_channels == -1 else (ch // num_head_channels, num_head_channels)
             if legacy:
                 dh = ch // heads
-            return SpatialTransformer(ch, heads, dh, depth=transformer_depth, context_dim=context_dim)
+            st = SpatialTransformer(ch, heads, dh, depth=transformer_depth, context_dim=context_dim)
+            st.fold_tail = True                 # proj_out rides in the last block's ff-out (attention.py, SpatialTransformer.fold_tail)
+            return st
 
         self.input_blocks = nn.ModuleList([TimestepEmbedSequential(conv_nd(dims, in_channels, model_channels, 3, padding=1))])
         skip_chans, ch, ds = [model_channels], model_channels, 1

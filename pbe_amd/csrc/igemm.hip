@@ -325,3 +325,57 @@ extern "C" int pbe_gemm_mx8out_plan(const pbe_gemm_desc* d, const pbe_mx8_out_de
     out6[5] = cdiv(p.N, t.bn);
     return PBE_OK;
 }
+
+// ---- GroupNorm fold (pbe_gemm_gnfold_f16): the GEMM reads the RAW rows; every A fragment is normalised behind its LDS read (igemm_kernel.h, EX_GN) ----
+static int fill_gnfold(const pbe_gemm_desc* d, const pbe_gnfold_desc* g, IGemmP& p, const char* who) {
+    PBE_REQUIRE(d && g, "%s: null descriptor", who);
+    const int rc = fill_gemm(d, p, who);
+    if (rc != PBE_OK) return rc;
+    PBE_REQUIRE(d->operand_dtype == PBE_DTYPE_F16 && d->batch == 1 && !d->A2 && !d->ln_stats && !d->VT && !d->alpha_cols && d->act != PBE_ACT_GEGLU,
+                "%s: a 2-D fp16 problem with one A source and no LayerNorm fold, V^T, column alpha or GEGLU", who);
+    PBE_REQUIRE(d->K % 64 == 0 && d->K <= PBE_GN_MAX_K, "%s: K=%d must be a multiple of 64, at most %d", who, d->K, PBE_GN_MAX_K);
+    PBE_REQUIRE(g->table && al16(g->table) && g->tokens > 0 && g->ld == 2L * d->K, "%s: table [samples][K / 8][16] fp32, 16-byte aligned, ld = 2 K; tokens > 0", who);
+    p.gn_tab = g->table; p.gn_tdiv = g->tokens;       // (tokens per sample: launch_cfg turns it into row tiles per sample)
+    p.ws = nullptr;
+    return PBE_OK;
+}
+
+// the tile that launches: PBE_EINVAL when no streaming extended-epilogue tile divides the tokens of a sample (the caller then normalises in a pass of its own)
+static int plan_gnfold(const IGemmP& p, int want_cfg, Plan& pl, const char* who) {
+    pl = plan_igemm(p, 1, 0, want_cfg, 0);
+    PBE_REQUIRE(gn_tile_ok(p, kTiles[pl.cfg]) && pl.splits == 1, "%s: no tile's rows divide the %d tokens of a sample", who, p.gn_tdiv);
+    return PBE_OK;
+}
+
+extern "C" int pbe_gemm_gnfold_f16(const pbe_gemm_desc* d, const pbe_gnfold_desc* g, pbe_stream_t stream) {
+    IGemmP p;
+    int rc = fill_gnfold(d, g, p, "pbe_gemm_gnfold_f16");
+    if (rc != PBE_OK) return rc;
+    Plan pl;
+    rc = plan_gnfold(p, d->tile_cfg, pl, "pbe_gemm_gnfold_f16");
+    if (rc != PBE_OK) return rc;
+    p.splits = 1;
+#ifdef PBE_STAMPS
+    p.stamps = g_pbe_stamps;
+#endif
+    rc = pbe_launch_ex_gn(pl.cfg, p, 1, (hipStream_t)stream);
+    if (rc != PBE_OK) return rc;
+    PBE_LAUNCH_CHECK("pbe_gemm_gnfold_f16");
+    return PBE_OK;
+}
+
+extern "C" int pbe_gemm_gnfold_plan(const pbe_gemm_desc* d, const pbe_gnfold_desc* g, int32_t* out6) {
+    PBE_REQUIRE(out6, "pbe_gemm_gnfold_plan: null output");
+    IGemmP p;
+    int rc = fill_gnfold(d, g, p, "pbe_gemm_gnfold_plan");
+    if (rc != PBE_OK) return rc;
+    Plan pl;
+    rc = plan_gnfold(p, d->tile_cfg, pl, "pbe_gemm_gnfold_plan");
+    if (rc != PBE_OK) return rc;
+    const TileCfg& t = kTiles[pl.cfg];
+    out6[0] = pl.cfg; out6[1] = 1; out6[2] = t.bm; out6[3] = t.bn;
+    out6[4] = cdiv(p.M, t.bm) * cdiv(p.N, t.bn);
+    out6[5] = cdiv(p.N, t.bn);
+    return PBE_OK;
+}
+extern "C" size_t pbe_sizeof_gnfold_desc(void) { return sizeof(pbe_gnfold_desc); }

@@ -66,7 +66,9 @@ template <int BM, int BN, int NWM, int NWN, int MODE, int S, int HPA, bool F8, i
     static constexpr bool GS_OK = MODE != 0 && ONE_PASS && !F8 && (NT / (BN / 8)) >= 1 && (size_t)GS_OFF + ((size_t)(NT / (BN / 8)) * BN + BN) * 8 <= (size_t)RING;
     static_assert((!SCALES || SVEC_ROWS == 4) && (ONE_PASS ? BM * CLD * 2 : C_PASS) <= MAIN, "sca sits four svec rows behind svec; the C tile of a pass ends before svec");
     static_assert((F8 ? SCW_OFF + BN * 4 : (EX & 7) != 0 ? LNC_OFF + BN * 4 : SVEC_OFF + SVEC_ROWS * BN * 4) == LDS_BYTES, "the last region ends at LDS_BYTES");
-    static_assert(LDS_BYTES <= KIB160, "tile does not fit the 160 KiB LDS");
+    // EX_GN: the sample's sc | sh table, 8 K bytes for THIS launch's K, lies behind everything else (launch_cfg adds it to the dynamic LDS)
+    static constexpr int GN_OFF = LDS_BYTES, GN_MAX_BYTES = (EX & EX_GN) ? 8 * PBE_GN_MAX_K : 0;
+    static_assert(LDS_BYTES + GN_MAX_BYTES <= KIB160, "tile does not fit the 160 KiB LDS");
 };
 
 // ---- the tile table: every (BM, BN, NWM, NWN, S, HPA) the kernel is instantiated for; the planner and the dispatch (igemm_plan.h) walk it ----
@@ -139,6 +141,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     // the maximum over its paths, and the all-in-one form ran the GEGLU projection 11 % slower than the plain tile (tools/gemm_ex_ab.py).
     constexpr bool EXL = (EX & 1) != 0, EXS = (EX & 2) != 0, EXV = (EX & 4) != 0, EXM = (EX & EX_MX) != 0;
     constexpr int EXF = EX & 7;                       // the fp16 extended-epilogue features (EX_MX only changes the copy-out)
+    constexpr bool EXG = (EX & EX_GN) != 0;           // GroupNorm folded into the A fragments (MODE 0, K % 64 == 0, one sample per tile: the host checks)
     // F8 (MODE 0 only): A and W hold OCP e4m3 bytes, a k-tile row of 128 B is 128 k-values; v_mfma_f32_16x16x32_fp8_fp8 runs at
     // the fp16 MFMA's rate, the gain is half the bytes through the fill path that bounds these GEMMs.  The epilogue multiplies
     // by the per-row scale of A and the per-row scale of W (per output column) before bias / activation / residual.
@@ -164,6 +167,7 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
     static_assert(MODE != 2 || (HPA % 8 == 0 && HPA >= BM), "halo image must hold the tile");
     static_assert(EXF == 0 || (MODE == 0 && !F8), "extended epilogue: dense fp16 tiles only");
     static_assert(!EXM || (MODE == 0 && !EXS && (F8 || EXF == (EX_LN | EX_VT))), "MX-fp8 copy-out: the fp8 tiles and the q|k|v^T form");
+    static_assert(!EXG || (MODE == 0 && !F8 && !EXL), "GroupNorm fold: dense fp16 tiles whose A is not LayerNorm-folded too");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -735,6 +739,32 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
         if (kt0 + t < nk) issue(kt0 + t, t);
     PBE_STAMP(2);                                    // ring primed (issue only)
     stage_svec();
+    // EX_GN: this tile's sample's table -> LDS, a straight 16-byte copy behind the first DMAs; the first k-tile's barrier publishes it
+    const float* gnt = reinterpret_cast<const float*>(smem + G::GN_OFF);
+    if constexpr (EXG) {
+        const int smp = (int)udiv_mg((unsigned)tm_i, (unsigned)p.gn_tdiv, p.mg_gn_tdiv);
+        const f32x4* src = reinterpret_cast<const f32x4*>(p.gn_tab + (long)smp * 2 * p.K);
+        f32x4* dst = reinterpret_cast<f32x4*>(smem + G::GN_OFF);
+        for (int idx = tid; idx < p.K >> 1; idx += NT) dst[idx] = src[idx];
+    }
+    // one A fragment (8 consecutive channels from k) normalised in place: the fp32 multiply-add and the single rounding of gn_apply_kernel
+    auto gn_fold = [&](h16x8& a, int k) {
+        const f32x4* t = reinterpret_cast<const f32x4*>(gnt + 2 * k);
+        const f32x4 s0 = t[0], s1 = t[1], h0 = t[2], h1 = t[3];
+        // (the fp32 result is made opaque before it is rounded: left alone, multiply-add and conversion fuse into v_fma_mixlo / mixhi_f16,
+        //  which rounds the exact sum to fp16 ONCE - the pass rounds to fp32 first, and one element in some 8 000 then differs by an ulp)
+        float f[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            f[e] = (float)a[e] * s0[e] + h0[e];
+            f[4 + e] = (float)a[4 + e] * s1[e] + h1[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            asm("" : "+v"(f[e]));
+            a[e] = (h16)f[e];
+        }
+    };
     int slot_rd = 0, slot_wr = D % S;
     for (int kt = kt0; kt < nk; ++kt) {
 #ifdef PBE_STAMPS
@@ -764,6 +794,12 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
         __builtin_amdgcn_sched_barrier(0);           // fragment reads go out first, the DMA pieces behind them (tools/ubench_loop.hip:
         if (kt + D < nk) issue(kt + D, slot_wr);     //  cheaper there than before the reads, between the MFMAs or after them)
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (EXG) {
+#pragma unroll
+            for (int ks = 0; ks < (BOTH ? 2 : 1); ++ks)
+#pragma unroll
+                for (int j = 0; j < TM; ++j) gn_fold(fa[ks][j], kt * 64 + ks * 32 + fq * 8);
+        }
         PBE_ACC(acc_r_);
         PBE_ACC_T0();
         PBE_SETPRIO(1);
@@ -777,6 +813,10 @@ __global__ void __launch_bounds__(NWM* NWN * 64, ((EX & 4) != 0 && NWM * NWN == 
             for (int j = 0; j < TM; ++j) fa[0][j] = *reinterpret_cast<const h16x8*>(sa + a_rd + (rsw ^ 64) + j * 16 * 128);
 #pragma unroll
             for (int i = 0; i < TN; ++i) fw[0][i] = *reinterpret_cast<const h16x8*>(sw + w_rd + (rsw ^ 64) + i * 16 * 128);
+            if constexpr (EXG) {
+#pragma unroll
+                for (int j = 0; j < TM; ++j) gn_fold(fa[0][j], kt * 64 + 32 + fq * 8);
+            }
         }
 #pragma unroll
         for (int i = 0; i < TN; ++i)

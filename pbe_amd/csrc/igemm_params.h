@@ -62,6 +62,10 @@ struct IGemmP {
     unsigned char* mx_data[3]; unsigned char* mx_scale[3];
     int mx_c0[3], mx_layout[3]; float mx_alpha[3]; int mx_nr, mx_crow;
     int mx_H, mx_N, mx_D, mx_DP, mx_DV;
+    // GroupNorm folded into A (EX_GN instantiations, pbe_gemm_gnfold_f16): A holds the raw rows x, the tile's rows belong to ONE sample and every A
+    // fragment becomes (h16)(x * sc[k] + sh[k]) behind its LDS read - the value and the rounding of gn_apply_kernel (norm.hip).  gn_tab: fp32
+    // [samples][K / 8][16], sc | sh of 8 consecutive channels (pbe_groupnorm_table_f32); gn_tdiv = row tiles per sample
+    const float* gn_tab; int gn_tdiv; unsigned mg_gn_tdiv;
     int sv_ok;      // bias + row vector of a tile come from LDS (set per tile shape in launch_cfg)
 #ifdef PBE_STAMPS
     unsigned long long* stamps;     // diagnostic build only (tools/phase_stamps.py): 16 words per workgroup
@@ -137,6 +141,8 @@ static_assert(offsetof(IGemmP, bias) == 232 && offsetof(IGemmP, ldc) == 256 && o
 #define EX_ST 2
 #define EX_VT 4
 #define EX_MX 8        // MX-fp8 copy-out (IGemmP.mx_*): a compile-time form of copy_out, never a run-time branch of the fp16 kernels
+#define EX_GN 16       // GroupNorm applied to the A fragments (IGemmP.gn_*): a compile-time form of the main loop, its table behind the LDS image
+#define PBE_GN_MAX_K 1280
 #define PBE_GLDS16(gsrc, ldst)                                                                     \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc),         \
                                      (__attribute__((address_space(3))) void*)(ldst), 16, 0, 0)

@@ -74,7 +74,9 @@ static inline bool mx_tile_ok(const IGemmP& p, const TileCfg& t) {
     }
     return true;
 }
-static inline bool ex_needed(const IGemmP& p) { return p.alpha_cols > 0 || p.ln_stat || p.rstat || p.vt; }
+static inline bool ex_needed(const IGemmP& p) { return p.alpha_cols > 0 || p.ln_stat || p.rstat || p.vt || p.gn_tab; }
+// GroupNorm fold (IGemmP.gn_*; gn_tdiv holds the tokens per sample until launch_cfg divides it by the tile's rows): a tile's rows belong to one sample
+static inline bool gn_tile_ok(const IGemmP& p, const TileCfg& t) { return (t.forms & F_EX) && !(t.forms & F_ASTAT) && p.gn_tdiv % t.bm == 0; }
 
 // V^T columns start on a column tile (igemm_kernel's vtile): a tile with n0 < vt_col0 stores ALL its columns to C.  The widths the
 // extended-epilogue heuristic can choose among: is one of them a divisor of vt_col0?  (A requested tile that cannot run the problem
@@ -115,6 +117,7 @@ static Plan plan_igemm(const IGemmP& p, int batch, size_t ws_bytes, int want_cfg
         const TileCfg& t = kTiles[c];
         if (!(t.forms & forms) || ((t.forms & F_FORCED) && forced != c)) continue;
         if ((t.forms & F_ASTAT) && !pbe_astat_ok(p, batch, c)) continue;
+        if (p.gn_tab && !gn_tile_ok(p, t)) continue;                         // GroupNorm fold: a streaming tile whose rows lie inside one sample
         if (p.vt && p.vt_col0 % t.bn) continue;                              // extended epilogue: V^T columns start on a tile
         if (p.mx_nr && !mx_tile_ok(p, kTiles[p.sa ? t.f8 : c])) continue;    // MX-fp8 copy-out: the tile that launches keeps every block whole
         if (t.hpa && !halo_rows(p, mode, t.bm, t.hpa)) continue;              // a forced halo tile that does not apply falls back below
@@ -185,7 +188,9 @@ static void launch_cfg(IGemmP p, int batch, hipStream_t s) {
     using G = TileGeom<BM, BN, NWM, NWN, MODE, S, HPA, F8, EX>;      // the kernel's LDS layout
     p.sv_ok = !p.rowvec || p.group_rows % BM == 0 || (BM % p.group_rows == 0 && BM / p.group_rows <= G::SVEC_ROWS);
     static std::atomic<uint64_t> attr_done{0};
-    pbe_raise_dynamic_lds(attr_done, reinterpret_cast<const void*>(&igemm_kernel<BM, BN, NWM, NWN, MODE, S, HPA, PP, F8, EX>), G::LDS_BYTES);
+    pbe_raise_dynamic_lds(attr_done, reinterpret_cast<const void*>(&igemm_kernel<BM, BN, NWM, NWN, MODE, S, HPA, PP, F8, EX>), G::LDS_BYTES + G::GN_MAX_BYTES);
+    const int lds_bytes = G::LDS_BYTES + ((EX & EX_GN) ? 8 * p.K : 0);       // EX_GN: + this launch's sc | sh table (K <= PBE_GN_MAX_K)
+    if constexpr ((EX & EX_GN) != 0) { p.gn_tdiv /= BM; p.mg_gn_tdiv = mg_of((unsigned)p.gn_tdiv); }      // tokens per sample -> row tiles per sample
     const int tiles_m = cdiv(p.M, BM), tiles_n = cdiv(p.N, BN);
     dim3 grid((unsigned)(tiles_m * tiles_n), batch, p.splits > 1 ? p.splits : 1);
     igemm_prologue(p, batch, BM, BN, MODE);
@@ -196,7 +201,7 @@ static void launch_cfg(IGemmP p, int batch, hipStream_t s) {
     }
     // profiling brackets exactly ONE kernel each, so the event averages agree with rocprofv3's per-kernel averages
     pbe_prof_begin(MODE != 0 ? PBE_K_CONV3 : PBE_K_GEMM, s);
-    hipLaunchKernelGGL((igemm_kernel<BM, BN, NWM, NWN, MODE, S, HPA, PP, F8, EX>), grid, dim3(NWM * NWN * 64), G::LDS_BYTES, s, p);
+    hipLaunchKernelGGL((igemm_kernel<BM, BN, NWM, NWN, MODE, S, HPA, PP, F8, EX>), grid, dim3(NWM * NWN * 64), lds_bytes, s, p);
     {   // algorithmic bytes: every operand once (fp16): activations, weights, output, fused residual
         const double nout = p.act == PBE_ACT_GEGLU ? p.N * 0.5 : (double)p.N;
         const double a_el = MODE != 0 ? (double)(p.M / (p.Ho * p.Wo)) * p.H * p.Wd * (p.C1 + p.C2) : (double)p.M * p.K * batch;
@@ -235,7 +240,7 @@ static int launch_tile(int cfg, IGemmP p, int batch, hipStream_t s) {
     return pbe_set_error(PBE_ENOTSUP, "igemm: tile config %d is not instantiated in form 0x%x", cfg, FORM);
 }
 
-// ---- the instantiations live in ten translation units (igemm_dense / _conv / _halo / _f8 / _ex / _ex_ln / _ex_st / _ex_qkv / _ex_all / _astat
+// ---- the instantiations live in eleven translation units (igemm_dense / _conv / _halo / _f8 / _ex / _ex_ln / _ex_st / _ex_qkv / _ex_all / _ex_gn / _astat
 //      .hip), compiled in parallel ----
 int pbe_dispatch_dense(IGemmP p, int batch, hipStream_t s, size_t ws_bytes, int want_cfg);      // MODE 0
 int pbe_dispatch_conv(IGemmP p, int batch, hipStream_t s, size_t ws_bytes, int want_cfg);       // MODE 1 gather tiles; forwards F_HALO tiles to
@@ -246,6 +251,7 @@ int pbe_launch_ex_ln(int cfg, IGemmP p, int batch, hipStream_t s);
 int pbe_launch_ex_st(int cfg, IGemmP p, int batch, hipStream_t s);
 int pbe_launch_ex_qkv(int cfg, IGemmP p, int batch, hipStream_t s);
 int pbe_launch_ex_all(int cfg, IGemmP p, int batch, hipStream_t s);
+int pbe_launch_ex_gn(int cfg, IGemmP p, int batch, hipStream_t s);                                // GroupNorm fold + row statistics (igemm_ex_gn.hip)
 void pbe_launch_astat(int cfg, IGemmP p, hipStream_t s);                                                  // tiles 19 / 20 (igemm_astat.hip)
 // MX-fp8 copy-out forms (pbe_gemm_mx8out_f16): the q|k|v^T tiles (igemm_ex_qkv.hip, A-stationary tile 20 in igemm_astat.hip) and the fp8 tiles
 int pbe_launch_ex_qkv_mx8(int cfg, IGemmP p, int batch, hipStream_t s);

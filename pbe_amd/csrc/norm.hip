@@ -281,6 +281,59 @@ extern "C" int pbe_groupnorm_apply_f16(const void* X, const float* partials, int
     return PBE_OK;
 }
 
+// The normalisation pass as a TABLE: sc[b, c] = rstd gamma[c], sh[b, c] = beta[c] - mean sc[b, c] - the finalise and the fp32 expressions of
+// gn_apply_kernel, bit for bit - for a consumer that applies x * sc + sh itself (pbe_gemm_gnfold_f16).  One workgroup per sample;
+// table [B][C / 8][16]: sc | sh of 8 consecutive channels (what a GEMM lane reads for one A fragment).
+__global__ void __launch_bounds__(256) gn_table_kernel(const float* part, const float* gamma, const float* beta, float* table, int HW, int C,
+                                                        int groups, int nchunks, float eps) {
+    __shared__ float s_mean[64], s_rstd[64];
+    __shared__ double s_a[256], s_q[256];
+    const int cg = C / groups, tid = threadIdx.x, b = blockIdx.x;
+    {   // (gn_apply_kernel's finalise: same thread -> (group, slice) map, same summation order)
+        const int slices = 256 / groups;
+        const int g = tid % groups, sl = tid / groups;
+        double a = 0.0, q = 0.0;
+        if (sl < slices)
+            for (int c = sl; c < nchunks; c += slices) {
+                const float* src = part + (((long)b * nchunks + c) * groups + g) * 2;
+                a += (double)src[0]; q += (double)src[1];
+            }
+        s_a[tid] = a; s_q[tid] = q;
+        __syncthreads();
+        if (tid < groups) {
+            double ta = 0.0, tq = 0.0;
+            for (int s = 0; s < slices; ++s) { ta += s_a[s * groups + tid]; tq += s_q[s * groups + tid]; }
+            const double n = (double)HW * cg;
+            const double mean = ta / n;
+            double var = tq / n - mean * mean;
+            if (var < 0.0) var = 0.0;
+            s_mean[tid] = (float)mean;
+            s_rstd[tid] = (float)(1.0 / sqrt(var + (double)eps));
+        }
+        __syncthreads();
+    }
+    float* t = table + (long)b * 2 * C;
+    for (int c = tid; c < C; c += 256) {
+        const int g = c / cg;
+        const float a = s_rstd[g] * gamma[c];
+        t[(c >> 3) * 16 + (c & 7)] = a;
+        t[(c >> 3) * 16 + 8 + (c & 7)] = beta[c] - s_mean[g] * a;
+    }
+}
+
+extern "C" int pbe_groupnorm_table_f32(const float* partials, int32_t blocks, const float* gamma, const float* beta, float* table, int32_t B,
+                                       int32_t HW, int32_t C, int32_t groups, float eps, pbe_stream_t stream) {
+    PBE_REQUIRE(partials && gamma && beta && table && ((uintptr_t)table & 15) == 0, "pbe_groupnorm_table_f32: null operand or unaligned table");
+    PBE_REQUIRE(B > 0 && B <= 65535 && HW > 0 && C > 0 && C % 8 == 0 && C <= GN_MAX_C && blocks > 0, "pbe_groupnorm_table_f32: bad dims");
+    PBE_REQUIRE(groups > 0 && groups <= 64 && C % groups == 0, "pbe_groupnorm_table_f32: groups=%d must divide C=%d (<= 64)", groups, C);
+    hipStream_t s = (hipStream_t)stream;
+    pbe_prof_begin(PBE_K_GNORM, s);
+    hipLaunchKernelGGL(gn_table_kernel, dim3(B), dim3(256), 0, s, partials, gamma, beta, table, HW, C, groups, blocks, eps);
+    pbe_prof_end(PBE_K_GNORM, s, 8.0 * B * (double)C);
+    PBE_LAUNCH_CHECK("pbe_groupnorm_table_f32");
+    return PBE_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // LayerNorm: one wave per row, the row held in registers (<= 4 x 8 halfs per lane), two wave
 // reductions (mean, then centred variance — same two-pass form as torch's CPU kernel).

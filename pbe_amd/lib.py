@@ -54,6 +54,10 @@ class Mx8OutDesc(C.Structure):
     _fields_ = [("nranges", c_i32), ("channel_rows", c_i32), ("r", Mx8OutRange * 3)]
 
 
+class GnFoldDesc(C.Structure):
+    _fields_ = [("table", c_vp), ("ld", c_i64), ("tokens", c_i32)]
+
+
 class CtxAttnDesc(C.Structure):
     _fields_ = [("X", c_vp), ("Y", c_vp), ("Kq", c_vp), ("colsum", c_vp), ("kbias", c_vp), ("Vo", c_vp), ("bias", c_vp), ("ln_stats", c_vp),
                 ("row_stats_out", c_vp), ("M", c_i32), ("C", c_i32), ("tokens", c_i32), ("H", c_i32), ("Nk", c_i32),
@@ -72,6 +76,7 @@ SYMBOLS = {
     "pbe_sizeof_attn_mx8_desc": (c_sz, []),
     "pbe_sizeof_mx8_out_desc": (c_sz, []),
     "pbe_sizeof_ctx_attn_desc": (c_sz, []),
+    "pbe_sizeof_gnfold_desc": (c_sz, []),
     "pbe_sizeof_igemm_params": (c_sz, []),
     "pbe_sizeof_igemm_head": (c_sz, []),
     "pbe_ctx_attention_f16": (c_i32, [C.POINTER(CtxAttnDesc), c_vp]),
@@ -98,6 +103,9 @@ SYMBOLS = {
     "pbe_attention_mx8": (c_i32, [C.POINTER(AttnMx8Desc), c_vp]),
     "pbe_gemm_mx8out_f16": (c_i32, [C.POINTER(GemmDesc), C.POINTER(Mx8OutDesc), c_vp]),
     "pbe_gemm_mx8out_plan": (c_i32, [C.POINTER(GemmDesc), C.POINTER(Mx8OutDesc), C.POINTER(c_i32)]),
+    "pbe_groupnorm_table_f32": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
+    "pbe_gemm_gnfold_f16": (c_i32, [C.POINTER(GemmDesc), C.POINTER(GnFoldDesc), c_vp]),
+    "pbe_gemm_gnfold_plan": (c_i32, [C.POINTER(GemmDesc), C.POINTER(GnFoldDesc), C.POINTER(c_i32)]),
     "pbe_softmax_rows_f16": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_f32, c_vp]),
     "pbe_geglu_f16": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
     "pbe_timestep_embedding_f16": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f32, c_vp]),
@@ -155,7 +163,7 @@ SYMBOLS = {
 _lib = None
 _lock = threading.Lock()
 
-SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_astat.hip", "attention.hip", "attention_mx8.hip", "ctx_attention.hip", "norm.hip",
+SOURCES = ["runtime.hip", "igemm.hip", "igemm_dense.hip", "igemm_conv.hip", "igemm_halo.hip", "igemm_f8.hip", "igemm_ex.hip", "igemm_ex_ln.hip", "igemm_ex_st.hip", "igemm_ex_qkv.hip", "igemm_ex_all.hip", "igemm_ex_gn.hip", "igemm_astat.hip", "attention.hip", "attention_mx8.hip", "ctx_attention.hip", "norm.hip",
            "elementwise.hip", "window.hip", "holes.hip", "maskshape.hip", "tone.hip", "tone_field.hip", "exemplar.hip", "noise.hip"]
 # the shared headers, relative to this directory: every object file depends on them (build.py) and the source hash covers them
 HEADERS = [os.path.join("csrc", f) for f in ("common.h", "igemm_params.h", "igemm_mx8_out.h", "igemm_kernel.h", "igemm_plan.h", "tone_bytes.h", "u8_norm.h")] + [
@@ -204,7 +212,8 @@ def load() -> C.CDLL:
         if v != ABI_VERSION:
             raise PbeError(f"libpbe_hip.so ABI version {v} != expected {ABI_VERSION}")
         for cls, fn in ((GemmDesc, lib.pbe_sizeof_gemm_desc), (Conv3x3Desc, lib.pbe_sizeof_conv3x3_desc), (AttnDesc, lib.pbe_sizeof_attn_desc),
-                        (AttnMx8Desc, lib.pbe_sizeof_attn_mx8_desc), (Mx8OutDesc, lib.pbe_sizeof_mx8_out_desc), (CtxAttnDesc, lib.pbe_sizeof_ctx_attn_desc)):
+                        (AttnMx8Desc, lib.pbe_sizeof_attn_mx8_desc), (Mx8OutDesc, lib.pbe_sizeof_mx8_out_desc), (CtxAttnDesc, lib.pbe_sizeof_ctx_attn_desc),
+                        (GnFoldDesc, lib.pbe_sizeof_gnfold_desc)):
             if C.sizeof(cls) != fn():
                 raise PbeError(f"{cls.__name__}: ctypes layout is {C.sizeof(cls)} bytes, libpbe_hip.so was compiled with {fn()}")
         built, want = lib.pbe_source_hash().decode(), source_hash()

@@ -91,7 +91,8 @@ def _tile_cfg(key: str) -> int:
     return int(_TUNED.get(key, -1))
 
 
-# ---- tiled launches, kind "gemm" / "batch" (2-D / 3-D strided batch pbe_gemm_f16), "conv" (pbe_conv3x3_f16), "mx8" (pbe_gemm_mx8out_f16) ----
+# ---- tiled launches, kind "gemm" / "batch" (2-D / 3-D strided batch pbe_gemm_f16), "conv" (pbe_conv3x3_f16), "mx8" (pbe_gemm_mx8out_f16),
+#      "gn" (pbe_gemm_gnfold_f16); mx = the second descriptor of the last two ----
 def _key(kind: str, d, stats: bool = False) -> str:
     """Shape key of a launch (tuned table, _RECORD, _PLANS); stats: the GEMM also writes row statistics (row_stats_out is set later)."""
     if kind == "conv":
@@ -105,6 +106,8 @@ def _plan(kind: str, d, mx=None) -> list:
     out, lib = (C.c_int32 * 6)(), _l.load()
     if kind == "mx8":
         rc = lib.pbe_gemm_mx8out_plan(C.byref(d), C.byref(mx), out)
+    elif kind == "gn":
+        rc = lib.pbe_gemm_gnfold_plan(C.byref(d), C.byref(mx), out)
     else:
         rc = (lib.pbe_conv3x3_plan if kind == "conv" else lib.pbe_gemm_plan)(C.byref(d), out, C.byref(C.c_size_t()))
     _l.check(rc, f"plan ({kind})")
@@ -162,18 +165,18 @@ def _pinned(kind: str, d, mx=None, stats: bool = False) -> int:
             big.ln_stats_ld = max(big.ln_stats_ld, big.M)
         if big.row_stats_out:
             big.row_stats_ld = max(big.row_stats_ld, big.M)
-        for i in range(0 if bmx is None else bmx.nranges):
+        for i in range(bmx.nranges if kind == "mx8" else 0):
             bmx.r[i].B *= s
     key = _key(kind, big, stats)
     big.tile_cfg = int(_FORCE_CFG) if _FORCE_CFG is not None else int(_TUNED.get(key, -1))
-    if bmx is not None:
+    if kind == "mx8":
         big.tile_cfg = _mx8_tile(big, bmx, big.tile_cfg)
     pl = _plan(kind, big, bmx)
     hit = pl[0] | (max(1, pl[1]) << 8)
     small = type(d).from_buffer_copy(d)
     small.tile_cfg = hit
     got = _plan(kind, small, mx)
-    if got[1] != max(1, pl[1]) or (kind == "gemm" and small.row_stats_out and got[3] != pl[3]):      # (row statistics: one partial per column tile of BN)
+    if got[1] != max(1, pl[1]) or (kind in ("gemm", "gn") and small.row_stats_out and got[3] != pl[3]):      # (row statistics: one partial per column tile of BN)
         import warnings
         _PIN_MISSES.append((key, pl[0], pl[1], got[0], got[1]))
         warnings.warn(f"pinned_batch_scale({s}): {key} plans tile {pl[0]} / split-K {pl[1]} at the scaled batch but the "
@@ -211,16 +214,18 @@ def _launch(kind: str, d, mx=None, row_stats=None):
     d.tile_cfg = _tile(kind, d, key, mx, row_stats is not None)
     stats = None
     if row_stats is not None:                   # one partial per column tile of the plan this launch will take
-        stats = row_stats(_plan(kind, d)[5])
+        stats = row_stats(_plan(kind, d, mx)[5])
         d.row_stats_out, d.row_stats_ld = stats.ptr(), stats.ld
     if _PLANS is not None:
         _PLANS.append((key, *_plan(kind, d, mx)[:5]))
     if _TIMES is not None:                      # the _TIMES key: shape key + epilogue form
         key += "" if kind == "conv" else "|mx8" if kind == "mx8" else \
-            f"|a{d.act}{'r' * bool(d.resid)}{'v' * bool(d.rowvec)}{'L' * bool(d.ln_stats)}{'S' * (stats is not None)}{'T' * bool(d.VT)}"
+            f"|a{d.act}{'r' * bool(d.resid)}{'v' * bool(d.rowvec)}{'L' * bool(d.ln_stats)}{'S' * (stats is not None)}{'T' * bool(d.VT)}{'G' * (kind == 'gn')}"
     with _timed(key):
         if kind == "mx8":
             _l.check(_l.load().pbe_gemm_mx8out_f16(C.byref(d), C.byref(mx), _stream()), "pbe_gemm_mx8out_f16")
+        elif kind == "gn":
+            _l.check(_l.load().pbe_gemm_gnfold_f16(C.byref(d), C.byref(mx), _stream()), "pbe_gemm_gnfold_f16")
         elif kind == "conv":
             _l.check(_l.load().pbe_conv3x3_f16(C.byref(d), _stream()), "pbe_conv3x3_f16")
         else:
@@ -282,15 +287,28 @@ def row_stats(x: torch.Tensor) -> RowStats:
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, a2: Optional[torch.Tensor] = None,
          rowvec: Optional[torch.Tensor] = None, group_rows: int = 0, resid: Optional[torch.Tensor] = None, act: int = ACT_NONE,
          alpha: float = 1.0, bias_per_row: bool = False, out: Optional[torch.Tensor] = None, alpha_cols: int = 0, ln=None,
-         row_stats=False, vt: Optional[torch.Tensor] = None, vt_col0: int = 0, vt_tokens: int = 0):
+         row_stats=False, vt: Optional[torch.Tensor] = None, vt_col0: int = 0, vt_tokens: int = 0, gn=None):
     """out[m, n] = act(alpha * sum_k [a | a2][m, k] w[n, k] + bias + rowvec[m // group_rows, n]) + resid[m, n].
     2-D operands, or 3-D [batch, rows, cols] for a strided batch (w may have batch 1).
 
     Extended epilogue (2-D operands; include/pbe_hip.h, pbe_gemm_desc): alpha_cols = alpha on columns < alpha_cols only;
     ln = (RowStats of a's rows, colsum fp32 [N], eps): LayerNorm(a) is folded in (w = W * gamma, bias = W beta + b);
     row_stats = True (or a RowStats to fill, e.g. a slice of a shared buffer): also returns the RowStats of the output rows -> (out, stats);
-    vt [B, N - vt_col0, >= vt_tokens]: columns >= vt_col0 are written transposed there (V^T), `out` then has vt_col0 columns."""
+    vt [B, N - vt_col0, >= vt_tokens]: columns >= vt_col0 are written transposed there (V^T), `out` then has vt_col0 columns.
+    gn = (GroupStats of a's tensor, gamma, beta, eps[, tokens per sample]): a holds RAW rows and the result is that of
+    gemm(GroupNorm(a), ...), bit for bit - folded into the A operand (pbe_gemm_gnfold_f16) where a tile's rows divide a sample's tokens
+    (default: M / samples), else by the separate normalisation pass."""
     _h(a, "gemm a"); _h(w, "gemm w")
+    fold = None
+    if gn is not None:
+        if a.dim() != 2 or a2 is not None or ln is not None or vt is not None or alpha_cols or act == ACT_GEGLU:
+            raise _l.PbeError("gemm: gn takes a 2-D problem with one source and no LayerNorm fold, V^T, column alpha or GEGLU")
+        gst, g_gamma, g_beta, g_eps = gn[:4]
+        g_tok = int(gn[4]) if len(gn) > 4 else a.shape[0] // gst.batch
+        _f(g_gamma, "gemm gn gamma"); _f(g_beta, "gemm gn beta")
+        if not a.is_contiguous() or g_tok <= 0 or a.shape[0] > gst.batch * g_tok or g_gamma.numel() != a.shape[1] or g_beta.numel() != a.shape[1]:
+            raise _l.PbeError("gemm: gn needs contiguous rows of the statistics' samples and affine vectors of a's width")
+        fold = _l.GnFoldDesc(0, 2 * a.shape[1], g_tok)
     batch = 1
     sA = sW = sC = sR = 0
     if a.dim() == 3:
@@ -358,7 +376,28 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         if row_stats.parts < parts:
             raise _l.PbeError(f"gemm: row_stats buffer holds {row_stats.parts} partials, the plan writes {parts}")
         return RowStats(row_stats.buf, parts, row_stats.ld, row_stats.row0)
-    stats = _launch("batch" if a.dim() == 3 else "gemm", d, row_stats=None if row_stats is False else fill)
+    if fold is not None:
+        Cc = a.shape[1]
+        d.tile_cfg, fold.table = -1, 16
+        if row_stats is not False:
+            d.row_stats_out = 8
+        try:                                    # eligible?  (host-only plan query on the form that would launch)
+            _plan("gn", d, fold)
+        except _l.PbeError:
+            fold = None
+        d.row_stats_out = None
+        if fold is None:                        # the separate normalisation pass, then the plain launch
+            if M != gst.batch * g_tok:
+                raise _l.PbeError("gemm: gn without the fold needs every row of the statistics' samples")
+            a = _groupnorm_apply(a, gst, g_gamma, g_beta, g_eps, False)      # (bound to `a`: alive until the launch is queued)
+            d.A = _p(a)
+        else:
+            table = torch.empty((gst.batch, 2 * Cc), dtype=torch.float32, device=a.device)
+            with _timed(f"nt:{gst.batch}:{g_tok}:{Cc}"):
+                _l.check(_l.load().pbe_groupnorm_table_f32(_p(gst.buf), gst.blocks, _p(g_gamma), _p(g_beta), _p(table), gst.batch, g_tok, Cc, gst.groups,
+                                                           float(g_eps), _stream()), "pbe_groupnorm_table_f32")
+            fold.table = table.data_ptr()
+    stats = _launch("gn" if fold is not None else "batch" if a.dim() == 3 else "gemm", d, mx=fold, row_stats=None if row_stats is False else fill)
     return (out, stats) if row_stats is not False else out
 
 
@@ -449,6 +488,24 @@ class GroupStats:
         return self.buf.view(-1)[: self.batch * self.blocks * self.groups * 2].view(self.batch, self.blocks, self.groups, 2)
 
 
+def group_stats_of(x: torch.Tensor, groups: int = 32) -> Optional[GroupStats]:
+    """The statistics x's producing conv left on it (conv3x3(group_stats=G)) while they still describe it, else None."""
+    st = getattr(x, "_pbe_gstats", None)
+    ok = st is not None and st.groups == groups and st.batch == x.shape[0] and st.version == x._version      # (an in-place edit since the conv voids them)
+    return st if ok else None
+
+
+def _groupnorm_apply(x, st, gamma, beta, eps, silu):
+    """The normalisation pass alone, from a producer's statistics (one read, one write): x holds st.batch whole samples, channels last."""
+    B, C1 = st.batch, x.shape[-1]
+    HW = x.numel() // (B * C1)
+    y = torch.empty_like(x)
+    with _timed(f"n:{B}:{HW}:{C1}:0"):
+        _l.check(_l.load().pbe_groupnorm_apply_f16(_p(x), _p(st.buf), st.blocks, _p(gamma), _p(beta), _p(y), B, HW, C1, st.groups, float(eps),
+                                                   1 if silu else 0, _stream()), "pbe_groupnorm_apply_f16")
+    return y
+
+
 def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, silu: bool, *, x2: Optional[torch.Tensor] = None,
               groups: int = 32) -> torch.Tensor:
     """GroupNorm(+SiLU) of NHWC x (optionally the channel concat x | x2); output has C1+C2 channels."""
@@ -466,14 +523,9 @@ def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     if gamma.numel() != C1 + C2 or beta.numel() != C1 + C2:
         raise _l.PbeError("groupnorm: affine length mismatch")
     lib = _l.load()
-    st = getattr(x, "_pbe_gstats", None)
-    if st is not None and x2 is None and st.groups == groups and st.batch == B and st.version == x._version:      # (an in-place edit since the conv voids them)
-        # the producing conv left this tensor's statistics: normalisation pass only (one read, one write)
-        y = torch.empty_like(x)
-        with _timed(f"n:{B}:{HW}:{C1}:0"):
-            _l.check(lib.pbe_groupnorm_apply_f16(_p(x), _p(st.buf), st.blocks, _p(gamma), _p(beta), _p(y), B, HW, C1, groups, float(eps), 1 if silu else 0,
-                                                 _stream()), "pbe_groupnorm_apply_f16")
-        return y
+    st = group_stats_of(x, groups) if x2 is None else None
+    if st is not None:                          # the producing conv left this tensor's statistics: normalisation pass only
+        return _groupnorm_apply(x, st, gamma, beta, eps, silu)
     ws = workspace(x.device, "gn", lib.pbe_groupnorm_workspace_bytes(B, HW), 1 << 21)
     y = torch.empty(tuple(x.shape[:-1]) + (C1 + C2,), dtype=torch.float16, device=x.device)
     with _timed(f"n:{B}:{HW}:{C1}:{C2}"):

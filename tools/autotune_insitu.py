@@ -62,7 +62,8 @@ def main():
     ap.add_argument("--merge", default="", help="start from this table; shapes measured here replace their entries")
     ap.add_argument("--image-size", type=int, default=512, help="768 = BASELINE configs[4] geometry")
     ap.add_argument("--precision", default="fp16", choices=("fp16", "fp8"))
-    ap.add_argument("--only-regex", default="", help="keep only shape keys matching this regex (e.g. ':2$' = the phase-form upsampling convs); candidates: every tile, no split-K")
+    ap.add_argument("--only-regex", default="", help="keep only shape keys matching this regex (e.g. ':2$' = the phase-form upsampling convs); candidates: every tile, the split-K factors of --regex-splits")
+    ap.add_argument("--regex-splits", default="1", help="with --only-regex: the split-K factors tried on every tile (e.g. 1,2,3,4 for deep-K small-M GEMMs)")
     ap.add_argument("--only-prefix", default="", help="keep only shape keys with this prefix (gx: = the extended-epilogue GEMMs); candidates are then its tiles only")
     a = ap.parse_args()
     import cases
@@ -84,7 +85,7 @@ def main():
             one_pass(model, inp, a.steps, -1)                                   # warm: packs, workspaces
             cands = [cfg | (sp << 8) for cfg in range(NCFG) if cfg not in SKIP for sp in SPLITS]
             if a.only_regex:
-                cands = [cfg | (1 << 8) for cfg in range(NCFG) if cfg not in SKIP]
+                cands = [cfg | (int(sp) << 8) for cfg in range(NCFG) if cfg not in SKIP for sp in a.regex_splits.split(",")]
             if a.only_prefix == "gx:":                                            # extended epilogue: its instantiated tiles, never split-K
                 cands = [cfg | (1 << 8) for cfg in (3, 4, 5, 6, 8, 9, 15, 16, 17, 18)]
             data = {}                                                            # key -> {(cfg, splits): [us, ...]}
