@@ -21,6 +21,7 @@ from torch import nn
 from pbe_amd import ops
 from pbe_amd.hipmodule import HipModule, f32, require_gpu
 from pbe_amd.lib import PbeError
+from ldm.modules.attention import Conditioning
 from ldm.modules.diffusionmodules.util import extract_into_tensor, make_beta_schedule
 from ldm.modules.distributions.distributions import DiagonalGaussianDistribution
 from ldm.util import count_params, default, instantiate_from_config
@@ -70,13 +71,7 @@ class DiffusionWrapper(nn.Module):
         if self.conditioning_key is None:
             raise PbeError("DiffusionWrapper: unconditional U-Net is not on the Paint-by-Example path")
         cc = c_crossattn[0] if len(c_crossattn) == 1 else torch.cat(c_crossattn, 1)
-        if context_maps is not None:
-            return self.diffusion_model(x, t, context=cc, context_weights=context_weights, context_regions=context_regions, context_maps=context_maps)
-        if context_regions is not None:
-            return self.diffusion_model(x, t, context=cc, context_weights=context_weights, context_regions=context_regions)
-        if context_weights is None:
-            return self.diffusion_model(x, t, context=cc)
-        return self.diffusion_model(x, t, context=cc, context_weights=context_weights)
+        return self.diffusion_model(x, t, context=cc, **Conditioning(cc, context_weights, context_regions, context_maps).kwargs())
 
 
 class DDPM(nn.Module):
@@ -253,13 +248,7 @@ class LatentDiffusion(DDPM):
         context_maps: an attention.ContextMaps that collects the attribution maps of the call, or None."""
         if not isinstance(cond, dict):
             cond = {"c_crossattn": cond if isinstance(cond, list) else [cond]}
-        if context_weights is not None:
-            cond = dict(cond, context_weights=context_weights)
-        if context_regions is not None:
-            cond = dict(cond, context_regions=context_regions)
-        if context_maps is not None:
-            cond = dict(cond, context_maps=context_maps)
-        out = self.model(x_noisy, t, **cond)
+        out = self.model(x_noisy, t, **dict(cond, **Conditioning(None, context_weights, context_regions, context_maps).kwargs()))
         return out[0] if isinstance(out, tuple) and not return_ids else out
 
     def prepare(self):

@@ -21,7 +21,7 @@ import torch
 
 from pbe_amd import ops
 from pbe_amd.lib import PbeError
-from ldm.models.diffusion.plms import PLMSSampler, guidance_context, guidance_maps, guidance_regions, guidance_weights, inpaint_kwargs
+from ldm.models.diffusion.plms import PLMSSampler
 
 
 def dpmpp_coefficients(alphas, alphas_prev, order=2):
@@ -53,82 +53,30 @@ def dpmpp_coefficients(alphas, alphas_prev, order=2):
 
 
 class DPMSolverSampler(PLMSSampler):
-    @torch.no_grad()
-    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
-               eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
-               x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, disable_tqdm=True,
-               conditioning_weights=None, conditioning_regions=None, conditioning_maps=None, order=2, seeds=None, seed_sub=None, **kwargs):
-        """The arguments of DDIMSampler.sample (conditioning_weights / conditioning_regions / conditioning_maps / seeds / seed_sub as in
-        PLMSSampler.sample) plus order: 2 = DPM-Solver++(2M), 1 = its first order, which is DDIM with eta = 0.  eta must be 0."""
-        if conditioning is None:
-            raise PbeError("DPMSolverSampler.sample: conditioning is required")
-        if quantize_x0 or score_corrector is not None or noise_dropout != 0.:
-            raise PbeError("DPMSolverSampler: quantize_x0 / score_corrector / noise_dropout are not on the Paint-by-Example path")
-        if (mask is None) != (x0 is None):
-            raise PbeError("DPMSolverSampler: mask and x0 go together (ddim.py:178-181)")
+    accepts_rest = True
+    blend_ref = "ddim.py:178-181"
+
+    def _own_options(self, conditioning, batch_size, eta, temperature, kwargs):
+        """sample(order=): 2 = DPM-Solver++(2M), 1 = its first order, which is DDIM with eta = 0.  eta must be 0."""
         if eta != 0:
             raise PbeError("DPMSolverSampler: eta must be 0 (the stochastic SDE-DPM-Solver++ variant is not built)")
-        if order not in (1, 2):
-            raise PbeError(f"DPMSolverSampler: order must be 1 or 2, got {order!r}")
-        self.make_schedule(ddim_num_steps=S, ddim_eta=0., verbose=verbose)
-        C, H, W = shape
-        try:
-            x_T = self._seed_run(seeds, seed_sub, x_T, (batch_size, C, H, W))
-            return self.dpm_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
-                                     log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                     unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
-                                     conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
-                                     conditioning_maps=conditioning_maps, order=order, **kwargs)
-        finally:
-            self._seeded = None
+        if kwargs.get("order", 2) not in (1, 2):
+            raise PbeError(f"DPMSolverSampler: order must be 1 or 2, got {kwargs['order']!r}")
+        return 0., self.dpm_sampling, kwargs
 
     @torch.no_grad()
     def dpm_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100, unconditional_guidance_scale=1.,
                      unconditional_conditioning=None, timesteps=None, mask=None, x0=None, conditioning_weights=None,
                      conditioning_regions=None, conditioning_maps=None, order=2, **kwargs):
-        device = self.model.betas.device
-        if self.require_gpu and device.type != "cuda":
-            raise PbeError("DPMSolverSampler: the model must live on an MI355X; there is no CPU path")
-        b = shape[0]
-        img = (torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)).contiguous()
-        if "rest" in kwargs and "test_model_kwargs" not in kwargs:       # ddim.py:201-202: rest = cat(z_inpaint, mask)
-            rest = kwargs["rest"]
-            z_inp, msk = rest[:, :4], rest[:, 4:5]
-        else:
-            z_inp, msk = inpaint_kwargs(kwargs)
-        z_inp = z_inp.to(device=device, dtype=torch.float32).contiguous()
-        msk = msk.to(device=device, dtype=torch.float32).contiguous()
-        guided = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
-        if guided:
-            ctx = guidance_context(cond, unconditional_conditioning, b, device)      # a one-token uc is repeated to cond's K tokens (exact: plms.py)
-        else:
-            ctx = cond.to(device=device, dtype=torch.float16).contiguous()
-        dup = 2 if guided else 1
-        ctx_w = guidance_weights(conditioning_weights, cond, b, guided)
-        ctx_r = guidance_regions(conditioning_regions, cond, b, guided)
-        ctx_m = guidance_maps(conditioning_maps, cond, b, device)
-        scale = float(unconditional_guidance_scale)
-        time_range = np.flip(self._schedule_subset(timesteps))
-        total = time_range.shape[0]
+        run = self._begin_run(cond, shape, x_T, timesteps, unconditional_guidance_scale, unconditional_conditioning, mask, x0,
+                              conditioning_weights, conditioning_regions, conditioning_maps, kwargs)
         # the run covers grid rows total-1 .. 0: its first and last steps are first order whatever prefix `timesteps=` selects
-        coef = dpmpp_coefficients(self.ddim_alphas[:total], self.ddim_alphas_prev[:total], order) if total else None
-        if mask is not None:
-            mask, x0 = mask.to(device=device, dtype=torch.float32), x0.to(device=device, dtype=torch.float32)
-        inter = {"x_inter": [img], "pred_x0": [img]}
+        coef = dpmpp_coefficients(self.ddim_alphas[:run.total], self.ddim_alphas_prev[:run.total], order) if run.total else None
         x0_prev = None                                                    # the history: the previous step's data prediction
-        for i, step in enumerate(time_range):
-            index = total - i - 1
-            if mask is not None:
-                img = self._blend_known(img, x0, mask, step)
-            eps = self._eps(img, step, ctx, z_inp, msk, dup, ctx_w, ctx_r, ctx_m)
+
+        def update(i, index, img, eps):
+            nonlocal x0_prev
             k = coef[index].tolist()
-            img, pred_x0 = ops.dpmpp_update(eps, dup, scale, img, x0_prev if k[4] != 0.0 else None, k)
-            x0_prev = pred_x0
-            if callback:
-                callback(i)
-            if img_callback:
-                img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total - 1:
-                inter["x_inter"].append(img)
-                inter["pred_x0"].append(pred_x0)
-        return img, inter
+            img, x0_prev = ops.dpmpp_update(eps, run.dup, run.scale, img, x0_prev if k[4] != 0.0 else None, k)
+            return img, x0_prev
+        return self._run_loop(run, update, callback, img_callback, log_every_t)

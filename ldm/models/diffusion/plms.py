@@ -20,6 +20,7 @@ Unsupported reference options (score_corrector, quantize_denoised, eta != 0 - th
 noise_dropout, ddim_use_original_steps) raise instead of being silently ignored.
 """
 import math
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -27,6 +28,7 @@ import torch
 from pbe_amd import ops
 from pbe_amd.graph import GraphedUNet, graphs_enabled
 from pbe_amd.lib import PbeError
+from ldm.modules.attention import Conditioning
 from ldm.modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps
 
 _AB = {0: (1.0,), 1: (3 / 2, -1 / 2), 2: (23 / 12, -16 / 12, 5 / 12), 3: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
@@ -64,17 +66,24 @@ def guidance_context(cond, uc, b, device):
     return torch.cat((uc.to(torch.float16), cond.to(torch.float16))).contiguous()
 
 
+def _guidance_rows(v, cond, b, guided, name, extra, per):
+    """The body of guidance_weights (extra = ()) and guidance_regions (extra = ("Hr", "Wr")): [b, K, *extra] -> fp64 on the host, with
+    a leading half of ones under guidance."""
+    if v is None:
+        return None
+    v = torch.as_tensor(v).detach().to("cpu", torch.float64)
+    if v.dim() != 2 + len(extra) or tuple(v.shape[:2]) != (b, cond.shape[1]):
+        want = ", ".join([str(b), str(cond.shape[1]), *extra])
+        raise PbeError(f"sampler: {name} must be [{want}] ({per} per conditioning token), got {tuple(v.shape)}")
+    return torch.cat((torch.ones_like(v), v)).contiguous() if guided else v.contiguous()
+
+
 def guidance_weights(weights, cond, b, guided):
     """Exemplar weights of the context guidance_context builds: conditioning_weights [b, K] (>= 0, positive sum per sample, 0 = token
     absent) -> fp64 host tensor [2b, K] for a guidance pair (the unconditional half gets ones: on K copies of one token any weights
     with a positive sum give that token, for the reason above) or [b, K] unguided; None for None.  One tensor per run, so the U-Net's
     per-context cache sees one identity across the steps; validated where the operands are built (attention.prepare_context_weights)."""
-    if weights is None:
-        return None
-    w = torch.as_tensor(weights).detach().to("cpu", torch.float64)
-    if tuple(w.shape) != (b, cond.shape[1]):
-        raise PbeError(f"sampler: conditioning_weights must be [{b}, {cond.shape[1]}] (one per conditioning token), got {tuple(w.shape)}")
-    return torch.cat((torch.ones_like(w), w)).contiguous() if guided else w.contiguous()
+    return _guidance_rows(weights, cond, b, guided, "conditioning_weights", (), "one")
 
 
 def guidance_regions(regions, cond, b, guided):
@@ -82,12 +91,7 @@ def guidance_regions(regions, cond, b, guided):
     position) -> fp64 host tensor [2b, K, Hr, Wr] for a guidance pair (the unconditional half gets ones: uc is one token repeated K
     times, and any weights with a positive sum give that token) or [b, K, Hr, Wr] unguided; None for None.  One tensor per run, like
     guidance_weights; validated where the tables are built (attention.prepare_context_regions)."""
-    if regions is None:
-        return None
-    r = torch.as_tensor(regions).detach().to("cpu", torch.float64)
-    if r.dim() != 4 or tuple(r.shape[:2]) != (b, cond.shape[1]):
-        raise PbeError(f"sampler: conditioning_regions must be [{b}, {cond.shape[1]}, Hr, Wr] (one map per conditioning token), got {tuple(r.shape)}")
-    return torch.cat((torch.ones_like(r), r)).contiguous() if guided else r.contiguous()
+    return _guidance_rows(regions, cond, b, guided, "conditioning_regions", ("Hr", "Wr"), "one map")
 
 
 def guidance_maps(maps, cond, b, device):
@@ -148,12 +152,23 @@ class PLMSSampler(object):
         self.register_buffer("ddim_alphas_prev", a_prev)
         self.register_buffer("ddim_sqrt_one_minus_alphas", np.sqrt(1. - a))
 
+    accepts_rest = False              # ddim.py:201-202's `rest=` spelling of the inpainting inputs: DDIMSampler and DPMSolverSampler take it
+    blend_ref = "plms.py:150-153"     # where the reference blends mask / x0 (named when only one of them is given)
+
+    def _own_options(self, conditioning, batch_size, eta, temperature, kwargs):
+        """What the shared sample() leaves to each sampler: its own checks -> (the schedule's eta, its loop, the loop's further keywords)."""
+        if conditioning.shape[0] != batch_size:
+            print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+        return eta, self.plms_sampling, kwargs
+
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None, quantize_x0=False,
                eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, conditioning_weights=None,
                conditioning_regions=None, conditioning_maps=None, seeds=None, seed_sub=None, **kwargs):
-        """seeds: per-sample noise seeds (an int64 tensor [batch_size] on the GPU or ints in [0, 2^64)), seed_sub their substreams or
+        """The sample() of all three samplers; what is a sampler's own is in its _own_options (DDIMSampler: eta > 0 and temperature;
+        DPMSolverSampler: order=).
+        seeds: per-sample noise seeds (an int64 tensor [batch_size] on the GPU or ints in [0, 2^64)), seed_sub their substreams or
         None: x_T (which must then be None) and the q_sample noise are drawn by pbe_amd.noise.SeededNoise, sample i from seeds[i] alone.
         conditioning_weights: per-sample exemplar weights [batch_size, K] over conditioning's K tokens (>= 0, positive sum per sample;
         0 = token absent, so a ragged batch is padded to one K), or None: every token counts once.
@@ -163,28 +178,28 @@ class PLMSSampler(object):
         each conditioning token received at each position, from every U-Net call of the run (the probe call included); under guidance
         only the CONDITIONAL half is collected.  With it every level runs the fused cross-attention kernel: with regions the samples are
         those of the run without it bit for bit, without regions those of a run whose blocks have ctx_fused_max_width = 1280."""
+        name = type(self).__name__
         if conditioning is None:
-            raise PbeError("PLMSSampler.sample: conditioning is required")
-        if conditioning.shape[0] != batch_size:
-            print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+            raise PbeError(f"{name}.sample: conditioning is required")
         if quantize_x0 or score_corrector is not None or noise_dropout != 0.:
-            raise PbeError("PLMSSampler: quantize_x0 / score_corrector / noise_dropout are not on the Paint-by-Example path")
+            raise PbeError(f"{name}: quantize_x0 / score_corrector / noise_dropout are not on the Paint-by-Example path")
         if (mask is None) != (x0 is None):
-            raise PbeError("PLMSSampler: mask and x0 go together (plms.py:150-153)")
+            raise PbeError(f"{name}: mask and x0 go together ({self.blend_ref})")
+        eta, loop, kwargs = self._own_options(conditioning, batch_size, eta, temperature, kwargs)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         try:
             x_T = self._seed_run(seeds, seed_sub, x_T, (batch_size, C, H, W))
-            return self.plms_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T,
-                                      log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                      unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
-                                      conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
-                                      conditioning_maps=conditioning_maps, **kwargs)
+            return loop(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback, x_T=x_T, log_every_t=log_every_t,
+                        unconditional_guidance_scale=unconditional_guidance_scale, unconditional_conditioning=unconditional_conditioning,
+                        mask=mask, x0=x0, conditioning_weights=conditioning_weights, conditioning_regions=conditioning_regions,
+                        conditioning_maps=conditioning_maps, **kwargs)
         finally:
             self._seeded = None
 
     # ---- one U-Net evaluation with guidance (plms.py:181-195) -----------------------------------
-    def _eps(self, x, step, ctx, z_inp, msk, dup, ctx_w=None, ctx_r=None, ctx_m=None):
+    def _eps(self, x, step, cond, z_inp, msk, dup):
+        """cond: the run's attention.Conditioning.  A plain context hands the U-Net no keyword beyond paired= and step=."""
         b = x.shape[0]
         t = torch.full((dup * b,), int(step), device=x.device, dtype=torch.int64)
         unet = self.model.model.diffusion_model
@@ -194,18 +209,9 @@ class PLMSSampler(object):
         if (graphs_enabled(dup * b) if self.use_graph is None else self.use_graph) and x.is_cuda:      # launch-bound regime: one HIP graph per call
             if self._graphed is None or self._graphed.unet is not unet:
                 self._graphed = GraphedUNet(unet)
-            if ctx_m is not None:
-                return self._graphed(x9, t, ctx, paired, ctx_w, ctx_r, ctx_m)
-            if ctx_r is not None:
-                return self._graphed(x9, t, ctx, paired, ctx_w, ctx_r)
-            return self._graphed(x9, t, ctx, paired) if ctx_w is None else self._graphed(x9, t, ctx, paired, ctx_w)
-        if ctx_m is not None:                                                     # the collector covers the last b samples: the conditional half
-            return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step), context_weights=ctx_w, context_regions=ctx_r, context_maps=ctx_m)
-        if ctx_r is not None:
-            return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step), context_weights=ctx_w, context_regions=ctx_r)
-        if ctx_w is not None:                                                     # (without weights: exactly the call made before they existed)
-            return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step), context_weights=ctx_w)
-        return unet.forward_nhwc(x9, t, ctx, paired=paired, step=int(step))      # every row of t is `step`: the embedding rows come from the per-value cache
+            return self._graphed(x9, t, cond, paired)
+        # every row of t is `step`: the embedding rows come from the per-value cache.  A collector covers the last b samples: the conditional half
+        return unet.forward_nhwc(x9, t, cond.context, paired=paired, step=int(step), **cond.kwargs())
 
     def _coef(self, index, weights):
         a_t, a_prev = float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index])
@@ -225,16 +231,21 @@ class PLMSSampler(object):
         ac = float(self.model.alphas_cumprod[int(step)])
         return ops.qsample_blend(x0, self._noise(tuple(x0.shape), x0.device).float(), mask, img, math.sqrt(ac), math.sqrt(1.0 - ac))
 
-    @torch.no_grad()
-    def plms_sampling(self, cond, shape, x_T=None, callback=None, timesteps=None, img_callback=None, log_every_t=100,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, mask=None, x0=None, conditioning_weights=None,
-                      conditioning_regions=None, conditioning_maps=None, **kwargs):
+    # ---- the frame of a run: prelude and loop, shared by the three samplers; each hands the loop its update ------------------------
+    def _begin_run(self, cond, shape, x_T, timesteps, unconditional_guidance_scale, unconditional_conditioning, mask, x0,
+                   conditioning_weights, conditioning_regions, conditioning_maps, kwargs):
+        """The state of one run: img (the start latent), z_inp / msk (the inpainting inputs), cond (the attention.Conditioning every
+        U-Net call of the run gets: one object, so both per-conditioning caches see one identity across the steps), dup (2 = a
+        guidance pair), scale, time_range (reversed; a prefix of the schedule for timesteps=), total, and mask / x0 on the device."""
         device = self.model.betas.device
         if self.require_gpu and device.type != "cuda":
-            raise PbeError("PLMSSampler: the model must live on an MI355X (model.to('cuda')); there is no CPU path")
+            raise PbeError(f"{type(self).__name__}: the model must live on an MI355X (model.to('cuda')); there is no CPU path")
         b = shape[0]
         img = (torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)).contiguous()
-        z_inp, msk = inpaint_kwargs(kwargs)
+        if self.accepts_rest and "rest" in kwargs and "test_model_kwargs" not in kwargs:       # ddim.py:201-202: rest = cat(z_inpaint, mask)
+            z_inp, msk = kwargs["rest"][:, :4], kwargs["rest"][:, 4:5]
+        else:
+            z_inp, msk = inpaint_kwargs(kwargs)
         z_inp = z_inp.to(device=device, dtype=torch.float32).contiguous()
         msk = msk.to(device=device, dtype=torch.float32).contiguous()
         cond = cond.to(device)
@@ -243,41 +254,54 @@ class PLMSSampler(object):
             ctx = guidance_context(cond, unconditional_conditioning, b, device)      # a one-token uc is repeated to cond's K tokens (exact)
         else:
             ctx = cond.to(torch.float16).contiguous()
-        dup = 2 if guided else 1
-        ctx_w = guidance_weights(conditioning_weights, cond, b, guided)
-        ctx_r = guidance_regions(conditioning_regions, cond, b, guided)
-        ctx_m = guidance_maps(conditioning_maps, cond, b, device)
-        scale = float(unconditional_guidance_scale)
-
+        cond = Conditioning(ctx, guidance_weights(conditioning_weights, cond, b, guided), guidance_regions(conditioning_regions, cond, b, guided),
+                            guidance_maps(conditioning_maps, cond, b, device))
         time_range = np.flip(self._schedule_subset(timesteps))
-        total = time_range.shape[0]
         if mask is not None:
             mask, x0 = mask.to(device=device, dtype=torch.float32), x0.to(device=device, dtype=torch.float32)
+        return SimpleNamespace(img=img, z_inp=z_inp, msk=msk, cond=cond, dup=2 if guided else 1, scale=float(unconditional_guidance_scale),
+                               time_range=time_range, total=time_range.shape[0], mask=mask, x0=x0)
+
+    def _run_loop(self, run, update, callback, img_callback, log_every_t):
+        """Per step: blend the known region in (mask / x0), evaluate the U-Net, update(i, index, img, eps) -> (img, pred_x0) - the
+        sampler's own part -, then the callbacks and the log -> (img, {'x_inter', 'pred_x0'})."""
+        img = run.img
         inter = {"x_inter": [img], "pred_x0": [img]}
-        old = []                                                      # newest last, at most 3 (plms.py:163-165)
-        for i, step in enumerate(time_range):
-            index = total - i - 1
-            step_next = time_range[min(i + 1, total - 1)]
-            if mask is not None:
-                img = self._blend_known(img, x0, mask, step)
-            eps = self._eps(img, step, ctx, z_inp, msk, dup, ctx_w, ctx_r, ctx_m)
-            if len(old) == 0:
-                # pseudo improved Euler (plms.py:230-235): probe x_prev with e_t, re-evaluate at t_next, average
-                x_probe, _, e_t = ops.plms_update(eps, dup, scale, img, [], self._coef(index, _AB[0]), want_pred=False)
-                eps2 = self._eps(x_probe, step_next, ctx, z_inp, msk, dup, ctx_w, ctx_r, ctx_m)
-                # e' = (e_t + e_next)/2 : c0 weights the fresh eps (= e_next), history slot 1 = e_t
-                img, pred_x0, _ = ops.plms_update(eps2, dup, scale, img, [e_t], self._coef(index, (0.5, 0.5)), want_e_t=False)
-            else:
-                hist = old[::-1]
-                img, pred_x0, e_t = ops.plms_update(eps, dup, scale, img, hist, self._coef(index, _AB[len(hist)]))
-            old.append(e_t)
-            if len(old) >= 4:
-                old.pop(0)
+        for i, step in enumerate(run.time_range):
+            index = run.total - i - 1
+            if run.mask is not None:
+                img = self._blend_known(img, run.x0, run.mask, step)
+            eps = self._eps(img, step, run.cond, run.z_inp, run.msk, run.dup)
+            img, pred_x0 = update(i, index, img, eps)
             if callback:
                 callback(i)
             if img_callback:
                 img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total - 1:
+            if index % log_every_t == 0 or index == run.total - 1:
                 inter["x_inter"].append(img)
                 inter["pred_x0"].append(pred_x0)
         return img, inter
+
+    @torch.no_grad()
+    def plms_sampling(self, cond, shape, x_T=None, callback=None, timesteps=None, img_callback=None, log_every_t=100,
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, mask=None, x0=None, conditioning_weights=None,
+                      conditioning_regions=None, conditioning_maps=None, **kwargs):
+        run = self._begin_run(cond, shape, x_T, timesteps, unconditional_guidance_scale, unconditional_conditioning, mask, x0,
+                              conditioning_weights, conditioning_regions, conditioning_maps, kwargs)
+        old = []                                                      # newest last, at most 3 (plms.py:163-165)
+
+        def update(i, index, img, eps):
+            if len(old) == 0:
+                # pseudo improved Euler (plms.py:230-235): probe x_prev with e_t, re-evaluate at t_next, average
+                x_probe, _, e_t = ops.plms_update(eps, run.dup, run.scale, img, [], self._coef(index, _AB[0]), want_pred=False)
+                eps2 = self._eps(x_probe, run.time_range[min(i + 1, run.total - 1)], run.cond, run.z_inp, run.msk, run.dup)
+                # e' = (e_t + e_next)/2 : c0 weights the fresh eps (= e_next), history slot 1 = e_t
+                img, pred_x0, _ = ops.plms_update(eps2, run.dup, run.scale, img, [e_t], self._coef(index, (0.5, 0.5)), want_e_t=False)
+            else:
+                hist = old[::-1]
+                img, pred_x0, e_t = ops.plms_update(eps, run.dup, run.scale, img, hist, self._coef(index, _AB[len(hist)]))
+            old.append(e_t)
+            if len(old) >= 4:
+                old.pop(0)
+            return img, pred_x0
+        return self._run_loop(run, update, callback, img_callback, log_every_t)

@@ -445,6 +445,36 @@ class ContextMaps:
         return out
 
 
+class Conditioning:
+    """The cross-attention conditioning of one U-Net call or sampler run, carried as one value: context [B, K, Dc], weights (exemplar
+    weights [B, K]), regions (region maps [B, K, Hr, Wr]) and maps (a ContextMaps collector); any of the last three may be None.  The
+    public entry points build it from their context_weights= / context_regions= / context_maps= keywords; below them it is handed
+    on whole.  It validates nothing: prepare_context_weights / prepare_context_regions do, where the operands are built."""
+    __slots__ = ("context", "weights", "regions", "maps")
+
+    def __init__(self, context, weights=None, regions=None, maps=None):
+        self.context, self.weights, self.regions, self.maps = context, weights, regions, maps
+
+    def key(self):
+        """The identity both per-conditioning caches compare (UNetModel.context_vectors, pbe_amd.graph.GraphedUNet): per tensor its
+        pointer, version, shape, dtype and device, per non-tensor its repr, for the collector its id.  It is the union of the two
+        keys those caches used to build for themselves and changes exactly when either of them did - a tensor of another dtype or
+        device is another storage, so its pointer differs too - hence neither cache hits or misses differently, with one exception
+        that computes the same values: the U-Net's cache, which knew only WHETHER a collector is present, now also rebuilds when
+        the same tensors come with another collector.  A cache that stores the key keeps the tensors alive beside it, so that a
+        pointer cannot be recycled."""
+        def one(v):
+            if isinstance(v, torch.Tensor):
+                return (v.data_ptr(), v._version, tuple(v.shape), v.dtype, str(v.device))
+            return None if v is None else ("values", repr(v))
+        return (one(self.context), one(self.weights), one(self.regions), None if self.maps is None else ("maps", id(self.maps)))
+
+    def kwargs(self):
+        """The keywords of forward_nhwc / forward for what is present: a plain context passes none."""
+        kw = {"context_weights": self.weights, "context_regions": self.regions, "context_maps": self.maps}
+        return {k: v for k, v in kw.items() if v is not None}
+
+
 class RegionalVectors:
     """What SpatialTransformer.context_vectors returns for a context WITH regions: the per-block list and the context's
     ContextRegions.  The level is known only where the grid is: run / run_paired resolve it there (SpatialTransformer._levelled)."""

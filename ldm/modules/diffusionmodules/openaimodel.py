@@ -25,7 +25,7 @@ from torch import nn
 from pbe_amd import ops
 from pbe_amd.hipmodule import HipModule, f32, require_gpu
 from pbe_amd.lib import PbeError
-from ldm.modules.attention import SpatialTransformer, prepare_context_regions, prepare_context_weights
+from ldm.modules.attention import Conditioning, SpatialTransformer, prepare_context_regions, prepare_context_weights
 from ldm.modules.diffusionmodules.util import conv_nd, linear, normalization, timestep_embedding, zero_module
 
 
@@ -239,32 +239,21 @@ class UNetModel(HipModule):
         self.__dict__["_ctx_cache"] = None
         self.__dict__["_emb_cache"] = {}
 
-    def context_vectors(self, context, context_weights=None, context_regions=None, maps=False):
-        """What the 16 transformer blocks need of this context [N, K, context_dim] (cached while the same context tensor is presented,
-        i.e. across the 51 calls of one PLMS run): for K = 1 the per-sample cross-attention constants, for K > 1 tokens per sample the
-        operands of the multi-token cross-attention (BasicTransformerBlock.context_operands).  context_weights: exemplar weights [N, K]
-        or None; the cache key holds the weights tensor's identity and version too (the same context with other weights is another
-        entry), and the weights are validated and uploaded once per entry (attention.prepare_context_weights).  context_regions: region
-        maps [N, K, Hr, Wr] or None (attention.prepare_context_regions), keyed and kept alive exactly as the weights are; the entry's
-        ContextRegions is shared by every transformer, so each level's table is built and uploaded once per entry.  maps: a ContextMaps
-        will collect the attribution maps; the key holds that too, because the levels wider than ctx_fused_max_width then take other
-        operands (ops.CtxOperands instead of ContextKV: BasicTransformerBlock.context_operands)."""
-        def tkey(w):
-            if isinstance(w, torch.Tensor):
-                return (w.data_ptr(), w._version, tuple(w.shape), w.dtype, str(w.device))
-            return None if w is None else ("values", repr(w))
-        w, r = context_weights, context_regions
-        key = (context.data_ptr(), context._version, tuple(context.shape), context.dtype, tkey(w))
-        if r is not None:                     # (without regions: the key as it was)
-            key += (tkey(r),)
-        if maps:                              # (without a collector: the key as it was)
-            key += ("maps",)
+    def context_vectors(self, cond):
+        """What the 16 transformer blocks need of cond (an attention.Conditioning; context [N, K, context_dim]), cached while the same
+        conditioning is presented (Conditioning.key), i.e. across the 51 calls of one PLMS run: for K = 1 the per-sample cross-attention
+        constants, for K > 1 tokens per sample the operands of the multi-token cross-attention (BasicTransformerBlock.context_operands).
+        The weights [N, K] and region maps [N, K, Hr, Wr] are validated and uploaded once per entry (attention.prepare_context_weights /
+        prepare_context_regions); the entry's ContextRegions is shared by every transformer, so each level's table is built and uploaded
+        once per entry.  A collector is part of the key because the levels wider than ctx_fused_max_width then take other operands
+        (ops.CtxOperands instead of ContextKV: BasicTransformerBlock.context_operands)."""
+        key = cond.key()
         c = self.__dict__.get("_ctx_cache")
         if c is None or c[0] != key:
-            cw = prepare_context_weights(context, w)
-            cr = prepare_context_regions(context, r, cw)
-            vecs = {id(st): st.context_vectors(context, cw, cr, maps=bool(maps)) for st in self._transformers()}
-            c = (key, vecs, context, w, r)    # keep `context` (and the weights / regions) alive so a data_ptr cannot be recycled
+            cw = prepare_context_weights(cond.context, cond.weights)
+            cr = prepare_context_regions(cond.context, cond.regions, cw)
+            vecs = {id(st): st.context_vectors(cond.context, cw, cr, maps=cond.maps is not None) for st in self._transformers()}
+            c = (key, vecs, cond)             # keep the context, weights and regions alive so a data_ptr cannot be recycled
             self.__dict__["_ctx_cache"] = c
         return c[1]
 
@@ -324,7 +313,7 @@ class UNetModel(HipModule):
                 maps.bind(context.shape[0], context.shape[1], context.device)
             if maps.K != context.shape[1] or maps.B > context.shape[0]:
                 raise PbeError(f"UNetModel: the ContextMaps collects {maps.B} samples x {maps.K} tokens, the context is {tuple(context.shape)}")
-        ctx = self.context_vectors(context, context_weights, context_regions, maps=maps is not None)
+        ctx = self.context_vectors(Conditioning(context, context_weights, context_regions, maps))
         if step is not None:                                           # the caller vouches that every entry of `timesteps` equals `step` (the samplers do)
             emb_all = self.embedding_rows(step, x16.device).expand(timesteps.shape[0], -1)      # one cached row, stride-0 broadcast over the samples
         else:

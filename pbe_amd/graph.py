@@ -31,38 +31,33 @@ class GraphedUNet:
         self.graph = None
         self.replays = 0
 
-    def __call__(self, x9: torch.Tensor, t: torch.Tensor, ctx: torch.Tensor, paired: bool, ctx_w=None, ctx_r=None, ctx_m=None) -> torch.Tensor:
-        """Same contract as ``unet.forward_nhwc(x9, t, ctx, paired=paired, context_weights=ctx_w, context_regions=ctx_r)``.  The returned tensor is a static buffer that
-        the next call overwrites (the samplers consume it before calling again).  ctx_m: an attention.ContextMaps (context_maps=): the
-        captured launches add to its accumulators, which the eager pass put in place; every replay accumulates exactly as an eager
-        call does, and tells the collector the launch counts the capture recorded."""
-        wkey = None if ctx_w is None else (ctx_w.data_ptr(), ctx_w._version, tuple(ctx_w.shape))      # (a tensor: plms.guidance_weights)
-        key = (tuple(x9.shape), tuple(t.shape), ctx.data_ptr(), ctx._version, tuple(ctx.shape), bool(paired), wkey)
-        kw = {"context_weights": ctx_w}
-        if ctx_r is not None:                                                                         # (a tensor: plms.guidance_regions)
-            key += ((ctx_r.data_ptr(), ctx_r._version, tuple(ctx_r.shape)),)
-            kw["context_regions"] = ctx_r
-        if ctx_m is not None:                                                                         # (the collector itself: its accumulators are baked in)
-            key += (("maps", id(ctx_m)),)
-            kw["context_maps"] = ctx_m
+    def __call__(self, x9: torch.Tensor, t: torch.Tensor, cond, paired: bool) -> torch.Tensor:
+        """Same contract as ``unet.forward_nhwc(x9, t, cond.context, paired=paired, **cond.kwargs())`` for cond, an
+        attention.Conditioning.  The graph is captured again when the shapes, ``paired`` or the conditioning (Conditioning.key)
+        change.  The returned tensor is a static buffer that the next call overwrites (the samplers consume it before calling
+        again).  With a collector (cond.maps) the captured launches add to its accumulators, which the eager pass put in place;
+        every replay accumulates exactly as an eager call does, and tells the collector the launch counts the capture recorded."""
+        key = (tuple(x9.shape), tuple(t.shape), bool(paired), cond.key())
+        maps = cond.maps                               # (the collector itself: its accumulators are baked in)
         if key != self.key:
-            self.sx, self.st, self.ctx, self.ctx_w, self.ctx_r, self.ctx_m = x9.clone(), t.clone(), ctx, ctx_w, ctx_r, ctx_m
-            out = self.unet.forward_nhwc(self.sx, self.st, ctx, paired=paired, **kw)     # eager: builds packs / caches / function attributes
+            self.sx, self.st, self.cond = x9.clone(), t.clone(), cond      # (cond: keeps the keyed tensors alive)
+            kw = cond.kwargs()
+            out = self.unet.forward_nhwc(self.sx, self.st, cond.context, paired=paired, **kw)     # eager: builds packs / caches / function attributes
             torch.cuda.current_stream().synchronize()
             g = torch.cuda.CUDAGraph()
-            if ctx_m is not None:
-                ctx_m.begin_tape()                     # captured launches run at replay: counted there
+            if maps is not None:
+                maps.begin_tape()                      # captured launches run at replay: counted there
             try:
                 with torch.cuda.graph(g):
-                    self.out = self.unet.forward_nhwc(self.sx, self.st, ctx, paired=paired, **kw)
+                    self.out = self.unet.forward_nhwc(self.sx, self.st, cond.context, paired=paired, **kw)
             finally:
-                self.tape = ctx_m.end_tape() if ctx_m is not None else None
+                self.tape = maps.end_tape() if maps is not None else None
             self.graph, self.key = g, key
             return out
         self.sx.copy_(x9)
         self.st.copy_(t)
         self.graph.replay()
-        if ctx_m is not None:
-            ctx_m.replayed(self.tape)
+        if maps is not None:
+            maps.replayed(self.tape)
         self.replays += 1
         return self.out

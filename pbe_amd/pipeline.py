@@ -116,17 +116,15 @@ def inpaint(model, image: torch.Tensor, mask: torch.Tensor, ref: torch.Tensor, *
         smp = DPMSolverSampler(model)
     else:
         smp = (PLMSSampler if sampler == "plms" else DDIMSampler)(model)
-    more = {} if ref_regions is None else {"conditioning_regions": ref_regions}
-    if seeds is not None:
-        more["seeds"], more["seed_sub"] = seeds, seed_sub
+    more = {} if seeds is None else {"seeds": seeds, "seed_sub": seed_sub}
     cm = None
     if return_ref_maps:
         from ldm.modules.attention import ContextMaps
-        cm = more["conditioning_maps"] = ContextMaps()
+        cm = ContextMaps()
     z0, _ = smp.sample(S=steps, batch_size=B, shape=list(z_inp.shape[1:]), conditioning=c, verbose=False,
                        unconditional_guidance_scale=scale, unconditional_conditioning=uc, eta=0.0, x_T=x_T,
                        test_model_kwargs={"inpaint_image": z_inp, "inpaint_mask": m_lat}, conditioning_weights=ref_weights,
-                       **more)
+                       conditioning_regions=ref_regions, conditioning_maps=cm, **more)
     if ev:
         ev[3].record()
     img = ops.image_post(model.decode_first_stage_nhwc(z0))                              # inference.py:346-347

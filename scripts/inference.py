@@ -473,18 +473,18 @@ def main(argv=None):
             extra_seeds = {"seeds": list(opt.seeds)}
         else:
             extra_seeds = {}
-        cr, extra = None, {}
+        cr = None
         if opt.reference_region is not None:                                           # one map per exemplar token, the same for every sample
             cr = load_regions(opt.reference_region, z_inpaint.shape[-2:], device, win).expand(c.shape[0], -1, -1, -1).contiguous()
-            extra["conditioning_regions"] = cr
         cm = None
         if opt.save_reference_maps:
             from ldm.modules.attention import ContextMaps
-            cm = extra["conditioning_maps"] = ContextMaps()
+            cm = ContextMaps()
         shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
         samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=nb, shape=shape, verbose=False,
                                     unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc, eta=opt.ddim_eta,
-                                    x_T=start_code, test_model_kwargs=test_model_kwargs, conditioning_weights=cw, **extra, **extra_seeds)
+                                    x_T=start_code, test_model_kwargs=test_model_kwargs, conditioning_weights=cw, conditioning_regions=cr,
+                                    conditioning_maps=cm, **extra_seeds)
         xd = ops.image_post(model.decode_first_stage_nhwc(samples))                  # clamp((x+1)/2, 0, 1), still on the GPU
         tags = [opt.seed] * xd.shape[0] if opt.seeds is None else list(opt.seeds)      # what names sample i's files
         if not opt.skip_save:
